@@ -7,9 +7,14 @@
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
         bench.py --gpus N --steps K --warmup W
 
-Rank 0 prints ONE JSON line.
+Rank 0 prints ONE JSON line.  A plain run sets up, warms up, times the steps and prints the headline (`value`,
+`ms_per_step`, `step_ms`); `--full` adds everything else described below (`roofline` / `top_kernels`, `cpu_baseline`,
+and the other model families under `extra`).  `--dump-outputs DIR` writes what the last timed step computed -- the loss,
+the model's outputs, the parameters after the optimizer step and their gradients -- as DIR/<name>.npy (float32, integer
+outputs as float64; an array above its share of 64 MB is a fixed seeded sample of its elements), so that two builds can
+be compared output for output on the same seeded inputs.
 
-`roofline`: measured live with HIP events on a sample of the timed steps (one in 20: ~520 event records cost a step ~8 ms).
+`roofline` (`--full`): measured live with HIP events on a sample of the timed steps (one in 20: ~520 event records cost a step ~8 ms).
 The events are recorded INSIDE the library calls, immediately around each kernel, on the stream it is launched on.
 The object describes the dominant kernel family of the step -- ALL sparse-convolution launches (forward,
 backward-data, backward-weight: the SURVEY 8d / BASELINE.md figure, sum over the layers of
@@ -22,7 +27,7 @@ script; corrections as MI355X_MICROARCH.md prescribes) and is null when that fil
 other kernel sources than the ones running (`kernel_source_digest`).  `step_ms` = median / min / max / mean of the
 per-step durations between HIP events at the step boundaries; `ms_per_step` = wall time of the timed region / steps.
 
-`cpu_baseline` times the same training step on the host cores with every operator served by the CPU oracle (a PORT
+`cpu_baseline` (`--full`) times the same training step on the host cores with every operator served by the CPU oracle (a PORT
 of the reference algorithms -- the reference's own CPU path needs MinkowskiEngine, which is not available), on a
 bounded sample (one ~150k-point scene: 1 warm-up + 3 timed steps, median), N=1 / rank 0 only, with a per-operator
 breakdown; `--cpu-config1` runs BASELINE config 1 (4 x ~20k-point scenes) instead.
@@ -81,7 +86,8 @@ def build(cfg, device, seed=0):
 PREFETCH_AT = os.environ.get("MS3D_PREFETCH_AT", "grouping")
 
 
-def train_step(model, ddp, opt, batch, next_batch=None):
+def train_step(model, ddp, opt, batch, next_batch=None, keep=None):
+    """one training step; `keep` (a dict) receives the step's forward outputs and loss (--dump-outputs)"""
     opt.zero_grad(set_to_none=True)
     # input pipelining, as a data loader would do it: the coordinate-only work of the NEXT batch (row order, kernel maps,
     # pair lists) is built on its own stream -- issued right behind this step's backbone, so that it runs inside the
@@ -105,6 +111,8 @@ def train_step(model, ddp, opt, batch, next_batch=None):
         prefetch()
     loss.backward()
     opt.step()
+    if keep is not None:
+        keep["out"], keep["loss"] = out, loss
     return loss
 
 
@@ -279,12 +287,50 @@ def roofline_report(groups, n_sampled, lib, model_name="pointgroup"):
     return roof, top
 
 
+# --------------------------------------------------------------------------------------------- --dump-outputs
+DUMP_BYTES = 64 << 20       # all files together
+DUMP_SEED = 20240601        # the sample of a large array: the same elements in every run with the same arguments
+
+
+def _flatten_outputs(prefix, obj, into):
+    """name -> tensor for every tensor in a (nested) output structure; private entries ('_...': stream events, packs of
+    the scheduling machinery) are not outputs of the step"""
+    if torch.is_tensor(obj):
+        into[prefix] = obj
+    elif isinstance(obj, dict):
+        for k, v in obj.items():
+            if not str(k).startswith("_"):
+                _flatten_outputs(f"{prefix}.{k}", v, into)
+    elif isinstance(obj, (list, tuple)):
+        for i, v in enumerate(obj):
+            _flatten_outputs(f"{prefix}.{i}", v, into)
+
+
+def dump_outputs(path, model, keep):
+    """what the last timed step handed back: loss, forward outputs, parameters after the optimizer step, gradients"""
+    arrays = {"loss": keep["loss"].detach()}
+    _flatten_outputs("out", keep["out"], arrays)
+    params = list(model.parameters())      # in registration order, concatenated
+    arrays["params"] = torch.cat([p.detach().reshape(-1).float() for p in params])
+    arrays["grads"] = torch.cat([(p.grad if p.grad is not None else torch.zeros_like(p)).detach().reshape(-1).float()
+                                 for p in params])
+    os.makedirs(path, exist_ok=True)
+    share = DUMP_BYTES // len(arrays)
+    for name, t in sorted(arrays.items()):
+        a = t.detach().cpu().numpy()
+        a = a.astype(np.float64 if a.dtype.kind in "iu" or a.dtype == np.float64 else np.float32)
+        if a.nbytes > share:          # a fixed seeded sample of the elements, in index order
+            idx = np.sort(np.random.default_rng(DUMP_SEED).choice(a.size, share // a.itemsize, replace=False))
+            a = a.reshape(-1)[idx]
+        np.save(os.path.join(path, name + ".npy"), a)
+
+
 def other_model_line(model_name, args):
     """BASELINE configs 3 / 4 for the driver's one JSON line: the same benchmark for another model family, run in a CHILD
     process after (outside) the timed headline region -- a fresh process, so nothing of it touches the headline numbers"""
     import subprocess
     cmd = [sys.executable, os.path.abspath(__file__), "--model", model_name, "--gpus", "1", "--steps", str(args.steps),
-           "--warmup", str(args.warmup), "--batch", str(args.batch), "--no-cpu-baseline", "--also", "none"]
+           "--warmup", str(args.warmup), "--batch", str(args.batch), "--no-cpu-baseline", "--also", "none", "--full"]
     try:
         r = subprocess.run(cmd, capture_output=True, text=True, timeout=900)
         d = json.loads(r.stdout.strip().splitlines()[-1])
@@ -309,17 +355,23 @@ def main(argv=None):
     ap.add_argument("--density", type=float, default=1700.0,
                     help="points per m^2 of the synthetic scenes (1700 = the ~150k-point headline workload; small "
                          "values expose the host launch floor)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline does not need: roofline / top_kernels (kernel events on sampled "
+                         "steps), cpu_baseline, and the other model families of --also auto; off = a lean headline run")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write what the last one computed as DIR/<name>.npy (rank 0)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--cpu-config1", action="store_true", help="cpu_baseline on BASELINE config 1 (4 x ~20k-point scenes)")
     ap.add_argument("--no-roofline", action="store_true")
-    ap.add_argument("--all-kernels", action="store_true", help="print every timed kernel group to stderr")
+    ap.add_argument("--all-kernels", action="store_true",
+                    help="print every timed kernel group to stderr (turns the kernel events on, also without --full)")
     ap.add_argument("--override", action="append", default=[], help="Hydra-style key=value on top of the model's config")
     ap.add_argument("--scene", default=None, help="JSON keyword arguments of synthetic.make_scene (smaller scenes)")
     ap.add_argument("--also", default="auto",
                     help="comma list of the other model families (hais,softgroup) to run AFTER the timed headline region, "
                          "each in its own child process, and report under `extra` (BASELINE configs 3 / 4: value, "
                          "ms_per_step, roofline.frac); 'none' = off; 'auto' = hais,softgroup for the plain headline "
-                         "invocation (PointGroup, one GPU, roofline and cpu_baseline on), none otherwise")
+                         "invocation with --full (PointGroup, one GPU, roofline and cpu_baseline on), none otherwise")
     ap.add_argument("--device", default="cuda", choices=["cuda", "cpu"],
                     help="cpu = DRY RUN of the launch / sharding / barrier / max-over-ranks / reporting path on host "
                          "tensors over gloo (tests/bench_dryrun.py installs the operator backend); never a measurement")
@@ -358,7 +410,7 @@ def main(argv=None):
     n_vox = float(np.mean([b["voxel_xyz"].shape[0] for b in batches])) / args.batch
 
     timer = None
-    if not args.no_roofline and rank == 0 and not dry:
+    if (args.full or args.all_kernels) and not args.no_roofline and rank == 0 and not dry:
         timer = ms_backend.KernelTimer(be.lib)
         timer.reserve(700 * (args.steps // SAMPLE_EVERY + 1))
         be.kernel_timer = timer
@@ -381,13 +433,15 @@ def main(argv=None):
         def record(self): self.t = time.perf_counter()
         def elapsed_time(self, other): return 1000.0 * (other.t - self.t)
     marks = [_HostMark() if dry else torch.cuda.Event(enable_timing=True) for _ in range(args.steps + 1)]
+    last = {} if args.dump_outputs and rank == 0 else None     # the last timed step's outputs (--dump-outputs)
     t0 = time.perf_counter()
     marks[0].record()
     for i in range(args.steps):
         if timer is not None:
             timer.sampling = (i % SAMPLE_EVERY == SAMPLE_EVERY // 2) or (args.steps <= SAMPLE_EVERY // 2 and i == args.steps - 1)
             n_sampled += int(timer.sampling)
-        loss = train_step(model, ddp, opt, batches[i % args.pool], batches[(i + 1) % args.pool])
+        loss = train_step(model, ddp, opt, batches[i % args.pool], batches[(i + 1) % args.pool],
+                          keep=last if i == args.steps - 1 else None)
         marks[i + 1].record()
     sync_all()
     dt = time.perf_counter() - t0
@@ -399,6 +453,8 @@ def main(argv=None):
         torch.distributed.all_reduce(t, op=torch.distributed.ReduceOp.MAX)
         dt = float(t.item())
     assert torch.isfinite(loss).item(), "loss is not finite"
+    if last is not None:
+        dump_outputs(args.dump_outputs, model, last)
 
     if rank == 0:
         scenes = world * args.batch * args.steps
@@ -447,11 +503,11 @@ def main(argv=None):
             line["dry_run"] = "host tensors over gloo: exercises the launch path only, the numbers mean nothing"
             if rank_report is not None:
                 line["dry_run_ranks"] = rank_report
-        if world == 1 and not args.no_cpu_baseline and not dry:
+        if args.full and world == 1 and not args.no_cpu_baseline and not dry:
             line["cpu_baseline"] = cpu_baseline(cfg, config1=args.cpu_config1)
         also = args.also
         if also == "auto":
-            plain = (args.model == "pointgroup" and world == 1 and not dry and not args.no_roofline
+            plain = (args.full and args.model == "pointgroup" and world == 1 and not dry and not args.no_roofline
                      and not args.no_cpu_baseline and not args.override and not args.scene and args.density == 1700.0)
             also = "hais,softgroup" if plain else "none"
         if also != "none" and world == 1 and not dry:

@@ -41,6 +41,30 @@ def test_driver_launch_line_on_gloo(world):
     assert rec["step_ms"]["min"] <= rec["step_ms"]["median"] <= rec["step_ms"]["max"]
 
 
+def test_dump_outputs_are_the_same_on_the_same_arguments(tmp_path):
+    """--dump-outputs DIR: the last timed step's loss, model outputs, parameters and gradients as float32 / float64 .npy
+    files within 64 MB, identical from run to run with the same arguments (two builds compare output for output)"""
+    import numpy as np
+    tail = ["--gpus", "1", "--steps", "2", "--warmup", "1", "--batch", "1", "--pool", "2", "--scene", SCENE,
+            "--override", "model.network.blocks=[1,2]"]
+    env = dict(os.environ, OMP_NUM_THREADS="1", MS3D_DIST_BACKEND="gloo")
+    dumps = []
+    for run in ("a", "b"):
+        d = tmp_path / run
+        out = subprocess.run([sys.executable, os.path.join(ROOT, "tests", "bench_dryrun.py")] + tail +
+                             ["--dump-outputs", str(d)], env=env, capture_output=True, text=True, timeout=600, cwd=ROOT)
+        assert out.returncode == 0, out.stderr[-3000:]
+        rec = json.loads([ln for ln in out.stdout.splitlines() if ln.startswith("{")][-1])
+        assert rec["steps"] == 2 and "roofline" not in rec and "cpu_baseline" not in rec and "extra" not in rec
+        dumps.append({f.name: np.load(f) for f in sorted(d.glob("*.npy"))})
+    a, b = dumps
+    assert {"loss.npy", "params.npy", "grads.npy", "out.semantic_scores.npy", "out.point_offsets.npy"} <= set(a)
+    assert sum(v.nbytes for v in a.values()) <= 64 << 20
+    assert all(v.dtype in (np.float32, np.float64) for v in a.values())
+    assert set(a) == set(b) and all(np.array_equal(a[k], b[k]) for k in a)
+    assert np.isfinite(a["loss.npy"]).all() and np.abs(a["grads.npy"]).max() > 0
+
+
 def test_eight_ranks_get_disjoint_scenes_and_cores():
     """BASELINE config 4's process layout (8 ranks on one node, LOCAL_WORLD_SIZE = 8) on host processes over gloo: every
     rank trains on its own scenes (no scene id twice) and -- when the container has the cores -- on its own core slice;

@@ -18,7 +18,7 @@ for n, hi in ((575000, 430000), (800000, 120000), (800000, 575000)):
             print(n, hi, dt, "stable" if stable else "unstable", "%.1f us" % ((time.perf_counter() - t0) / 20 * 1e6))
 PY
 for dyn in 0 1 0 1; do
-  MS3D_PL_DYNAMIC=$dyn python bench.py --steps 40 --warmup 8 --no-cpu-baseline --also none 2>/dev/null | tail -1 | python -c "
+  MS3D_PL_DYNAMIC=$dyn python bench.py --steps 40 --warmup 8 --full --no-cpu-baseline --also none 2>/dev/null | tail -1 | python -c "
 import sys, json; d = json.loads(sys.stdin.read()); print('dyn=$dyn', d['value'], d['step_ms'], d['roofline']['frac'])" >> gpurun_out/r5_ab.log 2>&1
 done
 cat gpurun_out/r5_det.log gpurun_out/r5_sort.log gpurun_out/r5_ab.log
