@@ -272,7 +272,7 @@ int ms3d_spconv_prep_weights_pair(const float *W, int K, int Cin, int Cout, int 
  * ms3d_spconv_prep_weights_multi must ask for the streamed images: field `stream`) */
 int ms3d_spconv_wants_stream_image(int K, int Cin, int Cout);
 /* what the aux slot (2n floats) behind each weight image of a layer buffer holds: 0 nothing, 1 the streamed f32 image,
- * 2 the three-piece bf16 image (wide square layers).  Layer buffer = [image n | aux 2n | transposed image n | aux 2n],
+ * 2 the three-piece bf16 image (wide square layers; 3 / 4: two- / one-piece, ms3d_spconv_aux_kind_p).  Layer buffer = [image n | aux 2n | transposed image n | aux 2n],
  * n = ms3d_spconv_wf_floats(K, Cin, Cout). */
 int ms3d_spconv_aux_kind(int K, int Cin, int Cout);
 /* Both images of n layers in ONE launch (a U-Net re-lays ~90 weight tensors per step, ~5 us of dispatch each).
@@ -344,6 +344,42 @@ int ms3d_spconv_layer_backward(const float *x, const float *dy, const float *wf_
                                                               launched either but described here; int[4] of the buffer =
                                                               variant (0: it was launched as usual), int[1..3] = its grid */,
                                ms3d_stream_t stream);
+/* Matmul precision (torch.set_float32_matmul_precision) of the *_p entry points: precision 0 = "highest", 1 = "high",
+ * 2 = "medium"; anything else returns MS3D_E_UNSUPPORTED (size queries: 0).  It changes only the routes that run on
+ * bf16 pieces at precision 0 -- forward / backward-data with both sides >= 48 channels, backward-weight of the wide
+ * K = 27 layers -- which then keep P = 3 / 2 / 1 pieces of the same split, x0 = bf16_rne(x), x1 = bf16_rne(x - x0),
+ * x2 = bf16_rne(x - x0 - x1), taken of the activated input (after the fused BatchNorm / ReLU) and of the weights / dy:
+ *   P = 3: x0w0 + x0w1 + x1w0 + x1w1 + x0w2 + x2w0 (float32 grade), P = 2: x0w0 + x0w1 + x1w0, P = 1: x0w0,
+ * each product exact in the f32 accumulator.  Every other route is exact float32 at every precision.  The existing
+ * entry points are the precision-0 forms of these.
+ * aux_kind_p: the aux image kind of a layer at that precision (2 / 3 / 4 = bf16 image of 3 / 2 / 1 pieces; what
+ * ms3d_spconv_prep_weights_multi's `stream` field takes).  layer_backward_p must be given the precision its
+ * layer_forward_p laid wf_buf out with.  wgrad_pieces: pieces of the backward-weight kernel (0 = f32 kernel).
+ * wgrad_ws_floats_p <= ms3d_spconv_wgrad_ws_floats; ms3d_spconv_layer_ws_floats bounds every precision. */
+int ms3d_spconv_aux_kind_p(int K, int Cin, int Cout, int precision);
+/* ms3d_spconv_prep_weights_multi for the descriptors of one precision: bf16 images are written for the layers whose
+ * `stream` is ms3d_spconv_aux_kind_p(.., precision) (the precision-0 entry point writes those of kind 2) */
+int ms3d_spconv_prep_weights_multi_p(const void *descs, int n, int total_blocks, int precision, ms3d_stream_t stream);
+int ms3d_spconv_wgrad_pieces(int Vout, int K, int Cin, int Cout, int offset_list, int precision);
+size_t ms3d_spconv_wgrad_ws_floats_p(int Vout, int K, int Cin, int Cout, int precision);
+int ms3d_spconv_backward_weight_p(const float *in, const float *dout, const int *nbr, int Vout, int K, int Cin,
+                                  int Cout, float *dW, const float *pre_scale, const float *pre_shift, int pre_relu,
+                                  float *partial_ws, const int *ol_kt_start, const int *ol_entries, int precision,
+                                  ms3d_stream_t stream);
+int ms3d_spconv_layer_forward_p(const float *x, const float *W, const int *nbr_fwd, int Vout, int K, int Cin, int Cout,
+                                int mirror_bwd, const float *pre_scale, const float *pre_shift, int pre_relu,
+                                const float *residual, const float *bias, float *wf_buf, float *y, float *stat_partial,
+                                const int *pl_tile_start, const int *pl_entries, void *ev_start, void *ev_stop,
+                                int precision, ms3d_stream_t stream);
+int ms3d_spconv_layer_backward_p(const float *x, const float *dy, const float *wf_buf, const int *nbr_fwd,
+                                 const int *nbr_bwd, int Vin, int Vout, int K, int Cin, int Cout, const float *scale,
+                                 const float *shift, const float *mean, const float *invstd, int pre_relu, int training,
+                                 int need_dx, float *dx, const float *dx_add, float *dgb, float *dW, float *ws,
+                                 const int *ol_fwd_kt_start, const int *ol_fwd_entries, const int *pl_bwd_tile_start,
+                                 const int *pl_bwd_entries, void *ev_start, void *ev_stop, void *ev_wg_start,
+                                 void *ev_wg_stop, float *ws_wgrad, ms3d_stream_t wgrad_stream, int join,
+                                 float *wgrad_slabs, int *wgrad_deferred_nblk, void *wgrad_deferred_launch, int precision,
+                                 ms3d_stream_t stream);
 /* Deferred backward-weight launches of MANY layers of one variant as one launch: descs = DEVICE array of the 128-byte
  * descriptions, each with its first int set to the layer's first block (blocks are numbered layer after layer, a layer
  * has int[1] * int[2] * int[3] of them), total_blocks = their sum.  x, dy, the tables and the slab areas the descriptions

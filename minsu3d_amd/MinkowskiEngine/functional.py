@@ -5,9 +5,66 @@
                  BN-backward channel sums, one elementwise BN-backward pass, one backward-weight launch.
   BNActFn      : stand-alone BN(+ReLU) for tensors whose consumer is not a convolution.
 """
+import contextlib
+import threading
+
 import torch
 
 from ..backend import get_backend
+
+# ---- matmul precision of the convolutions (torch.set_float32_matmul_precision)
+# "highest" = float32 grade everywhere; "high" / "medium" let the wide layers' bf16 kernels keep two / one of the three
+# bf16 pieces of each operand (csrc/spconv.hip, include/minsu3d_hip.h: the *_p entry points).  A forward pass reads the
+# switch ONCE (GeneralModel.__call__, or every convolution called outside a model forward) and its autograd nodes keep
+# that value for their backward, whatever the switch says by then.
+PRECISION_CODES = {"highest": 0, "high": 1, "medium": 2}
+_pass = threading.local()
+
+
+def precision_code(name):
+    """torch.get_float32_matmul_precision() string -> the C ABI's code (0 highest, 1 high, 2 medium)"""
+    try:
+        return PRECISION_CODES[name]
+    except KeyError:
+        raise ValueError(f"unknown float32 matmul precision {name!r}") from None
+
+
+@contextlib.contextmanager
+def pass_precision(code):
+    """every convolution inside the block runs at `code` (GeneralModel.__call__: one read of the switch per forward)"""
+    prev = getattr(_pass, "code", None)
+    _pass.code = code
+    try:
+        yield
+    finally:
+        _pass.code = prev
+
+
+def conv_precision(be=None):
+    """the precision code a convolution forward runs at: the enclosing pass's, else the switch's current value.  0 for
+    a backend without bf16 kernels (the float64 oracle)."""
+    code = getattr(_pass, "code", None)     # (set only to what this function returned for the pass's backend)
+    if code is not None:
+        return code
+    be = be if be is not None else get_backend()
+    if not getattr(be, "matmul_precision_aware", False):
+        return 0
+    return precision_code(torch.get_float32_matmul_precision())
+
+
+_PK = ({}, {"precision": 1}, {"precision": 2})
+
+
+def _pk(code):
+    """keyword argument of the backend's convolution calls (absent at 0: every backend takes that call); read only"""
+    return _PK[code]
+
+
+def _ready(W, tok, code):
+    """the weight buffer prepare_conv_weights stamped on W for this window AND this precision, else None (the
+    convolution then lays its images out itself: a kernel never reads an image laid out for another piece count)"""
+    r = getattr(W, "_ms3d_wf", None)
+    return r[0] if (r is not None and r[1] == tok and r[2] == code) else None
 
 
 class ConvSpec:
@@ -77,13 +134,14 @@ class SparseConvFn(torch.autograd.Function):
     def forward(ctx, x, W, gamma, beta, residual, spec, bn, want_stats, skip=None):
         be = get_backend()
         pre = (bn["scale"], bn["shift"]) if bn is not None else None
+        prec = ctx.prec = conv_precision(be)
         # weight images laid out for the whole model in one launch at the start of its forward (modules.prepare_conv_weights):
-        # the stamp on the parameter says whether that buffer still holds the current weights
-        ready = getattr(W, "_ms3d_wf", None)
-        ready = ready[0] if (ready is not None and ready[1] == getattr(be, "weight_token", None)) else None
+        # the stamp on the parameter says whether that buffer still holds the current weights, laid out for this precision
+        ready = _ready(W, getattr(be, "weight_token", None), prec)
         y, stats, wf_buf = be.conv_layer_forward(x, W.view(spec.K, spec.cin, spec.cout), spec.nbr_fwd, spec.vout, spec.K,
                                                  spec.cin, spec.cout, spec.mirror, pre, bool(bn and bn["relu"]), residual,
-                                                 None, want_stats, **({"wf_ready": ready} if ready is not None else {}))
+                                                 None, want_stats, **({"wf_ready": ready} if ready is not None else {}),
+                                                 **_pk(prec))
         if stats is None:
             stats = x.new_zeros(0)
         ctx.spec, ctx.bn, ctx.wf_buf, ctx.has_res = spec, bn, wf_buf, residual is not None
@@ -119,7 +177,7 @@ class SparseConvFn(torch.autograd.Function):
             dz, dgb = be.bn_bwd_reduce(da, x, bn["scale"], bn["shift"], bn["mean"], bn["invstd"], False)
             dx = (be.bn_bwd_apply(dz, x, bn["scale"], bn["mean"], bn["invstd"], dgb) if bn["training"] else dz * bn["scale"])
             dW = be.conv_backward_weight(x, dy, spec.nbr_fwd, spec.vout, spec.K, spec.cin, spec.cout,
-                                         pre=(bn["scale"], bn["shift"]), pre_relu=False)
+                                         pre=(bn["scale"], bn["shift"]), pre_relu=False, **_pk(ctx.prec))
         else:
             fused = add is not None and ctx.needs_input_grad[0] and be.fuses_dx_add(bn)
             extra = {"dx_add": add} if fused else {}
@@ -131,7 +189,8 @@ class SparseConvFn(torch.autograd.Function):
                 # gradient, the accumulation into an existing .grad): this layer's backward-weight is joined now
                 extra["join_now"] = True
             dx, dgb, dW = be.conv_layer_backward(x, dy, ctx.wf_buf, spec.nbr_fwd, spec.nbr_bwd, spec.vin, spec.vout,
-                                                 spec.K, spec.cin, spec.cout, bn, ctx.needs_input_grad[0], **extra)
+                                                 spec.K, spec.cin, spec.cout, bn, ctx.needs_input_grad[0], **extra,
+                                                 **_pk(ctx.prec))
             if fused:
                 add = None
         if add is not None and dx is not None:
@@ -158,16 +217,14 @@ class ResBlockFn(torch.autograd.Function):
         be = get_backend()
         V = spec.vout
         tok = getattr(be, "weight_token", None)
-        r1 = getattr(W1, "_ms3d_wf", None)
-        r1 = r1[0] if (r1 is not None and r1[1] == tok) else None
-        r2 = getattr(W2, "_ms3d_wf", None)
-        r2 = r2[0] if (r2 is not None and r2[1] == tok) else None
+        prec = ctx.prec = conv_precision(be)
+        r1, r2 = _ready(W1, tok, prec), _ready(W2, tok, prec)
         fast = None
         if (r1 is not None and r2 is not None and spec.cin == spec.cout and torch.is_tensor(stats_in) and x.is_contiguous()
                 and hasattr(be, "res_block_forward")):
             # round 6: the four calls below from ONE host call (same library calls, same order, same stream)
             fast = be.res_block_forward(x, stats_in, r1, r2, spec.nbr_fwd, V, spec.cout, bn0, g0.detach(), b0.detach(), bn1,
-                                        g1.detach(), b1.detach(), want_stats)
+                                        g1.detach(), b1.detach(), want_stats, **_pk(prec))
         if fast is not None:
             y1, y2, st2, (m0, i0, s0, h0), (m1, i1, s1, h1) = fast
             wf1, wf2 = r1, r2
@@ -175,11 +232,11 @@ class ResBlockFn(torch.autograd.Function):
             m0, i0, s0, h0 = be.bn_finalize(stats_in, V, bn0.eps, bn0.momentum, g0.detach(), b0.detach(), bn0.running_mean,
                                             bn0.running_var)
             y1, st1, wf1 = be.conv_layer_forward(x, W1, spec.nbr_fwd, V, 27, spec.cin, spec.cout, True, (s0, h0), True, None,
-                                                 None, True, **({"wf_ready": r1} if r1 is not None else {}))
+                                                 None, True, **({"wf_ready": r1} if r1 is not None else {}), **_pk(prec))
             m1, i1, s1, h1 = be.bn_finalize(st1, V, bn1.eps, bn1.momentum, g1.detach(), b1.detach(), bn1.running_mean,
                                             bn1.running_var)
             y2, st2, wf2 = be.conv_layer_forward(y1, W2, spec.nbr_fwd, V, 27, spec.cout, spec.cout, True, (s1, h1), True, x,
-                                                 None, want_stats, **({"wf_ready": r2} if r2 is not None else {}))
+                                                 None, want_stats, **({"wf_ready": r2} if r2 is not None else {}), **_pk(prec))
         ctx.spec, ctx.wf = spec, (wf1, wf2)
         ctx.bn = (dict(scale=s0, shift=h0, mean=m0, invstd=i0, relu=True, training=True),
                   dict(scale=s1, shift=h1, mean=m1, invstd=i1, relu=True, training=True))
@@ -199,10 +256,11 @@ class ResBlockFn(torch.autograd.Function):
         dy = dy.contiguous()
         V, c0, c1 = spec.vout, spec.cin, spec.cout
         e2 = {"defer": _queue(ctx.defer[1])} if _queue(ctx.defer[1]) is not None else {}
-        dx1, dgb1, dW2 = be.conv_layer_backward(y1, dy, ctx.wf[1], spec.nbr_fwd, spec.nbr_bwd, V, V, 27, c1, c1, ctx.bn[1], True, **e2)
+        dx1, dgb1, dW2 = be.conv_layer_backward(y1, dy, ctx.wf[1], spec.nbr_fwd, spec.nbr_bwd, V, V, 27, c1, c1, ctx.bn[1], True, **e2,
+                                                **_pk(ctx.prec))
         e1 = {"defer": _queue(ctx.defer[0])} if _queue(ctx.defer[0]) is not None else {}
         dx, dgb0, dW1 = be.conv_layer_backward(x, dx1, ctx.wf[0], spec.nbr_fwd, spec.nbr_bwd, V, V, 27, c0, c1, ctx.bn[0],
-                                               ctx.needs_input_grad[0], dx_add=dy, **e1)
+                                               ctx.needs_input_grad[0], dx_add=dy, **e1, **_pk(ctx.prec))
         return dx, dW1.view_as(W1), dgb0[1], dgb0[0], dW2.view_as(W2), dgb1[1], dgb1[0], None, None, None, None, None
 
 
@@ -218,10 +276,11 @@ class ResBlockDownFn(torch.autograd.Function):
         be = get_backend()
         V, cin, cout = spec.vout, spec.cin, spec.cout
         tok = getattr(be, "weight_token", None)
+        prec = ctx.prec = conv_precision(be)
 
         def ready(W):
-            r = getattr(W, "_ms3d_wf", None)
-            return {"wf_ready": r[0]} if (r is not None and r[1] == tok) else {}
+            r = _ready(W, tok, prec)
+            return dict({"wf_ready": r} if r is not None else {}, **_pk(prec))
 
         skip, _, wfd = be.conv_layer_forward(x, Wd.view(1, cin, cout), ident, V, 1, cin, cout, False, None, False, None, None,
                                              False, **ready(Wd))
@@ -255,7 +314,7 @@ class ResBlockDownFn(torch.autograd.Function):
         x, y1, Wd, W1, W2 = ctx.saved_tensors
         dy = dy.contiguous()
         V, cin, cout = spec.vout, spec.cin, spec.cout
-        ex = lambda d: ({"defer": _queue(d)} if _queue(d) is not None else {})
+        ex = lambda d: dict({"defer": _queue(d)} if _queue(d) is not None else {}, **_pk(ctx.prec))
         dx1, dgb1, dW2 = be.conv_layer_backward(y1, dy, ctx.wf[2], spec.nbr_fwd, spec.nbr_bwd, V, V, 27, cout, cout, ctx.bn[1],
                                                 True, **ex(ctx.defer[2]))
         need = ctx.needs_input_grad[0]
@@ -281,11 +340,11 @@ class BnReluConvFn(torch.autograd.Function):
         else:
             m0, i0, s0, h0 = be.bn_finalize(stats_in, spec.vin, bn.eps, bn.momentum, g.detach(), b.detach(), bn.running_mean,
                                             bn.running_var)
-        r = getattr(W, "_ms3d_wf", None)
-        r = r[0] if (r is not None and r[1] == tok) else None
+        prec = ctx.prec = conv_precision(be)
+        r = _ready(W, tok, prec)
         y, st, wf = be.conv_layer_forward(x, W.view(spec.K, spec.cin, spec.cout), spec.nbr_fwd, spec.vout, spec.K, spec.cin,
                                           spec.cout, spec.mirror, (s0, h0), True, None, None, want_stats,
-                                          **({"wf_ready": r} if r is not None else {}))
+                                          **({"wf_ready": r} if r is not None else {}), **_pk(prec))
         ctx.spec, ctx.wf = spec, wf
         ctx.bn = dict(scale=s0.contiguous(), shift=h0.contiguous(), mean=m0.contiguous(), invstd=i0.contiguous(), relu=True,
                       training=True)
@@ -304,7 +363,7 @@ class BnReluConvFn(torch.autograd.Function):
         x, W = ctx.saved_tensors
         e = {"defer": _queue(ctx.defer)} if _queue(ctx.defer) is not None else {}
         dx, dgb, dW = be.conv_layer_backward(x, dy.contiguous(), ctx.wf, spec.nbr_fwd, spec.nbr_bwd, spec.vin, spec.vout, spec.K,
-                                             spec.cin, spec.cout, ctx.bn, ctx.needs_input_grad[0], **e)
+                                             spec.cin, spec.cout, ctx.bn, ctx.needs_input_grad[0], **e, **_pk(ctx.prec))
         return dx, dW.view_as(W), dgb[1], dgb[0], None, None, None, None
 
 

@@ -54,11 +54,14 @@ def _flush_group(name):
     return 1 if ("blocks_tail" in parts or "deconv" in parts) else 3
 
 
-def prepare_conv_weights(root):
+def prepare_conv_weights(root, precision=None):
     """Lay out the kernel-side images of EVERY convolution weight under `root` in one launch (instead of one ~5 us
     launch per layer inside each convolution call; ~90 per U-Net step) and stamp the parameters.  The stamp is valid
     until `release_conv_weights()`: call the pair around a forward pass during which the weights do not change
     (GeneralModel.__call__ does).  Convolutions called outside such a window lay out their own weights as before.
+    The images are laid out for the matmul precision code `precision` (functional.precision_code; default: what a
+    convolution would run at now) and the stamp is (buffer, weight_token, precision): a convolution that runs at another
+    precision lays its own images out.
     In training the convolutions are also handed their kernels through `GroupFlushFn` nodes (functional.py): the slab
     reductions behind the backward-weight kernels of a whole group of layers then run as one launch.
     Not part of ME's API."""
@@ -84,7 +87,8 @@ def prepare_conv_weights(root):
                 buf = m.__dict__["_wf_buf"] = torch.empty(be.wf_floats(K, cin, cout), dtype=torch.float32, device=m.kernel.device)
             # same orientation rule as the forward() of the module: 3x3x3 maps mirror their offsets in backward-data
             layers.append((m.kernel, buf, K, cin, cout, m.kernel_size == 3 and m.stride == 1, m, grp))
-    be.prep_weights_multi([l[:6] for l in layers])
+    prec = Fn.conv_precision(be) if precision is None else precision
+    be.prep_weights_multi([l[:6] for l in layers], **Fn._pk(prec))
     token = be.weight_token
     defer = torch.is_grad_enabled() and hasattr(be, "wgrad_queue")
     if defer:
@@ -99,11 +103,11 @@ def prepare_conv_weights(root):
                 break
             eff = Fn.GroupFlushFn.apply(queue, *[w for w, _, _ in members])
             for e, (w, buf, m) in zip(eff, members):
-                e._ms3d_wf = (buf, token)
+                e._ms3d_wf = (buf, token, prec)
                 e._ms3d_defer = (queue, token, [0])      # [uses of this alias in the forward]: functional._defer_of
                 m.__dict__["_kernel_eff"] = (e, token)
     for w, buf, *_ in layers:
-        w._ms3d_wf = (buf, token)
+        w._ms3d_wf = (buf, token, prec)
 
 
 def release_conv_weights():

@@ -187,6 +187,7 @@ class HipBackend:
         self.ws = _Workspace()
         self.kernel_timer = None  # bench.py installs a KernelTimer to bracket chosen launches with HIP events
         self.weight_token = 0     # see prep_weights_multi
+        self.matmul_precision_aware = True   # the convolution calls take precision= (MinkowskiEngine/functional.py)
         self._prep_table = None
 
     # ------------------------------------------------------------------ helpers
@@ -573,6 +574,10 @@ _FAST_ARGTYPES = {
     "ms3d_spconv_layer_forward": [_VP] * 3 + [_I] * 5 + [_VP] * 2 + [_I] + [_VP] * 5 + [_VP] * 2 + [_VP] * 2 + [_VP],
     "ms3d_spconv_layer_backward": [_VP] * 5 + [_I] * 5 + [_VP] * 4 + [_I] * 3 + [_VP] * 5 + [_VP] * 4 + [_VP] * 4 +
                                   [_VP, _VP, _I, _VP, _VP, _VP, _VP],
+    # the same with the matmul precision (0 highest, 1 high, 2 medium) in front of the stream
+    "ms3d_spconv_layer_forward_p": [_VP] * 3 + [_I] * 5 + [_VP] * 2 + [_I] + [_VP] * 5 + [_VP] * 2 + [_VP] * 2 + [_I, _VP],
+    "ms3d_spconv_layer_backward_p": [_VP] * 5 + [_I] * 5 + [_VP] * 4 + [_I] * 3 + [_VP] * 5 + [_VP] * 4 + [_VP] * 4 +
+                                    [_VP, _VP, _I, _VP, _VP, _VP, _I, _VP],
     "ms3d_bn_finalize": [_VP, _I, C.c_long, _I, C.c_float, C.c_float] + [_VP] * 4 + [_VP] * 4 + [_VP],
 }
 
@@ -1034,7 +1039,8 @@ class _HipEngine:
         v = cache.get(k)
         if v is None:
             fn = getattr(self.lib, what)
-            if what in ("ms3d_spconv_wf_floats", "ms3d_spconv_layer_ws_floats", "ms3d_spconv_wgrad_ws_floats"):
+            if what in ("ms3d_spconv_wf_floats", "ms3d_spconv_layer_ws_floats", "ms3d_spconv_wgrad_ws_floats",
+                        "ms3d_spconv_wgrad_ws_floats_p"):
                 fn.restype = C.c_size_t
             v = cache[k] = fn(*[int(a) for a in key])
         return v
@@ -1043,14 +1049,14 @@ class _HipEngine:
         """floats of a layer's weight buffer: forward and backward-data image, each followed by its streamed form"""
         return 6 * self._geom("ms3d_spconv_wf_floats", K, cin, cout)    # [image | aux 2n | transposed image | aux 2n]
 
-    def prep_weights_multi(self, layers):
+    def prep_weights_multi(self, layers, precision=0):
         """layers: [(W [K,cin,cout] parameter, wf_buf, K, cin, cout, mirror_bwd)] -> both weight images of every layer in
         ONE launch; bumps `weight_token`, the stamp that says "the images in these buffers are the current weights"
         (release_weights() bumps it again).  The descriptor table lives on the device and is rebuilt only when the set
-        of tensors changes."""
+        of tensors or the matmul precision (0 highest, 1 high, 2 medium: the piece count of the bf16 images) changes."""
         if not layers:
             return
-        key = tuple((w.data_ptr(), b.data_ptr(), m) for w, b, _, _, _, m in layers)
+        key = tuple((w.data_ptr(), b.data_ptr(), m) for w, b, _, _, _, m in layers) + (int(precision),)
         cached = self._prep_table
         if cached is None or cached[0] != key:
             rec = np.zeros(len(layers), dtype=np.dtype([("W", "<u8"), ("wf", "<u8"), ("wft", "<u8"), ("K", "<i4"),
@@ -1061,12 +1067,12 @@ class _HipEngine:
                 assert w.is_contiguous() and w.dtype == torch.float32 and b.numel() >= self.wf_floats(K, cin, cout)
                 rec[i] = (w.data_ptr(), b.data_ptr(), b.data_ptr() + 4 * 3 * self._geom("ms3d_spconv_wf_floats", K, cin, cout),
                           K, cin, cout, int(bool(m)), begin,
-                          int(self.lib.ms3d_spconv_aux_kind(int(K), int(cin), int(cout))))
+                          self._aux_kind(K, cin, cout, precision))
                 begin += self.lib.ms3d_spconv_prep_blocks(int(K), int(cin), int(cout))
             table = torch.from_numpy(rec.view(np.uint8).copy()).to(layers[0][0].device)
             cached = self._prep_table = (key, table, begin)
-        _lib.check(self.lib.ms3d_spconv_prep_weights_multi(_lib.ptr(cached[1]), len(layers), int(cached[2]),
-                                                           _lib.stream_handle()), "ms3d_spconv_prep_weights_multi")
+        _lib.check(self.lib.ms3d_spconv_prep_weights_multi_p(_lib.ptr(cached[1]), len(layers), int(cached[2]), int(precision),
+                                                             _lib.stream_handle()), "ms3d_spconv_prep_weights_multi_p")
         self.weight_token += 1
         if self.__dict__.get("_wgrad_join_queued"):
             # MS3D_WGRAD_STREAM=2: a backward pass that raised never ran its end-of-pass callback -- join here, or no
@@ -1076,6 +1082,12 @@ class _HipEngine:
 
     def release_weights(self):
         self.weight_token += 1
+
+    def _aux_kind(self, K, cin, cout, precision):
+        kind = self._geom("ms3d_spconv_aux_kind_p", K, cin, cout, precision)
+        if kind not in (0, 1, 2, 3, 4):
+            raise ValueError(f"matmul precision code {precision!r}: expected 0 (highest), 1 (high) or 2 (medium)")
+        return kind
 
     def wgrad_queue(self):
         """a fresh WgradQueue, or None when deferred slab reductions are off (MS3D_WGRAD_DEFER=0, or backward-weight on
@@ -1098,9 +1110,11 @@ class _HipEngine:
         return on
 
     def conv_layer_forward(self, x, W3, nbr_fwd, vout, K, cin, cout, mirror_bwd, pre, pre_relu, residual, bias,
-                           want_stats, wf_ready=None):
+                           want_stats, wf_ready=None, precision=0):
         """-> (y, stats or None, wf_buf) ; wf_buf carries both weight images to the backward call.  wf_ready: a buffer
-        that already holds the current images (prep_weights_multi) -- the per-layer re-lay launch is skipped."""
+        that already holds the current images (prep_weights_multi) -- the per-layer re-lay launch is skipped.
+        precision: matmul precision code (0 highest, 1 high, 2 medium; functional.precision_code) -- the images are laid
+        out for it, wf_ready must have been, and the backward call must be given the same code."""
         x = self._dev(x)
         dev = x.device
         wf_buf = wf_ready if wf_ready is not None else torch.empty(self.wf_floats(K, cin, cout), dtype=torch.float32, device=dev)
@@ -1116,18 +1130,18 @@ class _HipEngine:
             y, stats = ext.conv_layer_forward(
                 x, None if wf_ready is not None else self._dev(W3), nbr_fwd, vout, K, cin, cout, bool(mirror_bwd),
                 _f32(ps), _f32(pb), bool(pre_relu), _f32(residual), _f32(bias), wf_buf, nparts, pl[0], pl[1],
-                (ev0.value or 0) if ev0 is not None else 0, (ev1.value or 0) if ev1 is not None else 0)
+                (ev0.value or 0) if ev0 is not None else 0, (ev1.value or 0) if ev1 is not None else 0, int(precision))
             return y, stats, wf_buf
         y = torch.empty((vout, cout), dtype=torch.float32, device=dev)
         stats = torch.empty((nparts, 2, cout), dtype=torch.float32, device=dev) if want_stats else None
-        _lib.check(self._fast("ms3d_spconv_layer_forward")(
+        _lib.check(self._fast("ms3d_spconv_layer_forward_p")(
             _p(x), _p(None if wf_ready is not None else self._dev(W3)), _p(nbr_fwd), int(vout), int(K), int(cin), int(cout),
             int(bool(mirror_bwd)), _p(_f32(ps)), _p(_f32(pb)), int(bool(pre_relu)), _p(_f32(residual)),
             _p(_f32(bias)), _p(wf_buf), _p(y), _p(stats), _p(pl[0]), _p(pl[1]),
-            ev0, ev1, _lib.stream_handle()), "ms3d_spconv_layer_forward")
+            ev0, ev1, int(precision), _lib.stream_handle()), "ms3d_spconv_layer_forward_p")
         return y, stats, wf_buf
 
-    def res_block_forward(self, x, stats_in, wf1, wf2, nbr, V, c, bn0, g0, b0, bn1, g1, b1, want_stats):
+    def res_block_forward(self, x, stats_in, wf1, wf2, nbr, V, c, bn0, g0, b0, bn1, g1, b1, want_stats, precision=0):
         """the four library calls of an identity-skip residual block's forward from ONE host call (csrc_host/ms3d_host.cpp:
         res_block_forward) -> (y1, y2, stats of y2 or None, bn0 = (mean, invstd, scale, shift), bn1 = ...), or None when the
         fast path does not apply (no host extension, a sampled step of the kernel timer, an unusual BatchNorm)"""
@@ -1140,16 +1154,18 @@ class _HipEngine:
         nparts = self._geom("ms3d_spconv_partial_blocks", V, 27, c, c, self._pl_rows(pl))
         y1, y2, st2, o0, o1 = ext.res_block_forward(
             x, stats_in, wf1, wf2, nbr, V, c, pl[0], pl[1], nparts, bool(want_stats), _f32(g0), _f32(b0), bn0.running_mean,
-            bn0.running_var, bn0.eps, bn0.momentum, _f32(g1), _f32(b1), bn1.running_mean, bn1.running_var, bn1.eps, bn1.momentum)
+            bn0.running_var, bn0.eps, bn0.momentum, _f32(g1), _f32(b1), bn1.running_mean, bn1.running_var, bn1.eps, bn1.momentum,
+            int(precision))
         return y1, y2, st2, o0.unbind(0), o1.unbind(0)
 
     def conv_layer_backward(self, x, dy, wf_buf, nbr_fwd, nbr_bwd, vin, vout, K, cin, cout, bn, need_dx, dx_add=None,
-                            defer=None, join_now=False):
+                            defer=None, join_now=False, precision=0):
         """-> (dx or None, dgb [2,cin] = (dbeta, dgamma) or None, dW [K,cin,cout]).  dx_add [vin, cin]: a gradient that
         reaches x over a skip connection, added to dx inside the BatchNorm-backward pass / the residual epilogue (needs
         training-mode statistics when a BatchNorm is fused: `fuses_dx_add`).  defer: a WgradQueue -- dW is returned
         UNREDUCED and completed by the queue's flush.  join_now: with MS3D_WGRAD_STREAM=2, make the caller's stream wait
-        for this layer's backward-weight (somebody consumes dW on it right after this call)."""
+        for this layer's backward-weight (somebody consumes dW on it right after this call).  precision: the code the
+        forward call laid wf_buf out with."""
         x = self._dev(x); dy = self._dev(dy)
         dev = x.device
         ws = self.ws.get("layer", 4 * self._geom("ms3d_spconv_layer_ws_floats", vin, vout, K, cin, cout), dev)
@@ -1179,7 +1195,8 @@ class _HipEngine:
                 bn["scale"] if has_bn else None, bn["shift"] if has_bn else None, bn["mean"] if has_bn else None,
                 bn["invstd"] if has_bn else None, bool(has_bn and bn["relu"]), bool(has_bn and bn["training"]), bool(need_dx),
                 _f32(dx_add) if (dx_add is not None and need_dx) else None, ws, plf[0], plf[1], plb[0], plb[1], *evs,
-                self._geom("ms3d_spconv_wgrad_ws_floats", vout, K, cin, cout) if defer is not None else 0, batch)
+                self._geom("ms3d_spconv_wgrad_ws_floats", vout, K, cin, cout) if defer is not None else 0, batch,
+                int(precision))
             if desc:
                 defer.add_launch(desc, (x, dy, nbr_fwd, bn, slabs, dW), timing)
             if nblk > 0:
@@ -1205,7 +1222,7 @@ class _HipEngine:
             slabs = torch.empty(self._geom("ms3d_spconv_wgrad_ws_floats", vout, K, cin, cout), dtype=torch.float32, device=dev)
             n_defer = self._defer_n_addr
         launch = (C.c_char * 128)() if (batch and slabs is not None) else None
-        _lib.check(self._fast("ms3d_spconv_layer_backward")(
+        _lib.check(self._fast("ms3d_spconv_layer_backward_p")(
             _p(x), _p(dy), _p(wf_buf), _p(nbr_fwd), _p(nbr_bwd), int(vin), int(vout), int(K),
             int(cin), int(cout), _p(bn["scale"] if has_bn else None), _p(bn["shift"] if has_bn else None),
             _p(bn["mean"] if has_bn else None), _p(bn["invstd"] if has_bn else None),
@@ -1213,8 +1230,8 @@ class _HipEngine:
             _p(_f32(dx_add) if (dx_add is not None and need_dx) else None), _p(dgb), _p(dW), _p(ws), _p(plf[0]), _p(plf[1]), _p(plb[0]),
             _p(plb[1]), ev0, ev1, ev2, ev3, _p(ws2), side.cuda_stream if side is not None else None,
             int(mode == 1 or (mode == 2 and join_now) or (mode == 3 and defer is None)), _p(slabs), n_defer,
-            C.addressof(launch) if launch is not None else None, _lib.stream_handle()),
-            "ms3d_spconv_layer_backward")
+            C.addressof(launch) if launch is not None else None, int(precision), _lib.stream_handle()),
+            "ms3d_spconv_layer_backward_p")
         if launch is not None and np.frombuffer(launch, dtype=np.int32, count=6)[4] != 0:
             defer.add_launch(bytes(launch), (x, dy, nbr_fwd, bn, slabs, dW), timing)
         if slabs is not None and self._defer_n.value > 0:
@@ -1267,17 +1284,17 @@ class _HipEngine:
         except RuntimeError:            # not inside a backward pass (a direct call): join now
             join()
 
-    def conv_backward_weight(self, x, dout, nbr, vout, K, cin, cout, pre=None, pre_relu=False):
+    def conv_backward_weight(self, x, dout, nbr, vout, K, cin, cout, pre=None, pre_relu=False, precision=0):
         x = self._dev(x); dout = self._dev(dout)
         dW = torch.empty((K, cin, cout), dtype=torch.float32, device=x.device)
         ps, pb = (pre if pre is not None else (None, None))
         self.lib.ms3d_spconv_wgrad_ws_floats.restype = C.c_size_t
         ws = self.ws.get("wgrad", 4 * self.lib.ms3d_spconv_wgrad_ws_floats(int(vout), int(K), int(cin), int(cout)), x.device)
         ol = self.offsetlist(nbr, K, vout)
-        _lib.check(self.lib.ms3d_spconv_backward_weight(
+        _lib.check(self.lib.ms3d_spconv_backward_weight_p(
             _lib.ptr(x), _lib.ptr(dout), _lib.ptr(nbr), int(vout), int(K), int(cin), int(cout), _lib.ptr(dW),
             _lib.ptr(_f32(ps)), _lib.ptr(_f32(pb)), int(bool(pre_relu)), _lib.ptr(ws), _lib.ptr(ol[0]), _lib.ptr(ol[1]),
-            _lib.stream_handle()), "ms3d_spconv_backward_weight")
+            int(precision), _lib.stream_handle()), "ms3d_spconv_backward_weight_p")
         return dW
 
     # ---- batch norm pieces

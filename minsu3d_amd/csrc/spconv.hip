@@ -113,7 +113,16 @@ __device__ __forceinline__ long stream_slot(long o, int NBtot)
 //               lane = (j & 15) + 16*g holds W[k][c = 32*c32 + 8*g + e][j = 16*nb + (lane & 15)], e = 0..7
 // -- the B operand of the instruction for column block nb and 32-channel chunk c32, one ds_read_b128 per lane.
 // It lives in the AUX slot behind the f32 image (where rectangular layers keep their streamed image).
+// Lower precisions (torch.set_float32_matmul_precision "high" / "medium": the `precision` argument of the *_p entry
+// points) keep the first P pieces of the SAME split, x0 = bf16_rne(x), x1 = bf16_rne(x - x0), for both operands:
+//   P = 3  x0w0 + x0w1 + x1w0 + x1w1 + x0w2 + x2w0   (6 MFMAs, float32 grade)
+//   P = 2  x0w0 + x0w1 + x1w0                        (3 MFMAs, ~2^-16)
+//   P = 1  x0w0                                      (1 MFMA: bf16 x bf16 accumulated in f32)
+// Images of P pieces have the layout above with 3 replaced by P (aux kinds 2 / 3 / 4 = 3 / 2 / 1 pieces).
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
+
+// bf16 pieces of an aux kind (ms3d_spconv_aux_kind_p): 0 = not a bf16 image
+__host__ __device__ constexpr int aux_pieces(int aux_kind) { return aux_kind == 2 ? 3 : aux_kind == 3 ? 2 : aux_kind == 4 ? 1 : 0; }
 
 __host__ __device__ inline bool bf3_dims_ok(int K, int Cin, int Cout)
 {
@@ -143,6 +152,7 @@ __device__ __forceinline__ uint32_t cvt_pk_bf16(float a, float b)
     const bf16x2_t h = __builtin_convertvector((f32x2_t){a, b}, bf16x2_t);
     return *reinterpret_cast<const uint32_t *>(&h);
 }
+template <int P = 3>
 __device__ __forceinline__ void act_split8(const f32x4 &lo, const f32x4 &hi, bool affine, const f32x4 &s0, const f32x4 &s1,
                                            const f32x4 &b0, const f32x4 &b1, float floor_, int keep, bf16x8 &a0, bf16x8 &a1,
                                            bf16x8 &a2)
@@ -158,36 +168,70 @@ __device__ __forceinline__ void act_split8(const f32x4 &lo, const f32x4 &hi, boo
         }
     }
     uint32_t q0[4], q1[4], q2[4];
+    if constexpr (P == 3) {
+#pragma unroll
+        for (int t = 0; t < 4; t++) {
+            const float x = __int_as_float(__float_as_int(v[2 * t]) & keep), y = __int_as_float(__float_as_int(v[2 * t + 1]) & keep);
+            q0[t] = cvt_pk_bf16(x, y);
+            const float rx = x - __uint_as_float(q0[t] << 16), ry = y - __uint_as_float(q0[t] & 0xffff0000u);     // exact
+            q1[t] = cvt_pk_bf16(rx, ry);
+            const float sx = rx - __uint_as_float(q1[t] << 16), sy = ry - __uint_as_float(q1[t] & 0xffff0000u);   // exact
+            q2[t] = cvt_pk_bf16(sx, sy);
+        }
+        a0 = *reinterpret_cast<const bf16x8 *>(q0);
+        a1 = *reinterpret_cast<const bf16x8 *>(q1);
+        a2 = *reinterpret_cast<const bf16x8 *>(q2);
+        return;
+    }
 #pragma unroll
     for (int t = 0; t < 4; t++) {
         const float x = __int_as_float(__float_as_int(v[2 * t]) & keep), y = __int_as_float(__float_as_int(v[2 * t + 1]) & keep);
         q0[t] = cvt_pk_bf16(x, y);
+        if (P < 2) continue;   // one piece: no remainder arithmetic
         const float rx = x - __uint_as_float(q0[t] << 16), ry = y - __uint_as_float(q0[t] & 0xffff0000u);     // exact
         q1[t] = cvt_pk_bf16(rx, ry);
-        const float sx = rx - __uint_as_float(q1[t] << 16), sy = ry - __uint_as_float(q1[t] & 0xffff0000u);   // exact
-        q2[t] = cvt_pk_bf16(sx, sy);
     }
     a0 = *reinterpret_cast<const bf16x8 *>(q0);
-    a1 = *reinterpret_cast<const bf16x8 *>(q1);
-    a2 = *reinterpret_cast<const bf16x8 *>(q2);
+    if (P >= 2) a1 = *reinterpret_cast<const bf16x8 *>(q1);
 }
 
+// the products of P pieces into one accumulator, smallest terms first (P = 3: the original six-MFMA sequence)
+template <int P>
+__device__ __forceinline__ void mfma_pieces(f32x4 &d, const bf16x8 &a0, const bf16x8 &a1, const bf16x8 &a2, const bf16x8 &w0,
+                                            const bf16x8 &w1, const bf16x8 &w2)
+{
+    if (P >= 3) {
+        d = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a2, w0, d, 0, 0, 0);
+        d = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a0, w2, d, 0, 0, 0);
+        d = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a1, w1, d, 0, 0, 0);
+    }
+    if (P >= 2) {
+        d = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a1, w0, d, 0, 0, 0);
+        d = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a0, w1, d, 0, 0, 0);
+    }
+    d = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a0, w0, d, 0, 0, 0);
+}
+
+template <int P = 3>
 __device__ __forceinline__ void write_bf3(float *aux, int k, int c, int j, int Cin_e, int NB, float v)
 {
     __bf16 *img = reinterpret_cast<__bf16 *>(aux);
     const int NC32 = (Cin_e + 31) >> 5, c32 = c >> 5, g = (c >> 3) & 3, e = c & 7, nb = j >> 4, jl = j & 15;
-    const size_t base = ((((size_t)k * NC32 + c32) * NB + nb) * 3) * 64 + (jl + 16 * g);
+    const size_t base = ((((size_t)k * NC32 + c32) * NB + nb) * P) * 64 + (jl + 16 * g);
     __bf16 h0, h1, h2;
     split3(v, h0, h1, h2);
     img[(base + 0) * 8 + e] = h0;
-    img[(base + 64) * 8 + e] = h1;
-    img[(base + 128) * 8 + e] = h2;
+    if (P >= 2) img[(base + 64) * 8 + e] = h1;
+    if (P >= 3) img[(base + 128) * 8 + e] = h2;
 }
 
+// PB: pieces of the bf16 image this instantiation writes (aux kind 5 - PB; launched by the kind the caller asks for)
+template <int PB = 3>
 __global__ void prep_weights_kernel(const float *__restrict__ W, float *__restrict__ wf, int K, int Cin_e, int Cout_e,
                                     int NCH, int NBtot, int transpose, int mirror, float *__restrict__ wf2, int NCH2,
                                     int NBtot2, int mirror2, float *__restrict__ wfs, float *__restrict__ wfs2, int aux_kind)
-{   // aux_kind: 1 = wfs / wfs2 take the streamed f32 image, 2 = the three-piece bf16 image
+{   // aux_kind: 1 = wfs / wfs2 take the streamed f32 image, 2 / 3 / 4 = the three- / two- / one-piece bf16 image
+    constexpr int P = PB, BF_KIND = 5 - PB;
     const long total = (long)K * NCH * 4 * NBtot * 64;
     if (wf2) {
         // second image in the same launch: the backward-data operator (transposed, Cin/Cout swapped)
@@ -204,9 +248,9 @@ __global__ void prep_weights_kernel(const float *__restrict__ W, float *__restri
             const float v = (c < Cout_e && j < Cin_e) ? W[((size_t)ks * Cin_e + j) * Cout_e + c] : 0.f;
             wf2[o] = v;
             if (wfs2 && aux_kind == 1) wfs2[stream_slot(o, NBtot2)] = v;
-            if (wfs2 && aux_kind == 2 && c < Cout_e && j < Cin_e) {
-                write_bf3(wfs2, k, c, j, Cout_e, NBtot2, v);
-                if ((Cout_e & 16) && c >= Cout_e - 16) write_bf3(wfs2, k, c + 16, j, Cout_e, NBtot2, 0.f);   // zero pad
+            if (wfs2 && aux_kind == BF_KIND && c < Cout_e && j < Cin_e) {
+                write_bf3<P>(wfs2, k, c, j, Cout_e, NBtot2, v);
+                if ((Cout_e & 16) && c >= Cout_e - 16) write_bf3<P>(wfs2, k, c + 16, j, Cout_e, NBtot2, 0.f);   // zero pad
             }
         }
     }
@@ -225,9 +269,9 @@ __global__ void prep_weights_kernel(const float *__restrict__ W, float *__restri
                           : W[((size_t)ks * Cin_e + c) * Cout_e + j];
         wf[o] = v;
         if (wfs && aux_kind == 1) wfs[stream_slot(o, NBtot)] = v;
-        if (wfs && aux_kind == 2 && c < Cin_e && j < Cout_e) {
-            write_bf3(wfs, k, c, j, Cin_e, NBtot, v);
-            if ((Cin_e & 16) && c >= Cin_e - 16) write_bf3(wfs, k, c + 16, j, Cin_e, NBtot, 0.f);              // zero pad
+        if (wfs && aux_kind == BF_KIND && c < Cin_e && j < Cout_e) {
+            write_bf3<P>(wfs, k, c, j, Cin_e, NBtot, v);
+            if ((Cin_e & 16) && c >= Cin_e - 16) write_bf3<P>(wfs, k, c + 16, j, Cin_e, NBtot, 0.f);              // zero pad
         }
     }
 }
@@ -239,10 +283,12 @@ struct PrepDesc {
     float *wf, *wft;  // forward image, backward-data image (transposed, offsets mirrored if mirror_bwd);
                       // each is followed by its aux image: wf + n, wft + n  (n = ms3d_spconv_wf_floats; slot of 2n)
     int K, Cin, Cout, mirror_bwd, block_begin;
-    int stream;       // aux images: 1 = streamed f32 (layers that can take spconv_fwd_pairstream_kernel), 2 = three-piece bf16
+    int stream;       // aux images: 1 = streamed f32 (layers that can take spconv_fwd_pairstream_kernel), 2 / 3 / 4 = three- /
+                      // two- / one-piece bf16 (ms3d_spconv_aux_kind_p)
 };
 static_assert(sizeof(PrepDesc) == 48, "layout shared with the host-side descriptor table");
 
+template <int PB = 3>   // pieces of the bf16 images it writes: the layers whose `stream` is aux kind 5 - PB
 __global__ __launch_bounds__(256) void prep_weights_multi_kernel(const PrepDesc *__restrict__ descs, int n)
 {
     int lo = 0, hi = n - 1;  // last layer with block_begin <= blockIdx.x
@@ -277,7 +323,8 @@ __global__ __launch_bounds__(256) void prep_weights_multi_kernel(const PrepDesc 
         d.wft[o] = v;
         if (d.stream == 1) d.wft[total + stream_slot(o, NCH)] = v;
     }
-    if (d.stream == 2) {
+    if (d.stream == 5 - PB) {
+        constexpr int P = PB;
         // The three-piece bf16 images (layout: write_bf3), 16 bytes per piece and thread: thread (k, c32, nb, lane) reads the
         // 8 weights of its operand register (input channels 32 c32 + 8 (lane >> 4) + e, column 16 nb + (lane & 15)) and
         // stores three whole operands.  (One weight per thread scattered 2-byte stores over the image: 0.4 ms per HAIS
@@ -301,8 +348,10 @@ __global__ __launch_bounds__(256) void prep_weights_multi_kernel(const PrepDesc 
                 split3(v, h0, h1, h2);
                 p0[e] = h0; p1[e] = h1; p2[e] = h2;
             }
-            bf16x8 *dst = reinterpret_cast<bf16x8 *>(aux) + ((((size_t)k * NC32 + c32) * nb_tot + nb) * 3) * 64 + lane;
-            dst[0] = p0; dst[64] = p1; dst[128] = p2;
+            bf16x8 *dst = reinterpret_cast<bf16x8 *>(aux) + ((((size_t)k * NC32 + c32) * nb_tot + nb) * P) * 64 + lane;
+            dst[0] = p0;
+            if (P >= 2) dst[64] = p1;
+            if (P >= 3) dst[128] = p2;
         };
         image(d.wf + total, d.Cin, d.Cout, NB, false);
         image(d.wft + total, d.Cout, d.Cin, NCH, true);     // the transposed operator: input side = Cout, columns = Cin
@@ -690,7 +739,7 @@ __global__ __launch_bounds__(1024) void spconv_fwd_kernel(ConvArgs p)
 constexpr int OGB = 5;   // offsets per gather group: 10 x 16 B per lane in flight
 
 // OG: offsets per gather round / stage (bf3_round_offsets(NBT): the most that stays inside the 128 registers of a 1024-thread block)
-template <int NBT, int OG>
+template <int NBT, int OG, int P = 3>
 __global__ __launch_bounds__(1024) void spconv_fwd_bf3_kernel(ConvArgs p)
 {
     extern __shared__ float lds[];
@@ -700,7 +749,7 @@ __global__ __launch_bounds__(1024) void spconv_fwd_bf3_kernel(ConvArgs p)
     const int NC32 = (p.Cin + 31) >> 5;
     const int GC = p.GC > 0 ? p.GC : NC32;                                  // chunks per stage
     uint4 *sW = reinterpret_cast<uint4 *>(lds);                             // [offset in group][chunk in range][nb][piece][lane] x 16 B
-    const int slab = NBT * 3 * 64;                                          // uint4 per (offset, c32) in the LDS image
+    const int slab = NBT * P * 64;                                          // uint4 per (offset, c32) in the LDS image
     float *s_part = lds + (size_t)p.G * GC * slab * 4;                      // [waves] statistics slots when asked for
     const uint4 *img = reinterpret_cast<const uint4 *>(p.wfb);
     // offsets [k_lo, k_lo + cnt) x chunks [c_lo, c_lo + ccnt) of this block's column slice, copied by
@@ -709,11 +758,11 @@ __global__ __launch_bounds__(1024) void spconv_fwd_bf3_kernel(ConvArgs p)
     // work), completion on vmcnt (tools/probe/lds_direct_probe.hip checks the lane -> address mapping)
     auto stage = [&](int k_lo, int cnt, int c_lo, int ccnt) {
         uint4 *dst = sW;
-        const int chunks = cnt * ccnt * NBT * 3;                            // 1 KB each
+        const int chunks = cnt * ccnt * NBT * P;                            // 1 KB each
         for (int ch = wave_id(); ch < chunks; ch += waves) {
-            const int r = ch / (NBT * 3), within = ch - r * (NBT * 3);
+            const int r = ch / (NBT * P), within = ch - r * (NBT * P);
             const int kk = r / ccnt, cc = r - kk * ccnt;
-            const uint4 *src = img + ((size_t)((k_lo + kk) * NC32 + c_lo + cc) * p.NBtot + nb0) * 3 * 64 + within * 64 + l;
+            const uint4 *src = img + ((size_t)((k_lo + kk) * NC32 + c_lo + cc) * p.NBtot + nb0) * P * 64 + within * 64 + l;
             __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void *)src,
                                              (__attribute__((address_space(3))) void *)(dst + (size_t)ch * 64), 16, 0, 0);
         }
@@ -767,20 +816,24 @@ __global__ __launch_bounds__(1024) void spconv_fwd_bf3_kernel(ConvArgs p)
             if (!any[u]) continue;
             bf16x8 a0, a1, a2;
             // absent neighbour (idx < 0) / padded channels contribute nothing
-            act_split8(r.lo[u], r.hi[u], affine, s0, s1, b0, b1, relu_floor, ~(idx[u] >> 31) & c_keep, a0, a1, a2);
+            act_split8<P>(r.lo[u], r.hi[u], affine, s0, s1, b0, b1, relu_floor, ~(idx[u] >> 31) & c_keep, a0, a1, a2);
             const uint4 *w = sW + (size_t)(u * cstride + cslot) * slab + l;
 #pragma unroll
             for (int nb = 0; nb < NBT; nb++) {
-                const uint4 r0 = w[(nb * 3 + 0) * 64], r1 = w[(nb * 3 + 1) * 64], r2 = w[(nb * 3 + 2) * 64];
+                const uint4 r0 = w[(nb * P + 0) * 64], r1 = w[(nb * P + (P >= 2 ? 1 : 0)) * 64], r2 = w[(nb * P + (P >= 3 ? 2 : 0)) * 64];
                 const bf16x8 w0 = *reinterpret_cast<const bf16x8 *>(&r0), w1 = *reinterpret_cast<const bf16x8 *>(&r1),
                              w2 = *reinterpret_cast<const bf16x8 *>(&r2);
                 // smallest terms first
-                acc[nb] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a2, w0, acc[nb], 0, 0, 0);
-                acc[nb] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a0, w2, acc[nb], 0, 0, 0);
-                acc[nb] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a1, w1, acc[nb], 0, 0, 0);
-                acc[nb] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a1, w0, acc[nb], 0, 0, 0);
-                acc[nb] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a0, w1, acc[nb], 0, 0, 0);
-                acc[nb] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a0, w0, acc[nb], 0, 0, 0);
+                if constexpr (P == 3) {
+                    acc[nb] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a2, w0, acc[nb], 0, 0, 0);
+                    acc[nb] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a0, w2, acc[nb], 0, 0, 0);
+                    acc[nb] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a1, w1, acc[nb], 0, 0, 0);
+                    acc[nb] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a1, w0, acc[nb], 0, 0, 0);
+                    acc[nb] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a0, w1, acc[nb], 0, 0, 0);
+                    acc[nb] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a0, w0, acc[nb], 0, 0, 0);
+                } else {
+                    mfma_pieces<P>(acc[nb], a0, a1, a2, w0, w1, w2);
+                }
             }
         }
     };
@@ -826,13 +879,13 @@ __global__ __launch_bounds__(1024) void spconv_fwd_bf3_kernel(ConvArgs p)
 // measured per column count (profiles/r03_fwd_experiments.txt section 9)
 constexpr int bf3_round_offsets(int nbt) { return nbt == 2 || nbt == 4 || nbt == 6 ? 5 : 4; }
 
-template <int NBT>
+template <int NBT, int P = 3>
 int launch_fwd_bf3(const ConvArgs &p, dim3 grid, int threads, size_t lds, hipStream_t stream)
 {
     constexpr int OG = bf3_round_offsets(NBT);
-    static const hipError_t attr = raise_lds_ceiling((const void *)spconv_fwd_bf3_kernel<NBT, OG>);
+    static const hipError_t attr = raise_lds_ceiling((const void *)spconv_fwd_bf3_kernel<NBT, OG, P>);
     MS3D_CHECK(attr);
-    spconv_fwd_bf3_kernel<NBT, OG><<<grid, threads, lds, stream>>>(p);
+    spconv_fwd_bf3_kernel<NBT, OG, P><<<grid, threads, lds, stream>>>(p);
     MS3D_LAUNCH_CHECK();
     return 0;
 }
@@ -890,7 +943,7 @@ __global__ __launch_bounds__(256) void spconv_fwd_small_kernel(ConvArgs p)
 // B operands (16 bytes per lane and piece) straight from the L2-resident image, no LDS staging -- the bf16x3 counterpart
 // of spconv_fwd_small_kernel.  The operands of the NEXT (offset, column group) are requested before the current group's
 // MFMAs (two register sets, unconditional loads); an offset no row of the tile has skips its MFMAs only.
-template <int NBT>
+template <int NBT, int P = 3>
 __global__ __launch_bounds__(256) void spconv_fwd_small_bf3_kernel(ConvArgs p)
 {
     extern __shared__ float lds[];
@@ -938,22 +991,22 @@ __global__ __launch_bounds__(256) void spconv_fwd_small_bf3_kernel(ConvArgs p)
             const float *ps = p.pre_scale ? p.pre_scale : p.in, *pb = p.pre_scale ? p.pre_shift : p.in;
             const f32x4 s0 = *reinterpret_cast<const f32x4 *>(ps + c0), s1 = *reinterpret_cast<const f32x4 *>(ps + c0 + 4);
             const f32x4 b0 = *reinterpret_cast<const f32x4 *>(pb + c0), b1 = *reinterpret_cast<const f32x4 *>(pb + c0 + 4);
-            // B operands of (offset u, column group cg): [GB + 1][3 pieces] x 16 B, two sets
-            uint4 wb[2][(GB + 1) * 3];
-            auto load_b = [&](int u, int cg, uint4 (&dst)[(GB + 1) * 3]) {
+            // B operands of (offset u, column group cg): [GB + 1][P pieces] x 16 B, two sets
+            uint4 wb[2][(GB + 1) * P];
+            auto load_b = [&](int u, int cg, uint4 (&dst)[(GB + 1) * P]) {
                 const int kk = min(min(k0 + u, k_hi - 1), p.K - 1);
                 const int first = cg * GB + (cg < GR ? cg : GR);
-                const uint4 *w = img + ((size_t)(kk * NC32 + c32) * p.NBtot + nb0 + first) * 3 * 64 + l;
+                const uint4 *w = img + ((size_t)(kk * NC32 + c32) * p.NBtot + nb0 + first) * P * 64 + l;
 #pragma unroll
-                for (int i = 0; i < (GB + 1) * 3; i++) dst[i] = w[min(i, (NBT - first) * 3 - 1) * 64];
+                for (int i = 0; i < (GB + 1) * P; i++) dst[i] = w[min(i, (NBT - first) * P - 1) * 64];
             };
             load_b(0, 0, wb[0]);
 #pragma unroll
             for (int u = 0; u < OGB; u++) {
                 bf16x8 a0, a1, a2;
                 if (any[u])
-                    act_split8(lo[u], hi[u], p.pre_scale != nullptr, s0, s1, b0, b1, p.pre_relu ? 0.f : -INFINITY,
-                               ~(idx[u] >> 31) & c_keep, a0, a1, a2);
+                    act_split8<P>(lo[u], hi[u], p.pre_scale != nullptr, s0, s1, b0, b1, p.pre_relu ? 0.f : -INFINITY,
+                                  ~(idx[u] >> 31) & c_keep, a0, a1, a2);
 #pragma unroll
                 for (int cg = 0; cg < NG; cg++) {
                     constexpr int dummy = 0; (void)dummy;
@@ -967,16 +1020,21 @@ __global__ __launch_bounds__(256) void spconv_fwd_small_bf3_kernel(ConvArgs p)
 #pragma unroll
                         for (int i = 0; i < GB + 1; i++) {
                             if (i >= count) continue;
-                            const uint4 &r0 = wb[stage & 1][i * 3 + 0], &r1 = wb[stage & 1][i * 3 + 1], &r2 = wb[stage & 1][i * 3 + 2];
+                            const uint4 &r0 = wb[stage & 1][i * P + 0], &r1 = wb[stage & 1][i * P + (P >= 2 ? 1 : 0)],
+                                        &r2 = wb[stage & 1][i * P + (P >= 3 ? 2 : 0)];
                             const bf16x8 w0 = *reinterpret_cast<const bf16x8 *>(&r0), w1 = *reinterpret_cast<const bf16x8 *>(&r1),
                                          w2 = *reinterpret_cast<const bf16x8 *>(&r2);
                             f32x4 &d = acc[first + i];
-                            d = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a2, w0, d, 0, 0, 0);
-                            d = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a0, w2, d, 0, 0, 0);
-                            d = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a1, w1, d, 0, 0, 0);
-                            d = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a1, w0, d, 0, 0, 0);
-                            d = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a0, w1, d, 0, 0, 0);
-                            d = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a0, w0, d, 0, 0, 0);
+                            if constexpr (P == 3) {
+                                d = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a2, w0, d, 0, 0, 0);
+                                d = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a0, w2, d, 0, 0, 0);
+                                d = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a1, w1, d, 0, 0, 0);
+                                d = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a1, w0, d, 0, 0, 0);
+                                d = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a0, w1, d, 0, 0, 0);
+                                d = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a0, w0, d, 0, 0, 0);
+                            } else {
+                                mfma_pieces<P>(d, a0, a1, a2, w0, w1, w2);
+                            }
                         }
                     }
                 }
@@ -1008,7 +1066,7 @@ __global__ __launch_bounds__(256) void spconv_fwd_small_bf3_kernel(ConvArgs p)
 // step's B operands ONCE (two column groups, double-buffered in registers: the next group's / next step's loads fly
 // during this group's MFMAs) and uses them for all RT tiles; the next step's gathers and the table entries of the offset
 // after are in flight during the step.  Partial accumulators of the waves meet in LDS; wave t finishes tile t.
-template <int NBT, int RT>
+template <int NBT, int RT, int P = 3>
 __global__ __launch_bounds__(256) void spconv_fwd_small_bf3_rt_kernel(ConvArgs p)
 {
     extern __shared__ float lds[];
@@ -1062,16 +1120,16 @@ __global__ __launch_bounds__(256) void spconv_fwd_small_bf3_rt_kernel(ConvArgs p
             g.hi[t] = *reinterpret_cast<const f32x4 *>(row + 4);
         }
     };
-    auto load_b = [&](int k, int c32, int cg, uint4 (&dst)[CG * 3]) {
+    auto load_b = [&](int k, int c32, int cg, uint4 (&dst)[CG * P]) {
         const int kk = min(k, p.K - 1), first = cg * CG;
-        const uint4 *src = img + ((size_t)(kk * NC32 + c32) * p.NBtot + nb0 + first) * 3 * 64 + l;
+        const uint4 *src = img + ((size_t)(kk * NC32 + c32) * p.NBtot + nb0 + first) * P * 64 + l;
 #pragma unroll
-        for (int i = 0; i < CG * 3; i++) dst[i] = src[min(i, (NBT - first) * 3 - 1) * 64];
+        for (int i = 0; i < CG * P; i++) dst[i] = src[min(i, (NBT - first) * P - 1) * 64];
     };
 
     int idx_c[RT], idx_n[RT];
     Rows g_c;
-    uint4 wb[2][CG * 3];
+    uint4 wb[2][CG * P];
     load_idx(k_lo, idx_c);
     gather(0, idx_c, g_c);
     load_idx(k_lo + 1, idx_n);
@@ -1098,8 +1156,8 @@ __global__ __launch_bounds__(256) void spconv_fwd_small_bf3_rt_kernel(ConvArgs p
         for (int t = 0; t < RT; t++) {
             any[t] = __ballot(idx_c[t] >= 0) != 0ull;
             if (any[t])
-                act_split8(g_c.lo[t], g_c.hi[t], affine, s0, s1, b0, b1, relu_floor, ~(idx_c[t] >> 31) & c_keep, a[t][0], a[t][1],
-                           a[t][2]);
+                act_split8<P>(g_c.lo[t], g_c.hi[t], affine, s0, s1, b0, b1, relu_floor, ~(idx_c[t] >> 31) & c_keep, a[t][0],
+                              a[t][1], a[t][2]);
         }
 #pragma unroll
         for (int cg = 0; cg < 2; cg++) {
@@ -1111,18 +1169,23 @@ __global__ __launch_bounds__(256) void spconv_fwd_small_bf3_rt_kernel(ConvArgs p
             for (int i = 0; i < CG; i++) {
                 const int nb = cg * CG + i;
                 if (nb >= NBT) continue;
-                const bf16x8 w0 = *reinterpret_cast<const bf16x8 *>(&wb[cg][i * 3 + 0]), w1 = *reinterpret_cast<const bf16x8 *>(&wb[cg][i * 3 + 1]),
-                             w2 = *reinterpret_cast<const bf16x8 *>(&wb[cg][i * 3 + 2]);
+                const bf16x8 w0 = *reinterpret_cast<const bf16x8 *>(&wb[cg][i * P + 0]),
+                             w1 = *reinterpret_cast<const bf16x8 *>(&wb[cg][i * P + (P >= 2 ? 1 : 0)]),
+                             w2 = *reinterpret_cast<const bf16x8 *>(&wb[cg][i * P + (P >= 3 ? 2 : 0)]);
 #pragma unroll
                 for (int t = 0; t < RT; t++) {
                     if (!any[t]) continue;
                     f32x4 &d = acc[t][nb];
-                    d = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a[t][2], w0, d, 0, 0, 0);
-                    d = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a[t][0], w2, d, 0, 0, 0);
-                    d = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a[t][1], w1, d, 0, 0, 0);
-                    d = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a[t][1], w0, d, 0, 0, 0);
-                    d = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a[t][0], w1, d, 0, 0, 0);
-                    d = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a[t][0], w0, d, 0, 0, 0);
+                    if constexpr (P == 3) {
+                        d = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a[t][2], w0, d, 0, 0, 0);
+                        d = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a[t][0], w2, d, 0, 0, 0);
+                        d = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a[t][1], w1, d, 0, 0, 0);
+                        d = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a[t][1], w0, d, 0, 0, 0);
+                        d = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a[t][0], w1, d, 0, 0, 0);
+                        d = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a[t][0], w0, d, 0, 0, 0);
+                    } else {
+                        mfma_pieces<P>(d, a[t][0], a[t][1], a[t][2], w0, w1, w2);
+                    }
                 }
             }
         }
@@ -1157,20 +1220,20 @@ __global__ __launch_bounds__(256) void spconv_fwd_small_bf3_rt_kernel(ConvArgs p
     if (with_partial) stats_flush<NBT>(p, s_part, waves, nb0);
 }
 
-template <int NBT, int RT>
+template <int NBT, int RT, int P = 3>
 int launch_fwd_small_bf3_rt(const ConvArgs &p, dim3 grid, int threads, size_t lds, hipStream_t stream)
 {
-    static const hipError_t attr = raise_lds_ceiling((const void *)spconv_fwd_small_bf3_rt_kernel<NBT, RT>);
+    static const hipError_t attr = raise_lds_ceiling((const void *)spconv_fwd_small_bf3_rt_kernel<NBT, RT, P>);
     MS3D_CHECK(attr);
-    spconv_fwd_small_bf3_rt_kernel<NBT, RT><<<grid, threads, lds, stream>>>(p);
+    spconv_fwd_small_bf3_rt_kernel<NBT, RT, P><<<grid, threads, lds, stream>>>(p);
     MS3D_LAUNCH_CHECK();
     return 0;
 }
 
-template <int NBT>
+template <int NBT, int P = 3>
 int launch_fwd_small_bf3(const ConvArgs &p, dim3 grid, int threads, size_t lds, hipStream_t stream)
 {
-    spconv_fwd_small_bf3_kernel<NBT><<<grid, threads, lds, stream>>>(p);
+    spconv_fwd_small_bf3_kernel<NBT, P><<<grid, threads, lds, stream>>>(p);
     MS3D_LAUNCH_CHECK();
     return 0;
 }
@@ -2277,6 +2340,8 @@ __global__ __launch_bounds__(256) void spconv_wgrad_multi_kernel(const unsigned 
 // (every wave gathering and transposing for itself; dout operands re-read from LDS per offset) were slower than the f32
 // kernel on operand traffic alone (profiles/r03_fwd_experiments.txt section 6).  No cross-wave reduction: every
 // accumulator belongs to one (offset, column block).  rows_per_block is a multiple of 32.
+// (P pieces instead of 3 at the lower precisions: the same layouts with 3 replaced by P)
+template <int P>
 __device__ __forceinline__ void split_rows_bf3(long blk, const float *__restrict__ x, long V, int C, int NB, long ntile,
                                                bf16x8 *__restrict__ img)
 {
@@ -2296,10 +2361,13 @@ __device__ __forceinline__ void split_rows_bf3(long blk, const float *__restrict
         split3(v, h0, h1, h2);
         p0[e] = h0; p1[e] = h1; p2[e] = h2;
     }
-    bf16x8 *dst = img + (tn * 3) * 64 + lane;
-    dst[0] = p0; dst[64] = p1; dst[128] = p2;
+    bf16x8 *dst = img + (tn * P) * 64 + lane;
+    dst[0] = p0;
+    if (P >= 2) dst[64] = p1;
+    if (P >= 3) dst[128] = p2;
 }
 
+template <int P>
 __device__ __forceinline__ void act_split_bf3(long blk, const float *__restrict__ x, long V, int C,
                                               const float *__restrict__ scale, const float *__restrict__ shift, int relu,
                                               bf16x8 *__restrict__ xs)
@@ -2323,23 +2391,26 @@ __device__ __forceinline__ void act_split_bf3(long blk, const float *__restrict_
         split3(y, h0, h1, h2);
         p0[e] = h0; p1[e] = h1; p2[e] = h2;
     }
-    bf16x8 *dst = xs + (row * 3) * C8 + (c0 >> 3);
-    dst[0] = p0; dst[C8] = p1; dst[2 * C8] = p2;
+    bf16x8 *dst = xs + (row * P) * C8 + (c0 >> 3);
+    dst[0] = p0;
+    if (P >= 2) dst[C8] = p1;
+    if (P >= 3) dst[2 * C8] = p2;
 }
 
 // both passes in one launch: blocks [0, nblk_dout) lay dout out, the rest split the activated input
+template <int P>
 __global__ __launch_bounds__(256) void wgrad_bf3_operands_kernel(const float *__restrict__ dout, const float *__restrict__ x, long V,
                                                                  int Cin, int Cout, int NB, long ntile, int nblk_dout,
                                                                  const float *__restrict__ scale, const float *__restrict__ shift,
                                                                  int relu, bf16x8 *__restrict__ img, bf16x8 *__restrict__ xs)
 {
-    if ((int)blockIdx.x < nblk_dout) split_rows_bf3(blockIdx.x, dout, V, Cout, NB, ntile, img);
-    else act_split_bf3((long)blockIdx.x - nblk_dout, x, V, Cin, scale, shift, relu, xs);
+    if ((int)blockIdx.x < nblk_dout) split_rows_bf3<P>(blockIdx.x, dout, V, Cout, NB, ntile, img);
+    else act_split_bf3<P>((long)blockIdx.x - nblk_dout, x, V, Cin, scale, shift, relu, xs);
 }
 
 struct WgradBf3Args {
-    const bf16x8 *xs;        // activated input pieces, row-major [Vin][3][Cin/8]
-    const bf16x8 *dout_img;  // dout operands [Vout/32][NB][3][64]
+    const bf16x8 *xs;        // activated input pieces, row-major [Vin][P][Cin/8]
+    const bf16x8 *dout_img;  // dout operands [Vout/32][NB][P][64]
     const int *nbr;          // [K][Vout]
     float *partial;
     int Vout, K, Cin, Cout, NBtot, rows_per_block;
@@ -2347,12 +2418,12 @@ struct WgradBf3Args {
 
 typedef short s16x4 __attribute__((ext_vector_type(4)));
 
-template <int KG, int NW, int NBW>
+template <int KG, int NW, int NBW, int P = 3>
 __global__ __launch_bounds__(64 * NW, 2) void spconv_wgrad_bf3_kernel(WgradBf3Args p)
 {
-    constexpr int NT = 64 * NW, TILE = 192;                  // a tile = 32 rows x (3 pieces x 2 halves) 16-byte words
+    constexpr int NT = 64 * NW, TILE = 64 * P;               // a tile = 32 rows x (P pieces x 2 halves) 16-byte words
     constexpr int E = (KG * TILE + NT - 1) / NT;             // gather entries per thread and trip
-    __shared__ __attribute__((aligned(16))) short s_a[KG][3][32 * 16];          // [offset][piece][row][16 ch]
+    __shared__ __attribute__((aligned(16))) short s_a[KG][P][32 * 16];          // [offset][piece][row][16 ch]
     const int l = lane_id(), q = l >> 4, cl = l & 15, w = wave_id();
     const int k0 = blockIdx.y * KG;
     const int C8 = p.Cin >> 3;
@@ -2364,15 +2435,15 @@ __global__ __launch_bounds__(64 * NW, 2) void spconv_wgrad_bf3_kernel(WgradBf3Ar
     const int r_begin = blockIdx.x * p.rows_per_block;
     const int r_end = min(p.Vout, r_begin + p.rows_per_block);
     const int rd0 = (8 * q + (cl >> 2)) * 16 + 4 * (cl & 3), rd1 = rd0 + 4 * 16;
-    // entry e of the workgroup's gather list: offset e / 192, row (e % 192) / 6, piece ((e % 6) >> 1), half e & 1 -- packed
+    // entry e of the workgroup's gather list: offset e / TILE, row (e % TILE) / 2P, piece ((e % 2P) >> 1), half e & 1 -- packed
     // into one register per entry: bits 0-14 LDS slot (in 16-byte words... shorts / 8), 15-19 row, 20-27 source word, 28-32 offset
     unsigned e_pk[E];
 #pragma unroll
     for (int i = 0; i < E; i++) {
         const int e = threadIdx.x + i * NT;
-        const int kk = min(e / TILE, KG - 1), rem = e % TILE, row = rem / 6, pc = (rem % 6) >> 1, half = rem & 1;
+        const int kk = min(e / TILE, KG - 1), rem = e % TILE, row = rem / (2 * P), pc = (rem % (2 * P)) >> 1, half = rem & 1;
         const bool ok = e < KG * TILE && k0 + kk < p.K;
-        e_pk[i] = (unsigned)(((kk * 3 + pc) * 512 + row * 16 + half * 8) >> 3) | ((unsigned)row << 15)
+        e_pk[i] = (unsigned)(((kk * P + pc) * 512 + row * 16 + half * 8) >> 3) | ((unsigned)row << 15)
                   | ((unsigned)(pc * C8 + blockIdx.z * 2 + half) << 20) | ((unsigned)(ok ? kk : 15) << 28);
     }
     auto load_idx = [&](int r0, int (&idx)[E]) {
@@ -2387,24 +2458,24 @@ __global__ __launch_bounds__(64 * NW, 2) void spconv_wgrad_bf3_kernel(WgradBf3Ar
     auto gather = [&](const int (&idx)[E], uint4 (&g)[E]) {
 #pragma unroll
         for (int i = 0; i < E; i++) {
-            const uint4 v = reinterpret_cast<const uint4 *>(p.xs)[(size_t)max(idx[i], 0) * 3 * C8 + ((e_pk[i] >> 20) & 255)];
+            const uint4 v = reinterpret_cast<const uint4 *>(p.xs)[(size_t)max(idx[i], 0) * P * C8 + ((e_pk[i] >> 20) & 255)];
             const unsigned keep = idx[i] >= 0 ? 0xffffffffu : 0u;
             g[i] = make_uint4(v.x & keep, v.y & keep, v.z & keep, v.w & keep);
         }
     };
-    auto load_b = [&](int r0, uint4 (&bw)[NBW][3]) {
+    auto load_b = [&](int r0, uint4 (&bw)[NBW][P]) {
 #pragma unroll
         for (int j = 0; j < NBW; j++) {
             const int nb = w * NBW + j;
-            const uint4 *src = reinterpret_cast<const uint4 *>(p.dout_img) + (((size_t)(r0 >> 5) * p.NBtot + min(nb, p.NBtot - 1)) * 3) * 64 + l;
+            const uint4 *src = reinterpret_cast<const uint4 *>(p.dout_img) + (((size_t)(r0 >> 5) * p.NBtot + min(nb, p.NBtot - 1)) * P) * 64 + l;
             const bool ok = nb < p.NBtot && r0 < r_end;
 #pragma unroll
-            for (int pc = 0; pc < 3; pc++) bw[j][pc] = ok ? src[pc * 64] : make_uint4(0, 0, 0, 0);
+            for (int pc = 0; pc < P; pc++) bw[j][pc] = ok ? src[pc * 64] : make_uint4(0, 0, 0, 0);
         }
     };
     int idx_n[E];
     uint4 g[E];
-    uint4 bw[NBW][3];
+    uint4 bw[NBW][P];
     {
         int idx_c[E];
         load_idx(r_begin, idx_c);
@@ -2419,11 +2490,11 @@ __global__ __launch_bounds__(64 * NW, 2) void spconv_wgrad_bf3_kernel(WgradBf3Ar
         for (int i = 0; i < E; i++)
             if (E * NT == KG * TILE || threadIdx.x + i * NT < KG * TILE) *reinterpret_cast<uint4 *>(tiles + (e_pk[i] & 0x7fff) * 8) = g[i];
         __syncthreads();
-        uint4 bc[NBW][3];
+        uint4 bc[NBW][P];
 #pragma unroll
         for (int j = 0; j < NBW; j++)
 #pragma unroll
-            for (int pc = 0; pc < 3; pc++) bc[j][pc] = bw[j][pc];
+            for (int pc = 0; pc < P; pc++) bc[j][pc] = bw[j][pc];
         // the next trip's operands fly during this trip's MFMAs
         gather(idx_n, g);
         load_idx(r0 + 64, idx_n);
@@ -2432,8 +2503,8 @@ __global__ __launch_bounds__(64 * NW, 2) void spconv_wgrad_bf3_kernel(WgradBf3Ar
         for (int kk = 0; kk < KG; kk++) {
             bf16x8 a[3];
 #pragma unroll
-            for (int pc = 0; pc < 3; pc++) {
-                const short *tp = tiles + (kk * 3 + pc) * 512;
+            for (int pc = 0; pc < P; pc++) {
+                const short *tp = tiles + (kk * P + pc) * 512;
                 const s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4 *)(tp + rd0));
                 const s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4 *)(tp + rd1));
                 short t8[8] = {lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
@@ -2441,14 +2512,19 @@ __global__ __launch_bounds__(64 * NW, 2) void spconv_wgrad_bf3_kernel(WgradBf3Ar
             }
 #pragma unroll
             for (int j = 0; j < NBW; j++) {
-                const bf16x8 w0 = *reinterpret_cast<const bf16x8 *>(&bc[j][0]), w1 = *reinterpret_cast<const bf16x8 *>(&bc[j][1]),
-                             w2 = *reinterpret_cast<const bf16x8 *>(&bc[j][2]);
-                acc[kk][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a[2], w0, acc[kk][j], 0, 0, 0);
-                acc[kk][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a[0], w2, acc[kk][j], 0, 0, 0);
-                acc[kk][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a[1], w1, acc[kk][j], 0, 0, 0);
-                acc[kk][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a[1], w0, acc[kk][j], 0, 0, 0);
-                acc[kk][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a[0], w1, acc[kk][j], 0, 0, 0);
-                acc[kk][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a[0], w0, acc[kk][j], 0, 0, 0);
+                const bf16x8 w0 = *reinterpret_cast<const bf16x8 *>(&bc[j][0]),
+                             w1 = *reinterpret_cast<const bf16x8 *>(&bc[j][P >= 2 ? 1 : 0]),
+                             w2 = *reinterpret_cast<const bf16x8 *>(&bc[j][P >= 3 ? 2 : 0]);
+                if constexpr (P == 3) {
+                    acc[kk][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a[2], w0, acc[kk][j], 0, 0, 0);
+                    acc[kk][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a[0], w2, acc[kk][j], 0, 0, 0);
+                    acc[kk][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a[1], w1, acc[kk][j], 0, 0, 0);
+                    acc[kk][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a[1], w0, acc[kk][j], 0, 0, 0);
+                    acc[kk][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a[0], w1, acc[kk][j], 0, 0, 0);
+                    acc[kk][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a[0], w0, acc[kk][j], 0, 0, 0);
+                } else {
+                    mfma_pieces<P>(acc[kk][j], a[0], a[1], a[2], w0, w1, w2);
+                }
             }
         }
     }
@@ -2468,11 +2544,11 @@ __global__ __launch_bounds__(64 * NW, 2) void spconv_wgrad_bf3_kernel(WgradBf3Ar
     }
 }
 
-template <int KG, int NW, int NBW>
+template <int KG, int NW, int NBW, int P>
 int launch_wgrad_bf3(const WgradBf3Args &p, int nblk_rows, hipStream_t stream)
 {
     dim3 grid(nblk_rows, ms3d_divup(p.K, KG), ms3d_divup(p.Cin, 16));
-    spconv_wgrad_bf3_kernel<KG, NW, NBW><<<grid, 64 * NW, 0, stream>>>(p);
+    spconv_wgrad_bf3_kernel<KG, NW, NBW, P><<<grid, 64 * NW, 0, stream>>>(p);
     MS3D_LAUNCH_CHECK();
     return 0;
 }
@@ -3287,7 +3363,7 @@ int ms3d_spconv_prep_weights(const float *W, int K, int Cin_eff, int Cout_eff, i
 {
     const int NCH = ms3d_divup(Cin_eff, 16), NBtot = ms3d_divup(Cout_eff, 16);
     const long total = (long)K * NCH * 4 * NBtot * 64;
-    prep_weights_kernel<<<(int)((total + 255) / 256 < 2048 ? (total + 255) / 256 : 2048), 256, 0, (hipStream_t)stream>>>(
+    prep_weights_kernel<3><<<(int)((total + 255) / 256 < 2048 ? (total + 255) / 256 : 2048), 256, 0, (hipStream_t)stream>>>(
         W, wf, K, Cin_eff, Cout_eff, NCH, NBtot, transpose, mirror, nullptr, 0, 0, 0, wf_stream, nullptr, 1);
     MS3D_LAUNCH_CHECK();
     return 0;
@@ -3301,8 +3377,16 @@ static int prep_weights_pair_impl(const float *W, int K, int Cin, int Cout, int 
     const int NCH2 = ms3d_divup(Cout, 16), NBtot2 = ms3d_divup(Cin, 16);
     const long total = (long)K * NCH * 4 * NBtot * 64, total2 = (long)K * NCH2 * 4 * NBtot2 * 64;
     const long m = total > total2 ? total : total2;
-    prep_weights_kernel<<<(int)((m + 255) / 256 < 2048 ? (m + 255) / 256 : 2048), 256, 0, stream>>>(
-        W, wf, K, Cin, Cout, NCH, NBtot, 0, 0, wft, NCH2, NBtot2, mirror_bwd, wf_aux, wft_aux, aux_kind);
+    const dim3 grid((int)((m + 255) / 256 < 2048 ? (m + 255) / 256 : 2048));
+    if (aux_kind == 3)
+        prep_weights_kernel<2><<<grid, 256, 0, stream>>>(W, wf, K, Cin, Cout, NCH, NBtot, 0, 0, wft, NCH2, NBtot2, mirror_bwd,
+                                                         wf_aux, wft_aux, aux_kind);
+    else if (aux_kind == 4)
+        prep_weights_kernel<1><<<grid, 256, 0, stream>>>(W, wf, K, Cin, Cout, NCH, NBtot, 0, 0, wft, NCH2, NBtot2, mirror_bwd,
+                                                         wf_aux, wft_aux, aux_kind);
+    else
+        prep_weights_kernel<3><<<grid, 256, 0, stream>>>(W, wf, K, Cin, Cout, NCH, NBtot, 0, 0, wft, NCH2, NBtot2, mirror_bwd,
+                                                         wf_aux, wft_aux, aux_kind);
     MS3D_LAUNCH_CHECK();
     return 0;
 }
@@ -3318,12 +3402,20 @@ int ms3d_spconv_prep_blocks(int K, int Cin, int Cout)
 {
     return (int)(((long)K * ms3d_divup(Cin, 16) * 4 * ms3d_divup(Cout, 16) * 64 + 255) / 256);
 }
-int ms3d_spconv_prep_weights_multi(const void *descs, int n, int total_blocks, ms3d_stream_t stream)
+int ms3d_spconv_prep_weights_multi_p(const void *descs, int n, int total_blocks, int precision, ms3d_stream_t stream)
 {
+    if (precision < 0 || precision > 2) return MS3D_E_UNSUPPORTED;
     if (n <= 0 || total_blocks <= 0) return 0;
-    prep_weights_multi_kernel<<<total_blocks, 256, 0, (hipStream_t)stream>>>(reinterpret_cast<const PrepDesc *>(descs), n);
+    const PrepDesc *d = reinterpret_cast<const PrepDesc *>(descs);
+    if (precision == 1) prep_weights_multi_kernel<2><<<total_blocks, 256, 0, (hipStream_t)stream>>>(d, n);
+    else if (precision == 2) prep_weights_multi_kernel<1><<<total_blocks, 256, 0, (hipStream_t)stream>>>(d, n);
+    else prep_weights_multi_kernel<3><<<total_blocks, 256, 0, (hipStream_t)stream>>>(d, n);
     MS3D_LAUNCH_CHECK();
     return 0;
+}
+int ms3d_spconv_prep_weights_multi(const void *descs, int n, int total_blocks, ms3d_stream_t stream)
+{
+    return ms3d_spconv_prep_weights_multi_p(descs, n, total_blocks, 0, stream);
 }
 
 // mean / invstd / scale / shift (+ running stats) from per-block (sum, sum of squares) partials written by a conv epilogue
@@ -3679,6 +3771,15 @@ int ms3d_spconv_aux_kind(int K, int Cin, int Cout)
     return ms3d_spconv_wants_stream_image(K, Cin, Cout) ? 1 : 0;
 }
 
+// the same at a matmul precision (0 highest, 1 high, 2 medium): the bf16 image of the wide layers keeps 3 / 2 / 1 pieces
+// (aux kind 2 / 3 / 4); every other layer's aux slot is what it is at the highest precision
+int ms3d_spconv_aux_kind_p(int K, int Cin, int Cout, int precision)
+{
+    if (precision < 0 || precision > 2) return MS3D_E_UNSUPPORTED;
+    const int kind = ms3d_spconv_aux_kind(K, Cin, Cout);
+    return kind == 2 ? 2 + precision : kind;
+}
+
 int ms3d_kmap_pairlist_wanted(int K, int Vout) { return pairlist_min_rows() >= 0 && Vout >= pairlist_min_rows() && K > 1 && K <= 27; }
 
 // rows per tile of the pair list a forward / backward-data convolution of this shape walks: 0 = none (table walk /
@@ -3737,7 +3838,8 @@ static int spconv_forward_impl(const float *in, const float *wf, const int *nbr,
     p.bias = bias;
     p.wfs = nullptr;
     p.wfb = nullptr;
-    if (aux_kind != 1 && aux_kind != 2) wf_stream = nullptr;
+    const int pieces = aux_pieces(aux_kind);    // bf16 image of 3 / 2 / 1 pieces, or none
+    if (aux_kind != 1 && !pieces) wf_stream = nullptr;
     p.pl_tile_start = pl_tile_start; p.pl_entries = pl_entries;
     p.out_stats = (out_stats && bn_partial && !bn_x) ? 1 : 0;
     static const int dyn_picks = [] { const char *e = getenv("MS3D_PL_DYNAMIC"); return e ? atoi(e) : 0; }();
@@ -3793,27 +3895,32 @@ static int spconv_forward_impl(const float *in, const float *wf, const int *nbr,
         return MS3D_E_UNSUPPORTED;
     }
     p.RT = g.small ? g.rt : 1;
-    if (g.small && g.rt > 1 && aux_kind == 2 && wf_stream) {
+    // (P, NBT) -> the instantiation of a bf16 kernel family
+#define MS3D_BF_NBT(LAUNCH, P_, ...)                                                                                   \
+    switch (g.nbt) {                                                                                                   \
+        case 2: return LAUNCH<2, ##__VA_ARGS__, P_>(p, grid, g.threads, LDS_, stream);                                \
+        case 3: return LAUNCH<3, ##__VA_ARGS__, P_>(p, grid, g.threads, LDS_, stream);                                \
+        case 4: return LAUNCH<4, ##__VA_ARGS__, P_>(p, grid, g.threads, LDS_, stream);                                \
+        case 5: return LAUNCH<5, ##__VA_ARGS__, P_>(p, grid, g.threads, LDS_, stream);                                \
+        case 6: return LAUNCH<6, ##__VA_ARGS__, P_>(p, grid, g.threads, LDS_, stream);                                \
+        case 7: return LAUNCH<7, ##__VA_ARGS__, P_>(p, grid, g.threads, LDS_, stream);                                \
+        case 8: return LAUNCH<8, ##__VA_ARGS__, P_>(p, grid, g.threads, LDS_, stream);                                \
+    }
+#define MS3D_BF_P(LAUNCH, ...)                                                                                         \
+    if (pieces == 3) { MS3D_BF_NBT(LAUNCH, 3, ##__VA_ARGS__) }                                                         \
+    else if (pieces == 2) { MS3D_BF_NBT(LAUNCH, 2, ##__VA_ARGS__) }                                                    \
+    else { MS3D_BF_NBT(LAUNCH, 1, ##__VA_ARGS__) }
+    if (g.small && g.rt > 1 && pieces && wf_stream) {
         // the geometry (and the caller's statistics partials) count RT tiles per block
         p.wfb = wf_stream;
-#define MS3D_RT_CASE(N) case N: return launch_fwd_small_bf3_rt<N, 3>(p, grid, g.threads, g.lds, stream);
-        switch (g.nbt) {
-            MS3D_RT_CASE(2) MS3D_RT_CASE(3) MS3D_RT_CASE(4) MS3D_RT_CASE(5) MS3D_RT_CASE(6) MS3D_RT_CASE(7) MS3D_RT_CASE(8)
-        }
-#undef MS3D_RT_CASE
+        const size_t LDS_ = g.lds;
+        MS3D_BF_P(launch_fwd_small_bf3_rt, 3)
         return MS3D_E_UNSUPPORTED;
     }
-    if (g.small && aux_kind == 2 && wf_stream && bf3_dims_ok(K, Cin, Cout) && g.nbt >= 2) {
+    if (g.small && pieces && wf_stream && bf3_dims_ok(K, Cin, Cout) && g.nbt >= 2) {
         p.wfb = wf_stream;
-        switch (g.nbt) {
-            case 2: return launch_fwd_small_bf3<2>(p, grid, g.threads, g.lds, stream);
-            case 3: return launch_fwd_small_bf3<3>(p, grid, g.threads, g.lds, stream);
-            case 4: return launch_fwd_small_bf3<4>(p, grid, g.threads, g.lds, stream);
-            case 5: return launch_fwd_small_bf3<5>(p, grid, g.threads, g.lds, stream);
-            case 6: return launch_fwd_small_bf3<6>(p, grid, g.threads, g.lds, stream);
-            case 7: return launch_fwd_small_bf3<7>(p, grid, g.threads, g.lds, stream);
-            case 8: return launch_fwd_small_bf3<8>(p, grid, g.threads, g.lds, stream);
-        }
+        const size_t LDS_ = g.lds;
+        MS3D_BF_P(launch_fwd_small_bf3)
     }
     if (g.small) {
         switch (g.nbt) {
@@ -3828,11 +3935,11 @@ static int spconv_forward_impl(const float *in, const float *wf, const int *nbr,
         }
         return MS3D_E_UNSUPPORTED;
     }
-    if (aux_kind == 2 && wf_stream && bf3_dims_ok(K, Cin, Cout) && g.nbt >= 2) {
+    if (pieces && wf_stream && bf3_dims_ok(K, Cin, Cout) && g.nbt >= 2) {
         // same grid as the f32 table walk (the statistics partials are sized for it); only the staged group shrinks:
-        // three bf16 pieces are 6 bytes per weight
+        // three bf16 pieces are 6 bytes per weight (two 4, one 2: more chunks per stage)
         const int nc32 = (Cin + 31) / 32;
-        const size_t per_slab = (size_t)g.nbt * 3 * 1024;                 // one (offset, 32-channel chunk) of the slice
+        const size_t per_slab = (size_t)g.nbt * pieces * 1024;            // one (offset, 32-channel chunk) of the slice
         const size_t extra = (bn_x != nullptr || p.out_stats) ? STAT_MAX_WAVES * stat_slot_floats(g.nbt) * sizeof(float) : 0;
         const int slabs = (int)((LDS_BUDGET - extra) / per_slab);
         // a stage = one gather round's offsets x as many chunks as fit beside them.  (Layers whose f32 image is LDS
@@ -3846,18 +3953,12 @@ static int spconv_forward_impl(const float *in, const float *wf, const int *nbr,
             p.wfb = wf_stream;
             p.G = go;
             p.GC = gc;
-            const size_t lds = per_slab * p.G * p.GC + extra;
-            switch (g.nbt) {
-                case 2: return launch_fwd_bf3<2>(p, grid, g.threads, lds, stream);
-                case 3: return launch_fwd_bf3<3>(p, grid, g.threads, lds, stream);
-                case 4: return launch_fwd_bf3<4>(p, grid, g.threads, lds, stream);
-                case 5: return launch_fwd_bf3<5>(p, grid, g.threads, lds, stream);
-                case 6: return launch_fwd_bf3<6>(p, grid, g.threads, lds, stream);
-                case 7: return launch_fwd_bf3<7>(p, grid, g.threads, lds, stream);
-                case 8: return launch_fwd_bf3<8>(p, grid, g.threads, lds, stream);
-            }
+            const size_t LDS_ = per_slab * p.G * p.GC + extra;
+            MS3D_BF_P(launch_fwd_bf3)
         }
     }
+#undef MS3D_BF_P
+#undef MS3D_BF_NBT
     switch (g.nbt) {
         case 1: return launch_fwd<1>(p, grid, g.threads, g.lds, aligned, stream);
         case 2: return launch_fwd<2>(p, grid, g.threads, g.lds, aligned, stream);
@@ -3915,17 +4016,30 @@ static int wgrad_k1_chunks(int Vout, int K, int Cin, int Cout)
     int c = ms3d_divup(Vout, 128);
     return c > k1_max ? k1_max : c;
 }
-// slabs + (bf16x3 kernel) the dout operand image and the activated input pieces
-size_t ms3d_spconv_wgrad_ws_floats(int Vout, int K, int Cin, int Cout)
+// bf16 pieces of the backward-weight kernel of this shape at a matmul precision: 0 = the f32 kernels (every precision),
+// 3 / 2 / 1 = the bf16 kernel at precision 0 / 1 / 2; MS3D_E_UNSUPPORTED for another precision
+int ms3d_spconv_wgrad_pieces(int Vout, int K, int Cin, int Cout, int offset_list, int precision)
 {
+    if (precision < 0 || precision > 2) return MS3D_E_UNSUPPORTED;
+    return ms3d_spconv_wgrad_is_bf16x3(Vout, K, Cin, Cout, offset_list) ? 3 - precision : 0;
+}
+
+// slabs + (bf16 kernel) the dout operand image and the activated input pieces; 0 for a precision outside 0..2.
+// Fewer pieces need less: the precision-0 size is an upper bound for every precision.
+size_t ms3d_spconv_wgrad_ws_floats_p(int Vout, int K, int Cin, int Cout, int precision)
+{
+    if (precision < 0 || precision > 2) return 0;
     const int k1 = wgrad_k1_chunks(Vout, K, Cin, Cout), rc = ms3d_spconv_wgrad_row_chunks(Vout);
     size_t n = (size_t)(k1 > rc ? k1 : rc) * K * Cin * Cout + 64;
     if (wgrad_bf3_ok(Vout, K, Cin, Cout, false)) {
-        n += (size_t)ms3d_divup(Vout, 32) * ms3d_divup(Cout, 16) * 3 * 64 * 4 + 8;        // dout image, 16 B units
-        n += (size_t)Vout * Cin * 3 / 2 + 8;                                                 // 6 B per input element
+        const int P = 3 - precision;
+        n += (size_t)ms3d_divup(Vout, 32) * ms3d_divup(Cout, 16) * P * 64 * 4 + 8;        // dout image, 16 B units
+        n += (size_t)Vout * Cin * P / 2 + 8;                                                 // 2P B per input element
     }
     return n;
 }
+
+size_t ms3d_spconv_wgrad_ws_floats(int Vout, int K, int Cin, int Cout) { return ms3d_spconv_wgrad_ws_floats_p(Vout, K, Cin, Cout, 0); }
 
 int ms3d_spconv_wgrad_row_chunks(int Vout)
 {
@@ -3944,7 +4058,17 @@ int ms3d_spconv_wgrad_row_chunks(int Vout)
 static int spconv_backward_weight_impl(const float *in, const float *dout, const int *nbr, int Vout, int K, int Cin, int Cout,
                                        float *dW, const float *pre_scale, const float *pre_shift, int pre_relu,
                                        float *partial_ws, const int *ol_kt_start, const int *ol_entries, int *defer_nblk,
-                                       ms3d_stream_t stream_, void *defer_launch = nullptr);
+                                       ms3d_stream_t stream_, void *defer_launch = nullptr, int precision = 0);
+
+int ms3d_spconv_backward_weight_p(const float *in, const float *dout, const int *nbr, int Vout, int K, int Cin, int Cout,
+                                  float *dW, const float *pre_scale, const float *pre_shift, int pre_relu,
+                                  float *partial_ws, const int *ol_kt_start, const int *ol_entries, int precision,
+                                  ms3d_stream_t stream_)
+{
+    if (precision < 0 || precision > 2) return MS3D_E_UNSUPPORTED;
+    return spconv_backward_weight_impl(in, dout, nbr, Vout, K, Cin, Cout, dW, pre_scale, pre_shift, pre_relu, partial_ws,
+                                       ol_kt_start, ol_entries, nullptr, stream_, nullptr, precision);
+}
 
 int ms3d_spconv_backward_weight(const float *in, const float *dout, const int *nbr, int Vout, int K, int Cin, int Cout,
                                 float *dW, const float *pre_scale, const float *pre_shift, int pre_relu,
@@ -3957,7 +4081,7 @@ int ms3d_spconv_backward_weight(const float *in, const float *dout, const int *n
 static int spconv_backward_weight_impl(const float *in, const float *dout, const int *nbr, int Vout, int K, int Cin, int Cout,
                                        float *dW, const float *pre_scale, const float *pre_shift, int pre_relu,
                                        float *partial_ws, const int *ol_kt_start, const int *ol_entries, int *defer_nblk,
-                                       ms3d_stream_t stream_, void *defer_launch)
+                                       ms3d_stream_t stream_, void *defer_launch, int precision)
 {
     hipStream_t stream = (hipStream_t)stream_;
     const long n = (long)K * Cin * Cout;
@@ -4041,15 +4165,24 @@ static int spconv_backward_weight_impl(const float *in, const float *dout, const
         return 0;
     }
     if (wgrad_bf3_ok(Vout, K, Cin, Cout, use_list)) {
-        // wide submanifold layers: both operands pre-split into three bf16 pieces by two elementwise passes
+        // wide submanifold layers: both operands pre-split into P = 3 (2, 1 at the lower precisions) bf16 pieces by two
+        // elementwise passes
+        const int P = 3 - precision;
         float *base = partial_ws + (size_t)ms3d_spconv_wgrad_row_chunks(Vout) * K * Cin * Cout;
         bf16x8 *img = reinterpret_cast<bf16x8 *>((reinterpret_cast<uintptr_t>(base) + 15) & ~(uintptr_t)15);
         const long ntile = ms3d_divup(Vout, 32);
-        bf16x8 *xs = img + (size_t)ntile * nb * 3 * 64;
+        bf16x8 *xs = img + (size_t)ntile * nb * P * 64;
         const long t1 = ntile * nb * 64, t2 = (long)Vout * (Cin / 8);
         const int nb1 = (int)((t1 + 255) / 256), nb2 = (int)((t2 + 255) / 256);
-        wgrad_bf3_operands_kernel<<<nb1 + nb2, 256, 0, stream>>>(dout, in, Vout, Cin, Cout, nb, ntile, nb1, pre_scale, pre_shift,
-                                                                pre_relu, img, xs);
+        if (P == 3)
+            wgrad_bf3_operands_kernel<3><<<nb1 + nb2, 256, 0, stream>>>(dout, in, Vout, Cin, Cout, nb, ntile, nb1, pre_scale,
+                                                                       pre_shift, pre_relu, img, xs);
+        else if (P == 2)
+            wgrad_bf3_operands_kernel<2><<<nb1 + nb2, 256, 0, stream>>>(dout, in, Vout, Cin, Cout, nb, ntile, nb1, pre_scale,
+                                                                       pre_shift, pre_relu, img, xs);
+        else
+            wgrad_bf3_operands_kernel<1><<<nb1 + nb2, 256, 0, stream>>>(dout, in, Vout, Cin, Cout, nb, ntile, nb1, pre_scale,
+                                                                       pre_shift, pre_relu, img, xs);
         MS3D_LAUNCH_CHECK();
         WgradBf3Args q;
         q.xs = xs; q.dout_img = img; q.nbr = nbr; q.partial = partial_ws; q.Vout = Vout; q.K = K; q.Cin = Cin; q.Cout = Cout;
@@ -4071,8 +4204,11 @@ static int spconv_backward_weight_impl(const float *in, const float *dout, const
         // waves split the output columns (NW waves x NBW blocks of 16), a workgroup takes KG offsets
         // (KG offsets per workgroup, waves, 16-column blocks per wave): the largest tiles that stay inside 256 registers at
         // two workgroups per CU -- every larger one tried spills (profiles/r03_fwd_experiments.txt section 6)
-        rc = nb == 3 ? launch_wgrad_bf3<14, 3, 1>(q, nblk, stream) : nb == 4 ? launch_wgrad_bf3<9, 4, 1>(q, nblk, stream)
-           : nb <= 6 ? launch_wgrad_bf3<9, 3, 2>(q, nblk, stream) : launch_wgrad_bf3<9, 4, 2>(q, nblk, stream);
+#define MS3D_WG_BF(P_)                                                                                                 \
+    (nb == 3 ? launch_wgrad_bf3<14, 3, 1, P_>(q, nblk, stream) : nb == 4 ? launch_wgrad_bf3<9, 4, 1, P_>(q, nblk, stream)   \
+     : nb <= 6 ? launch_wgrad_bf3<9, 3, 2, P_>(q, nblk, stream) : launch_wgrad_bf3<9, 4, 2, P_>(q, nblk, stream))
+        rc = P == 3 ? MS3D_WG_BF(3) : P == 2 ? MS3D_WG_BF(2) : MS3D_WG_BF(1);
+#undef MS3D_WG_BF
         if (rc) return rc;
         if (defer_nblk) { *defer_nblk = nblk; return 0; }
         launch_wgrad_reduce(partial_ws, nblk, n, dW, stream);
@@ -4295,15 +4431,16 @@ size_t ms3d_spconv_layer_ws_floats(int Vin, int Vout, int K, int Cin, int Cout)
 
 // forward: weight images (kept in wf_buf for the backward pass) + conv (+ fused input BN/ReLU, residual, bias) +
 // optional output statistics (stat_partial [ms3d_spconv_partial_blocks(Vout,K,Cin,Cout)][2][Cout])
-int ms3d_spconv_layer_forward(const float *x, const float *W, const int *nbr_fwd, int Vout, int K, int Cin, int Cout,
-                              int mirror_bwd, const float *pre_scale, const float *pre_shift, int pre_relu,
-                              const float *residual, const float *bias, float *wf_buf, float *y, float *stat_partial,
-                              const int *pl_tile_start, const int *pl_entries, void *ev_start, void *ev_stop,
-                              ms3d_stream_t stream)
+int ms3d_spconv_layer_forward_p(const float *x, const float *W, const int *nbr_fwd, int Vout, int K, int Cin, int Cout,
+                                int mirror_bwd, const float *pre_scale, const float *pre_shift, int pre_relu,
+                                const float *residual, const float *bias, float *wf_buf, float *y, float *stat_partial,
+                                const int *pl_tile_start, const int *pl_entries, void *ev_start, void *ev_stop, int precision,
+                                ms3d_stream_t stream)
 {
     const size_t nwf = ms3d_spconv_wf_floats(K, Cin, Cout);  // wf_buf = [wf | aux (2n) | wft | aux (2n)], 6n floats
     float *wf = wf_buf, *wft = wf_buf + 3 * nwf;
-    const int aux_kind = ms3d_spconv_aux_kind(K, Cin, Cout);
+    const int aux_kind = ms3d_spconv_aux_kind_p(K, Cin, Cout, precision);   // W == NULL: wf_buf must hold images of this kind
+    if (aux_kind == MS3D_E_UNSUPPORTED) return MS3D_E_UNSUPPORTED;
     int rc = W ? prep_weights_pair_impl(W, K, Cin, Cout, mirror_bwd, wf, wft, wf + nwf, wft + nwf, aux_kind, (hipStream_t)stream) : 0;  // W == NULL: wf_buf is current
     if (rc) return rc;
     // optional HIP events bracketing ONLY the convolution kernel, on the stream it is launched on (bench.py roofline)
@@ -4313,6 +4450,16 @@ int ms3d_spconv_layer_forward(const float *x, const float *W, const int *nbr_fwd
                              pl_entries, wf + nwf, aux_kind, stream);
     if (ev_stop) MS3D_CHECK(hipEventRecord((hipEvent_t)ev_stop, (hipStream_t)stream));
     return rc;
+}
+
+int ms3d_spconv_layer_forward(const float *x, const float *W, const int *nbr_fwd, int Vout, int K, int Cin, int Cout,
+                              int mirror_bwd, const float *pre_scale, const float *pre_shift, int pre_relu,
+                              const float *residual, const float *bias, float *wf_buf, float *y, float *stat_partial,
+                              const int *pl_tile_start, const int *pl_entries, void *ev_start, void *ev_stop,
+                              ms3d_stream_t stream)
+{
+    return ms3d_spconv_layer_forward_p(x, W, nbr_fwd, Vout, K, Cin, Cout, mirror_bwd, pre_scale, pre_shift, pre_relu, residual,
+                                       bias, wf_buf, y, stat_partial, pl_tile_start, pl_entries, ev_start, ev_stop, 0, stream);
 }
 
 void *ms3d_event_create(void)
@@ -4358,18 +4505,19 @@ static hipEvent_t order_event()
     return pool[dev][i];
 }
 
-int ms3d_spconv_layer_backward(const float *x, const float *dy, const float *wf_buf, const int *nbr_fwd,
-                               const int *nbr_bwd, int Vin, int Vout, int K, int Cin, int Cout, const float *scale,
-                               const float *shift, const float *mean, const float *invstd, int pre_relu, int training,
-                               int need_dx, float *dx, const float *dx_add, float *dgb, float *dW, float *ws,
-                               const int *ol_fwd_kt_start, const int *ol_fwd_entries, const int *pl_bwd_tile_start,
-                               const int *pl_bwd_entries, void *ev_start, void *ev_stop, void *ev_wg_start, void *ev_wg_stop,
-                               float *ws_wgrad, ms3d_stream_t wgrad_stream, int join, float *wgrad_slabs,
-                               int *wgrad_deferred_nblk, void *wgrad_deferred_launch, ms3d_stream_t stream)
+int ms3d_spconv_layer_backward_p(const float *x, const float *dy, const float *wf_buf, const int *nbr_fwd,
+                                 const int *nbr_bwd, int Vin, int Vout, int K, int Cin, int Cout, const float *scale,
+                                 const float *shift, const float *mean, const float *invstd, int pre_relu, int training,
+                                 int need_dx, float *dx, const float *dx_add, float *dgb, float *dW, float *ws,
+                                 const int *ol_fwd_kt_start, const int *ol_fwd_entries, const int *pl_bwd_tile_start,
+                                 const int *pl_bwd_entries, void *ev_start, void *ev_stop, void *ev_wg_start, void *ev_wg_stop,
+                                 float *ws_wgrad, ms3d_stream_t wgrad_stream, int join, float *wgrad_slabs,
+                                 int *wgrad_deferred_nblk, void *wgrad_deferred_launch, int precision, ms3d_stream_t stream)
 {
     const size_t nwf = ms3d_spconv_wf_floats(K, Cin, Cout);
     const float *wft = wf_buf + 3 * nwf, *wfts = wf_buf + 4 * nwf;
-    const int aux_kind = ms3d_spconv_aux_kind(K, Cin, Cout);
+    const int aux_kind = ms3d_spconv_aux_kind_p(K, Cin, Cout, precision);   // the kind layer_forward_p laid out
+    if (aux_kind == MS3D_E_UNSUPPORTED) return MS3D_E_UNSUPPORTED;
     const bool bn = scale != nullptr;
     int rc;
     // Backward-weight needs x and dy only, not the backward-data result: with a second stream (and its own slab
@@ -4385,7 +4533,7 @@ int ms3d_spconv_layer_backward(const float *x, const float *dy, const float *wf_
         int r = spconv_backward_weight_impl(x, dy, nbr_fwd, Vout, K, Cin, Cout, dW, scale, shift, pre_relu,
                                             wgrad_slabs ? wgrad_slabs : slabs, ol_fwd_kt_start, ol_fwd_entries,
                                             wgrad_slabs ? wgrad_deferred_nblk : nullptr, (ms3d_stream_t)side,
-                                            (wgrad_slabs && !ev_wg_start) ? wgrad_deferred_launch : nullptr);
+                                            (wgrad_slabs && !ev_wg_start) ? wgrad_deferred_launch : nullptr, precision);
         if (ev_wg_stop) MS3D_CHECK(hipEventRecord((hipEvent_t)ev_wg_stop, side));
         return r;
     };
@@ -4450,6 +4598,21 @@ int ms3d_spconv_layer_backward(const float *x, const float *dy, const float *wf_
     const int pb2 = ms3d_spconv_partial_blocks(Vin, K, Cout, Cin, ms3d_spconv_pairlist_rows_dense(Vin, K, Cout, Cin));
     slabs = ws + (size_t)(pb0 > pb1 ? (pb0 > pb2 ? pb0 : pb2) : (pb1 > pb2 ? pb1 : pb2)) * 2 * Cin;
     return run_wgrad();
+}
+
+int ms3d_spconv_layer_backward(const float *x, const float *dy, const float *wf_buf, const int *nbr_fwd,
+                               const int *nbr_bwd, int Vin, int Vout, int K, int Cin, int Cout, const float *scale,
+                               const float *shift, const float *mean, const float *invstd, int pre_relu, int training,
+                               int need_dx, float *dx, const float *dx_add, float *dgb, float *dW, float *ws,
+                               const int *ol_fwd_kt_start, const int *ol_fwd_entries, const int *pl_bwd_tile_start,
+                               const int *pl_bwd_entries, void *ev_start, void *ev_stop, void *ev_wg_start, void *ev_wg_stop,
+                               float *ws_wgrad, ms3d_stream_t wgrad_stream, int join, float *wgrad_slabs,
+                               int *wgrad_deferred_nblk, void *wgrad_deferred_launch, ms3d_stream_t stream)
+{
+    return ms3d_spconv_layer_backward_p(x, dy, wf_buf, nbr_fwd, nbr_bwd, Vin, Vout, K, Cin, Cout, scale, shift, mean, invstd,
+                                        pre_relu, training, need_dx, dx, dx_add, dgb, dW, ws, ol_fwd_kt_start, ol_fwd_entries,
+                                        pl_bwd_tile_start, pl_bwd_entries, ev_start, ev_stop, ev_wg_start, ev_wg_stop, ws_wgrad,
+                                        wgrad_stream, join, wgrad_slabs, wgrad_deferred_nblk, wgrad_deferred_launch, 0, stream);
 }
 
 }  // extern "C"

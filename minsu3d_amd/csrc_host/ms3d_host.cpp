@@ -38,23 +38,24 @@ inline const int *iptr(const OptT &t)
 
 }  // namespace
 
-// -> (y [vout, cout], stats [nparts, 2, cout] or None).  W undefined: wf_buf already holds the current weight images.
+// -> (y [vout, cout], stats [nparts, 2, cout] or None).  W undefined: wf_buf already holds the current weight images (laid
+// out for `precision`: 0 highest, 1 high, 2 medium -- the *_p entry points of the header).
 std::tuple<at::Tensor, OptT> conv_layer_forward(const at::Tensor &x, const OptT &W, const at::Tensor &nbr_fwd, int64_t vout,
                                                 int64_t K, int64_t cin, int64_t cout, bool mirror_bwd, const OptT &pre_scale,
                                                 const OptT &pre_shift, bool pre_relu, const OptT &residual, const OptT &bias,
                                                 at::Tensor wf_buf, int64_t nparts /* 0: no statistics */, const OptT &pl_tile_start,
-                                                const OptT &pl_entries, int64_t ev_start, int64_t ev_stop)
+                                                const OptT &pl_entries, int64_t ev_start, int64_t ev_stop, int64_t precision)
 {
     TORCH_CHECK(x.is_cuda() && x.is_contiguous() && x.scalar_type() == at::kFloat, "x: contiguous float32 device tensor");
     at::Tensor y = at::empty({vout, cout}, x.options());
     OptT stats;
     if (nparts > 0) stats = at::empty({nparts, 2, cout}, x.options());
-    check(ms3d_spconv_layer_forward(x.data_ptr<float>(), fptr(W), nbr_fwd.data_ptr<int>(), (int)vout, (int)K, (int)cin,
-                                    (int)cout, mirror_bwd ? 1 : 0, fptr(pre_scale), fptr(pre_shift), pre_relu ? 1 : 0,
-                                    fptr(residual), fptr(bias), wf_buf.data_ptr<float>(), y.data_ptr<float>(),
-                                    stats.has_value() ? stats->data_ptr<float>() : nullptr, iptr(pl_tile_start),
-                                    iptr(pl_entries), (void *)ev_start, (void *)ev_stop, cur()),
-          "ms3d_spconv_layer_forward");
+    check(ms3d_spconv_layer_forward_p(x.data_ptr<float>(), fptr(W), nbr_fwd.data_ptr<int>(), (int)vout, (int)K, (int)cin,
+                                      (int)cout, mirror_bwd ? 1 : 0, fptr(pre_scale), fptr(pre_shift), pre_relu ? 1 : 0,
+                                      fptr(residual), fptr(bias), wf_buf.data_ptr<float>(), y.data_ptr<float>(),
+                                      stats.has_value() ? stats->data_ptr<float>() : nullptr, iptr(pl_tile_start),
+                                      iptr(pl_entries), (void *)ev_start, (void *)ev_stop, (int)precision, cur()),
+          "ms3d_spconv_layer_forward_p");
     return {y, stats};
 }
 
@@ -67,7 +68,7 @@ std::tuple<OptT, OptT, at::Tensor, OptT, int64_t, py::bytes> conv_layer_backward
     int64_t vin, int64_t vout, int64_t K, int64_t cin, int64_t cout, const OptT &scale, const OptT &shift, const OptT &mean,
     const OptT &invstd, bool relu, bool training, bool need_dx, const OptT &dx_add, at::Tensor ws, const OptT &ol_kt_start,
     const OptT &ol_entries, const OptT &pl_tile_start, const OptT &pl_entries, int64_t ev0, int64_t ev1, int64_t ev2,
-    int64_t ev3, int64_t defer_floats, bool defer_launch)
+    int64_t ev3, int64_t defer_floats, bool defer_launch, int64_t precision)
 {
     TORCH_CHECK(x.is_cuda() && x.is_contiguous() && dy.is_contiguous(), "x / dy: contiguous device tensors");
     const bool has_bn = scale.has_value() && scale->defined();
@@ -79,7 +80,7 @@ std::tuple<OptT, OptT, at::Tensor, OptT, int64_t, py::bytes> conv_layer_backward
     alignas(16) unsigned char launch[128];
     reinterpret_cast<int *>(launch)[4] = 0;
     if (defer_floats > 0) slabs = at::empty({defer_floats}, x.options());
-    check(ms3d_spconv_layer_backward(
+    check(ms3d_spconv_layer_backward_p(
               x.data_ptr<float>(), dy.data_ptr<float>(), wf_buf.data_ptr<float>(), nbr_fwd.data_ptr<int>(),
               nbr_bwd.data_ptr<int>(), (int)vin, (int)vout, (int)K, (int)cin, (int)cout, fptr(scale), fptr(shift), fptr(mean),
               fptr(invstd), (has_bn && relu) ? 1 : 0, (has_bn && training) ? 1 : 0, need_dx ? 1 : 0,
@@ -87,8 +88,9 @@ std::tuple<OptT, OptT, at::Tensor, OptT, int64_t, py::bytes> conv_layer_backward
               dgb.has_value() ? dgb->data_ptr<float>() : nullptr, dW.data_ptr<float>(), (float *)ws.data_ptr(), iptr(ol_kt_start),
               iptr(ol_entries), iptr(pl_tile_start), iptr(pl_entries), (void *)ev0, (void *)ev1, (void *)ev2, (void *)ev3,
               nullptr, nullptr, 0, slabs.has_value() ? slabs->data_ptr<float>() : nullptr,
-              slabs.has_value() ? &nblk : nullptr, (slabs.has_value() && defer_launch) ? (void *)launch : nullptr, cur()),
-          "ms3d_spconv_layer_backward");
+              slabs.has_value() ? &nblk : nullptr, (slabs.has_value() && defer_launch) ? (void *)launch : nullptr,
+              (int)precision, cur()),
+          "ms3d_spconv_layer_backward_p");
     if (!need_dx) dx = c10::nullopt;
     const bool described = reinterpret_cast<int *>(launch)[4] != 0;
     return {dx, dgb, dW, slabs, (int64_t)nblk, py::bytes(reinterpret_cast<const char *>(launch), described ? 128 : 0)};
@@ -119,7 +121,8 @@ at::Tensor bn_finalize(const at::Tensor &partial, int64_t V, double eps, double 
 std::tuple<at::Tensor, at::Tensor, OptT, at::Tensor, at::Tensor> res_block_forward(
     const at::Tensor &x, const at::Tensor &stats_in, at::Tensor wf1, at::Tensor wf2, const at::Tensor &nbr, int64_t V, int64_t C,
     const OptT &pl_tile_start, const OptT &pl_entries, int64_t nparts, bool want_stats, const OptT &g0, const OptT &b0,
-    OptT rm0, OptT rv0, double eps0, double mom0, const OptT &g1, const OptT &b1, OptT rm1, OptT rv1, double eps1, double mom1)
+    OptT rm0, OptT rv0, double eps0, double mom0, const OptT &g1, const OptT &b1, OptT rm1, OptT rv1, double eps1, double mom1,
+    int64_t precision)
 {
     TORCH_CHECK(x.is_cuda() && x.is_contiguous() && x.scalar_type() == at::kFloat && x.size(1) == C, "x: contiguous f32 [V, C]");
     TORCH_CHECK(stats_in.dim() == 3 && stats_in.size(2) == C && stats_in.is_contiguous(), "stats_in: [nparts, 2, C]");
@@ -130,20 +133,21 @@ std::tuple<at::Tensor, at::Tensor, OptT, at::Tensor, at::Tensor> res_block_forwa
     check(ms3d_bn_finalize(stats_in.data_ptr<float>(), (int)stats_in.size(0), (long)V, (int)C, (float)eps0, (float)mom0, fptr(g0),
                            fptr(b0), rs(rm0), rs(rv0), o0, o0 + C, o0 + 2 * C, o0 + 3 * C, st), "ms3d_bn_finalize");
     at::Tensor y1 = at::empty({V, C}, x.options()), st1 = at::empty({nparts, 2, C}, x.options());
-    check(ms3d_spconv_layer_forward(x.data_ptr<float>(), nullptr, nbr.data_ptr<int>(), (int)V, 27, (int)C, (int)C, 1, o0 + 2 * C,
-                                    o0 + 3 * C, 1, nullptr, nullptr, wf1.data_ptr<float>(), y1.data_ptr<float>(),
-                                    st1.data_ptr<float>(), iptr(pl_tile_start), iptr(pl_entries), nullptr, nullptr, st),
-          "ms3d_spconv_layer_forward");
+    check(ms3d_spconv_layer_forward_p(x.data_ptr<float>(), nullptr, nbr.data_ptr<int>(), (int)V, 27, (int)C, (int)C, 1, o0 + 2 * C,
+                                      o0 + 3 * C, 1, nullptr, nullptr, wf1.data_ptr<float>(), y1.data_ptr<float>(),
+                                      st1.data_ptr<float>(), iptr(pl_tile_start), iptr(pl_entries), nullptr, nullptr,
+                                      (int)precision, st),
+          "ms3d_spconv_layer_forward_p");
     check(ms3d_bn_finalize(st1.data_ptr<float>(), (int)nparts, (long)V, (int)C, (float)eps1, (float)mom1, fptr(g1), fptr(b1),
                            rs(rm1), rs(rv1), o1, o1 + C, o1 + 2 * C, o1 + 3 * C, st), "ms3d_bn_finalize");
     at::Tensor y2 = at::empty({V, C}, x.options());
     OptT st2;
     if (want_stats) st2 = at::empty({nparts, 2, C}, x.options());
-    check(ms3d_spconv_layer_forward(y1.data_ptr<float>(), nullptr, nbr.data_ptr<int>(), (int)V, 27, (int)C, (int)C, 1, o1 + 2 * C,
-                                    o1 + 3 * C, 1, x.data_ptr<float>(), nullptr, wf2.data_ptr<float>(), y2.data_ptr<float>(),
-                                    st2.has_value() ? st2->data_ptr<float>() : nullptr, iptr(pl_tile_start), iptr(pl_entries),
-                                    nullptr, nullptr, st),
-          "ms3d_spconv_layer_forward");
+    check(ms3d_spconv_layer_forward_p(y1.data_ptr<float>(), nullptr, nbr.data_ptr<int>(), (int)V, 27, (int)C, (int)C, 1, o1 + 2 * C,
+                                      o1 + 3 * C, 1, x.data_ptr<float>(), nullptr, wf2.data_ptr<float>(), y2.data_ptr<float>(),
+                                      st2.has_value() ? st2->data_ptr<float>() : nullptr, iptr(pl_tile_start), iptr(pl_entries),
+                                      nullptr, nullptr, (int)precision, st),
+          "ms3d_spconv_layer_forward_p");
     return {y1, y2, st2, bn0, bn1};
 }
 
@@ -160,9 +164,37 @@ at::Tensor gather_rows(const at::Tensor &x, const at::Tensor &idx)
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m)
 {
     m.doc() = "host-side fast path of the minsu3d_amd sparse-voxel engine (pybind over libminsu3d_hip.so's C ABI)";
+    // the three convolution calls take a trailing matmul precision (0 highest, 1 high, 2 medium); without it: 0
     m.def("conv_layer_forward", &conv_layer_forward);
+    m.def("conv_layer_forward",
+          [](const at::Tensor &x, const OptT &W, const at::Tensor &nbr_fwd, int64_t vout, int64_t K, int64_t cin, int64_t cout,
+             bool mirror_bwd, const OptT &pre_scale, const OptT &pre_shift, bool pre_relu, const OptT &residual,
+             const OptT &bias, at::Tensor wf_buf, int64_t nparts, const OptT &pl_tile_start, const OptT &pl_entries,
+             int64_t ev_start, int64_t ev_stop) {
+              return conv_layer_forward(x, W, nbr_fwd, vout, K, cin, cout, mirror_bwd, pre_scale, pre_shift, pre_relu, residual,
+                                        bias, wf_buf, nparts, pl_tile_start, pl_entries, ev_start, ev_stop, 0);
+          });
     m.def("conv_layer_backward", &conv_layer_backward);
+    m.def("conv_layer_backward",
+          [](const at::Tensor &x, const at::Tensor &dy, const at::Tensor &wf_buf, const at::Tensor &nbr_fwd,
+             const at::Tensor &nbr_bwd, int64_t vin, int64_t vout, int64_t K, int64_t cin, int64_t cout, const OptT &scale,
+             const OptT &shift, const OptT &mean, const OptT &invstd, bool relu, bool training, bool need_dx,
+             const OptT &dx_add, at::Tensor ws, const OptT &ol_kt_start, const OptT &ol_entries, const OptT &pl_tile_start,
+             const OptT &pl_entries, int64_t ev0, int64_t ev1, int64_t ev2, int64_t ev3, int64_t defer_floats,
+             bool defer_launch) {
+              return conv_layer_backward(x, dy, wf_buf, nbr_fwd, nbr_bwd, vin, vout, K, cin, cout, scale, shift, mean, invstd,
+                                         relu, training, need_dx, dx_add, ws, ol_kt_start, ol_entries, pl_tile_start,
+                                         pl_entries, ev0, ev1, ev2, ev3, defer_floats, defer_launch, 0);
+          });
     m.def("bn_finalize", &bn_finalize);
     m.def("gather_rows", &gather_rows);
     m.def("res_block_forward", &res_block_forward);
+    m.def("res_block_forward",
+          [](const at::Tensor &x, const at::Tensor &stats_in, at::Tensor wf1, at::Tensor wf2, const at::Tensor &nbr, int64_t V,
+             int64_t C, const OptT &pl_tile_start, const OptT &pl_entries, int64_t nparts, bool want_stats, const OptT &g0,
+             const OptT &b0, OptT rm0, OptT rv0, double eps0, double mom0, const OptT &g1, const OptT &b1, OptT rm1, OptT rv1,
+             double eps1, double mom1) {
+              return res_block_forward(x, stats_in, wf1, wf2, nbr, V, C, pl_tile_start, pl_entries, nparts, want_stats, g0, b0,
+                                       rm0, rv0, eps0, mom0, g1, b1, rm1, rv1, eps1, mom1, 0);
+          });
 }

@@ -84,12 +84,15 @@ class GeneralModel(nn.Module):
 
     def __call__(self, *args, **kwargs):
         # every convolution weight of the model (backbone, score / refinement nets) is laid out for the kernels in ONE
-        # launch here; the window closes when the forward returns (weights may change afterwards)
-        ME.prepare_conv_weights(self)
-        try:
-            return super().__call__(*args, **kwargs)
-        finally:
-            ME.release_conv_weights()
+        # launch here; the window closes when the forward returns (weights may change afterwards).  The matmul precision
+        # switch (torch.set_float32_matmul_precision) is read once here and governs the whole pass and its backward.
+        prec = ME.functional.conv_precision()
+        with ME.functional.pass_precision(prec):
+            ME.prepare_conv_weights(self, precision=prec)
+            try:
+                return super().__call__(*args, **kwargs)
+            finally:
+                ME.release_conv_weights()
 
     def forward(self, data_dict):
         out = self.backbone(data_dict["voxel_features"], data_dict["voxel_xyz"], data_dict["voxel_point_map"])
