@@ -190,6 +190,30 @@ int ms3d_downsample(const int *coords, int V, int tensor_stride, int *out_coords
 int ms3d_kmap_k2(const int *parent, const int *koff, int Vf, int Vc, int *nbr_down, int *nbr_up,
                  ms3d_stream_t stream);
 
+/* General kernel map (any kernel size, stride and dilation): nbr[k][o] = row of in_coords at (batch of o, xyz of o +
+ * offsets[k]), or -1.  offsets: DEVICE int[K][3] in voxel units (not multiples of the kernel index: the caller folds
+ * dilation and tensor stride in).  A row of in_coords that occurs twice is named by its first occurrence.  A shifted
+ * coordinate outside the packable range [-16384, 16384) gives -1.  1 <= K <= 65535; workspace:
+ * ms3d_coord_workspace_bytes(Vin).  For a strided layer out_coords is what ms3d_downsample produced. */
+int ms3d_kmap_general(const int *in_coords, int Vin, const int *out_coords, int Vout, const int *offsets, int K, int *nbr,
+                      void *workspace, size_t workspace_bytes, ms3d_stream_t stream);
+/* Inverse table nbr_inv[K][Vin]: nbr_inv[k][i] = o where nbr[k][o] == i, else -1 -- what ms3d_kmap_k2 returns as nbr_up for
+ * its one geometry.  Needs distinct output coordinates (then an input row feeds at most one output row per offset and the
+ * scatter is collision free: plain stores).  Backward-data of a strided convolution, pooling backward and transposed
+ * convolutions onto a cached coordinate set walk it. */
+int ms3d_kmap_invert(const int *nbr, int K, int Vout, int Vin, int *nbr_inv, ms3d_stream_t stream);
+
+/* ---- pooling over a kernel map (float32, any C; 16-byte row accesses when C % 4 == 0).  mode: 0 max, 1 average, 2 sum.
+ * forward: out[o] = reduce over the PRESENT inputs in[nbr[k][o]] in ascending k; max writes arg [Vout][C] = the winning k
+ * (lowest k on ties; 255 and out = 0 for a row without input), average divides by the number of present inputs and writes
+ * it to count [Vout].  arg / count may be NULL for the modes that do not use them.  K <= 254.
+ * backward: a gather through the inverse table, din[i] = sum_k [o = nbr_inv[k][i] >= 0] dout[o] * (max: arg[o][c] == k |
+ * average: 1 / count[o] | sum: 1).  No atomics: both directions are bit-reproducible. */
+int ms3d_pool_forward(int mode, const float *in, const int *nbr, int Vout, int K, int C, float *out, unsigned char *arg,
+                      int *count, ms3d_stream_t stream);
+int ms3d_pool_backward(int mode, const float *dout, const int *nbr_inv, int Vin, int K, int C, const unsigned char *arg,
+                       const int *count, float *din, ms3d_stream_t stream);
+
 /* Pair list = tile-compacted form of an offset-major table, built once per table and shared by every convolution of
  * the level (forward, backward-data, backward-weight).  Output rows are cut into tiles of 64; per tile and offset the
  * valid (input row, output row) pairs are stored contiguously, padded to a multiple of 16 ("batch" = one MFMA group).
@@ -380,6 +404,28 @@ int ms3d_spconv_layer_backward_p(const float *x, const float *dy, const float *w
                                  void *ev_wg_stop, float *ws_wgrad, ms3d_stream_t wgrad_stream, int join,
                                  float *wgrad_slabs, int *wgrad_deferred_nblk, void *wgrad_deferred_launch, int precision,
                                  ms3d_stream_t stream);
+/* Tables of ANY geometry (ms3d_kmap_general / ms3d_kmap_invert: other kernel sizes, strided and dilated layers, their
+ * transposes).  The forward / backward-data entry points read their input through the table only and serve every table
+ * (K > 27 and small levels of K > 36 take the general table walk; no pair list or offset list exists for K > 27).  The
+ * backward-weight side has one route that takes the input row set for the output row set (three-piece bf16 operands of the
+ * wide K = 27 layers): the *_g forms are told Vin and whether the table is a SUBMANIFOLD map (same coordinate set on both
+ * sides, row for row) and keep every other table off it.  submanifold != 0 with Vin != Vout is MS3D_E_UNSUPPORTED.  The
+ * entry points without the flag take a K = 27 table for a submanifold map, as they always did
+ * (ms3d_spconv_layer_backward_p: when also Vin == Vout).  The workspace sizes of the forms without the flag bound these. */
+int ms3d_spconv_wgrad_is_bf16x3_g(int Vout, int K, int Cin, int Cout, int offset_list, int submanifold);
+int ms3d_spconv_backward_weight_g(const float *in, const float *dout, const int *nbr, int Vin, int Vout, int K, int Cin,
+                                  int Cout, float *dW, const float *pre_scale, const float *pre_shift, int pre_relu,
+                                  float *partial_ws, const int *ol_kt_start, const int *ol_entries, int submanifold,
+                                  int precision, ms3d_stream_t stream);
+int ms3d_spconv_layer_backward_g(const float *x, const float *dy, const float *wf_buf, const int *nbr_fwd,
+                                 const int *nbr_bwd, int Vin, int Vout, int K, int Cin, int Cout, const float *scale,
+                                 const float *shift, const float *mean, const float *invstd, int pre_relu, int training,
+                                 int need_dx, float *dx, const float *dx_add, float *dgb, float *dW, float *ws,
+                                 const int *ol_fwd_kt_start, const int *ol_fwd_entries, const int *pl_bwd_tile_start,
+                                 const int *pl_bwd_entries, void *ev_start, void *ev_stop, void *ev_wg_start,
+                                 void *ev_wg_stop, float *ws_wgrad, ms3d_stream_t wgrad_stream, int join,
+                                 float *wgrad_slabs, int *wgrad_deferred_nblk, void *wgrad_deferred_launch, int precision,
+                                 int submanifold, ms3d_stream_t stream);
 /* Deferred backward-weight launches of MANY layers of one variant as one launch: descs = DEVICE array of the 128-byte
  * descriptions, each with its first int set to the layer's first block (blocks are numbered layer after layer, a layer
  * has int[1] * int[2] * int[3] of them), total_blocks = their sum.  x, dy, the tables and the slab areas the descriptions

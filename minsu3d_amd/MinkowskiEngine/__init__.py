@@ -1,14 +1,26 @@
 """The MinkowskiEngine subset the reference models import (`import MinkowskiEngine as ME`), served by the
-gfx950 sparse-voxel engine.  Exactly the 9 symbols the reference uses:
+gfx950 sparse-voxel engine.  The 9 symbols the reference uses:
 
     SparseTensor, MinkowskiConvolution, MinkowskiConvolutionTranspose, MinkowskiBatchNorm, MinkowskiReLU,
     cat, utils.sparse_quantize, utils.sparse_collate  (+ tensor attributes .features/.F, .coordinates/.C)
+
+and what other networks written against that API use: convolutions of any kernel size and dilation at stride 1 or 2
+with an optional bias, and
+
+    MinkowskiMaxPooling, MinkowskiAvgPooling, MinkowskiSumPooling, MinkowskiGlobalMaxPooling,
+    MinkowskiGlobalAvgPooling, MinkowskiGlobalSumPooling, MinkowskiLinear, MinkowskiDropout
+
+Not supported (each raises NotImplementedError naming it): strides other than 1 and 2, transposed convolutions or
+pooling that create coordinates, dimension != 3, per-axis kernel tuples.
 
 Module/parameter names match ME so reference state_dicts keep their keys (`kernel`, `bn.weight`, ...).
 """
 from . import utils  # noqa: F401
 from .tensor import SparseTensor, CoordinateManager, cat, prefetch_coordinates  # noqa: F401
 from .modules import (MinkowskiConvolution, MinkowskiConvolutionTranspose, MinkowskiBatchNorm,  # noqa: F401
-                      MinkowskiReLU, prepare_conv_weights, release_conv_weights)
+                      MinkowskiReLU, prepare_conv_weights, release_conv_weights,
+                      MinkowskiMaxPooling, MinkowskiAvgPooling, MinkowskiSumPooling, MinkowskiGlobalMaxPooling,
+                      MinkowskiGlobalAvgPooling, MinkowskiGlobalSumPooling, MinkowskiLinear, MinkowskiDropout)
+from .tensor import kernel_offsets  # noqa: F401  (engine extra: the offset list of a kernel, in weight order)
 from .functional import gather_rows  # noqa: F401  (engine extra: x[idx] with a scatter-add backward)
 from .functional import SkipLink  # noqa: F401  (engine extra: a residual block's skip gradient, see functional.py)

@@ -69,11 +69,20 @@ def _ready(W, tok, code):
 
 class ConvSpec:
     """non-tensor launch description shared by forward and backward"""
-    __slots__ = ("nbr_fwd", "nbr_bwd", "vin", "vout", "K", "cin", "cout", "mirror")
+    __slots__ = ("nbr_fwd", "nbr_bwd", "vin", "vout", "K", "cin", "cout", "mirror", "sub")
 
-    def __init__(self, nbr_fwd, nbr_bwd, vin, vout, K, cin, cout, mirror):
+    def __init__(self, nbr_fwd, nbr_bwd, vin, vout, K, cin, cout, mirror, sub=None):
         self.nbr_fwd, self.nbr_bwd, self.vin, self.vout = nbr_fwd, nbr_bwd, vin, vout
         self.K, self.cin, self.cout, self.mirror = K, cin, cout, mirror
+        # sub: None for the three geometries of the reference's models (the library's own rule: a 27-offset table is a
+        # submanifold map); True / False for a table of CoordinateManager.kernel_map -- said to the backward-weight call,
+        # whose wide K = 27 route takes the input rows for the output rows
+        self.sub = sub
+
+
+def _sk(spec):
+    """keyword argument of the backend's backward calls that says the table's kind (absent for the old geometries)"""
+    return {} if spec.sub is None else {"submanifold": spec.sub}
 
 
 class SkipLink:
@@ -131,7 +140,7 @@ class SparseConvFn(torch.autograd.Function):
     (non-differentiable side output that lets the next BatchNorm skip its statistics pass)"""
 
     @staticmethod
-    def forward(ctx, x, W, gamma, beta, residual, spec, bn, want_stats, skip=None):
+    def forward(ctx, x, W, gamma, beta, residual, spec, bn, want_stats, skip=None, bias=None):
         be = get_backend()
         pre = (bn["scale"], bn["shift"]) if bn is not None else None
         prec = ctx.prec = conv_precision(be)
@@ -140,11 +149,12 @@ class SparseConvFn(torch.autograd.Function):
         ready = _ready(W, getattr(be, "weight_token", None), prec)
         y, stats, wf_buf = be.conv_layer_forward(x, W.view(spec.K, spec.cin, spec.cout), spec.nbr_fwd, spec.vout, spec.K,
                                                  spec.cin, spec.cout, spec.mirror, pre, bool(bn and bn["relu"]), residual,
-                                                 None, want_stats, **({"wf_ready": ready} if ready is not None else {}),
+                                                 None if bias is None else bias.reshape(-1), want_stats, **({"wf_ready": ready} if ready is not None else {}),
                                                  **_pk(prec))
         if stats is None:
             stats = x.new_zeros(0)
         ctx.spec, ctx.bn, ctx.wf_buf, ctx.has_res = spec, bn, wf_buf, residual is not None
+        ctx.bias_shape = None if bias is None else tuple(bias.shape)
         # (deferred slab reduction: the queue of this kernel's group, stamped by prepare_conv_weights for this forward)
         ctx.defer = _defer_of(W, getattr(be, "weight_token", None))
         ctx.w_direct = W.is_leaf or ctx.defer is not None    # nobody computes on dW before the parameter / the flush node
@@ -177,7 +187,7 @@ class SparseConvFn(torch.autograd.Function):
             dz, dgb = be.bn_bwd_reduce(da, x, bn["scale"], bn["shift"], bn["mean"], bn["invstd"], False)
             dx = (be.bn_bwd_apply(dz, x, bn["scale"], bn["mean"], bn["invstd"], dgb) if bn["training"] else dz * bn["scale"])
             dW = be.conv_backward_weight(x, dy, spec.nbr_fwd, spec.vout, spec.K, spec.cin, spec.cout,
-                                         pre=(bn["scale"], bn["shift"]), pre_relu=False, **_pk(ctx.prec))
+                                         pre=(bn["scale"], bn["shift"]), pre_relu=False, **_pk(ctx.prec), **_sk(spec))
         else:
             fused = add is not None and ctx.needs_input_grad[0] and be.fuses_dx_add(bn)
             extra = {"dx_add": add} if fused else {}
@@ -190,7 +200,7 @@ class SparseConvFn(torch.autograd.Function):
                 extra["join_now"] = True
             dx, dgb, dW = be.conv_layer_backward(x, dy, ctx.wf_buf, spec.nbr_fwd, spec.nbr_bwd, spec.vin, spec.vout,
                                                  spec.K, spec.cin, spec.cout, bn, ctx.needs_input_grad[0], **extra,
-                                                 **_pk(ctx.prec))
+                                                 **_pk(ctx.prec), **_sk(spec))
             if fused:
                 add = None
         if add is not None and dx is not None:
@@ -200,7 +210,11 @@ class SparseConvFn(torch.autograd.Function):
         d_res = dy if ctx.has_res else None
         if role == "tail" and ctx.has_res:
             link.grad, d_res = dy, None      # the head adds it to its dx
-        return dx, dW.view_as(W), dgamma, dbeta, d_res, None, None, None, None
+        db = None
+        if ctx.bias_shape is not None and ctx.needs_input_grad[9]:
+            # the bias is added to every output row: its gradient is the column sum of dy
+            db = (be.column_sum(dy) if (hasattr(be, "column_sum") and dy.is_cuda) else dy.sum(0)).view(ctx.bias_shape)
+        return dx, dW.view_as(W), dgamma, dbeta, d_res, None, None, None, None, db
 
 
 class ResBlockFn(torch.autograd.Function):
@@ -363,7 +377,7 @@ class BnReluConvFn(torch.autograd.Function):
         x, W = ctx.saved_tensors
         e = {"defer": _queue(ctx.defer)} if _queue(ctx.defer) is not None else {}
         dx, dgb, dW = be.conv_layer_backward(x, dy.contiguous(), ctx.wf, spec.nbr_fwd, spec.nbr_bwd, spec.vin, spec.vout, spec.K,
-                                             spec.cin, spec.cout, ctx.bn, ctx.needs_input_grad[0], **e, **_pk(ctx.prec))
+                                             spec.cin, spec.cout, ctx.bn, ctx.needs_input_grad[0], **e, **_pk(ctx.prec), **_sk(spec))
         return dx, dW.view_as(W), dgb[1], dgb[0], None, None, None, None
 
 
@@ -390,16 +404,17 @@ def bn_act(x, pending):
     return BNActFn.apply(x, pending["gamma"], pending["beta"], pending)
 
 
-def conv(x, W, spec, pending, residual=None, want_stats=False, skip=None):
-    """-> (features, stats or None).  skip: ("head" | "tail", SkipLink) of a residual block, see SkipLink"""
+def conv(x, W, spec, pending, residual=None, want_stats=False, skip=None, bias=None):
+    """-> (features, stats or None).  skip: ("head" | "tail", SkipLink) of a residual block, see SkipLink.
+    bias [1, cout] or None: added in the kernel epilogue"""
     if pending is not None and pending.get("gamma") is None:
         x, pending = torch.relu(x), None
         if skip is not None and skip[0] == "head":
             skip = None       # x is no longer the skipped tensor itself: leave that block to autograd
     if pending is None:
-        y, st = SparseConvFn.apply(x, W, None, None, residual, spec, None, want_stats, skip)
+        y, st = SparseConvFn.apply(x, W, None, None, residual, spec, None, want_stats, skip, bias)
     else:
-        y, st = SparseConvFn.apply(x, W, pending["gamma"], pending["beta"], residual, spec, pending, want_stats, skip)
+        y, st = SparseConvFn.apply(x, W, pending["gamma"], pending["beta"], residual, spec, pending, want_stats, skip, bias)
     return y, (st if want_stats else None)
 
 
@@ -503,3 +518,26 @@ def gather_rows(x, idx, max_dup=None):
     if x.dim() == 2 and idx.dim() == 1 and idx.dtype == torch.int64 and x.requires_grad:
         return GatherRowsFn.apply(x, idx, max_dup)
     return _rows(x, idx) if x.dim() == 2 and idx.dim() == 1 else x[idx]
+
+
+class SparsePoolFn(torch.autograd.Function):
+    """y = pool(x) over a kernel map: mode 0 max, 1 average (over the PRESENT inputs of a row), 2 sum.  Forward walks the
+    forward table, backward gathers through its inverse (csrc/pool.hip): no atomics in either direction."""
+
+    @staticmethod
+    def forward(ctx, x, nbr_fwd, nbr_inv, vin, vout, K, mode):
+        be = get_backend()
+        if not hasattr(be, "pool_forward"):
+            raise NotImplementedError("sparse pooling needs the HIP backend (ms3d_pool_forward)")
+        y, arg, count = be.pool_forward(mode, x, nbr_fwd, vout, K)
+        ctx.geom = (nbr_inv, vin, K, mode, arg, count)
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        nbr_inv, vin, K, mode, arg, count = ctx.geom
+        return get_backend().pool_backward(mode, dy.contiguous(), nbr_inv, vin, K, arg, count), None, None, None, None, None, None
+
+
+def sparse_pool(x, nbr_fwd, nbr_inv, vin, vout, K, mode):
+    return SparsePoolFn.apply(x, nbr_fwd, nbr_inv, vin, vout, K, mode)

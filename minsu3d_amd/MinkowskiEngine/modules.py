@@ -1,6 +1,13 @@
 """nn.Module surface of the MinkowskiEngine subset (same constructor arguments, parameter names and init as ME
-v0.5.4): `kernel` of shape (K, in, out) -- (in, out) for kernel_size 1 -- no bias,
-uniform(-1/sqrt(in*K), +1/sqrt(in*K)); MinkowskiBatchNorm wraps `self.bn = nn.BatchNorm1d`."""
+v0.5.4): `kernel` of shape (K, in, out) -- (in, out) for kernel_size 1 -- and, when asked for,
+`bias` of shape (1, out), both uniform(-1/sqrt(in*K), +1/sqrt(in*K)); MinkowskiBatchNorm wraps `self.bn =
+nn.BatchNorm1d`.
+
+Convolutions take any integer kernel size and dilation with stride 1 (odd sizes) or 2; pooling layers walk the same
+kernel maps.  What MinkowskiEngine does for the geometries beyond the reference's three -- the offset order of even
+kernels, average pooling dividing by the number of inputs PRESENT, the bias shape -- is written down from memory of
+its v0.5 sources: MinkowskiEngine is not installed where this package is developed (as SURVEY Appendix A says of the
+conventions it recalls), so these are this engine's definitions, checked against dense torch operators."""
 import math
 import os
 
@@ -9,22 +16,37 @@ import torch.nn as nn
 
 from ..backend import get_backend
 from . import functional as Fn
-from .tensor import SparseTensor
+from .tensor import SparseTensor, check_geometry
 
 
 class _ConvBase(nn.Module):
     def __init__(self, in_channels, out_channels, kernel_size=-1, stride=1, dilation=1, bias=False, dimension=3):
         super().__init__()
-        assert dimension == 3 and dilation == 1 and not bias, "only what the reference uses is implemented"
+        if dimension != 3:
+            raise NotImplementedError(f"dimension={dimension}: only 3-D sparse tensors are supported")
+        check_geometry(kernel_size, stride, dilation)
         self.in_channels, self.out_channels = in_channels, out_channels
-        self.kernel_size, self.stride = kernel_size, stride
+        self.kernel_size, self.stride, self.dilation = kernel_size, stride, dilation
         K = kernel_size ** 3
         self.kernel_volume = K
         shape = (in_channels, out_channels) if (kernel_size == 1 and stride == 1) else (K, in_channels, out_channels)
         self.kernel = nn.Parameter(torch.empty(shape, dtype=torch.float32))
         s = 1.0 / math.sqrt(in_channels * K)
+        # ME's name and shape, so that state_dict keys carry over; same uniform bound as the kernel
+        self.bias = nn.Parameter(torch.empty((1, out_channels), dtype=torch.float32)) if bias else None
         with torch.no_grad():
             self.kernel.uniform_(-s, s)
+            if bias:
+                self.bias.uniform_(-s, s)
+
+    def _spec(self, cm, ts):
+        """-> (ConvSpec of the forward convolution from tensor stride ts, output tensor stride)"""
+        cin, cout = self.in_channels, self.out_channels
+        nbr_fwd, nbr_bwd, vin, vout, K, out_ts, mirror = cm.kernel_map(ts, self.kernel_size, self.stride, self.dilation)
+        # the three maps of the reference's models keep the library's own rule for what a table is (sub = None); the
+        # general ones say whether they map a coordinate set onto itself
+        old = (self.kernel_size, self.stride, self.dilation) in ((3, 1, 1), (2, 2, 1)) or K == 1
+        return Fn.ConvSpec(nbr_fwd, nbr_bwd, vin, vout, K, cin, cout, mirror, None if old else mirror), out_ts
 
     def _kernel(self):
         """the kernel this forward uses: the parameter, or -- inside a prepare_conv_weights window in training -- its
@@ -35,7 +57,8 @@ class _ConvBase(nn.Module):
         return self.kernel
 
     def extra_repr(self):
-        return f"in={self.in_channels}, out={self.out_channels}, kernel_size={self.kernel_size}, stride={self.stride}"
+        return (f"in={self.in_channels}, out={self.out_channels}, kernel_size={self.kernel_size}, stride={self.stride}, "
+                f"dilation={self.dilation}, bias={self.bias is not None}")
 
 
 def _flush_group(name):
@@ -86,7 +109,7 @@ def prepare_conv_weights(root, precision=None):
             if buf is None or buf.device != m.kernel.device:
                 buf = m.__dict__["_wf_buf"] = torch.empty(be.wf_floats(K, cin, cout), dtype=torch.float32, device=m.kernel.device)
             # same orientation rule as the forward() of the module: 3x3x3 maps mirror their offsets in backward-data
-            layers.append((m.kernel, buf, K, cin, cout, m.kernel_size == 3 and m.stride == 1, m, grp))
+            layers.append((m.kernel, buf, K, cin, cout, m.kernel_size % 2 == 1 and m.kernel_size > 1 and m.stride == 1, m, grp))
     prec = Fn.conv_precision(be) if precision is None else precision
     be.prep_weights_multi([l[:6] for l in layers], **Fn._pk(prec))
     token = be.weight_token
@@ -117,7 +140,10 @@ def release_conv_weights():
 
 
 class MinkowskiConvolution(_ConvBase):
-    """k3 s1 (submanifold, output coords = input coords), k2 s2 (downsample) and k1 s1"""
+    """Any kernel size and dilation at stride 1 (odd sizes: submanifold, output coords = input coords) or stride 2 (output on
+    the stride-2 coordinate set, whatever the kernel size).  k3 s1, k2 s2 and k1 s1 -- the reference's layers -- run on the
+    tables, pair lists and fused blocks tuned for them; every other geometry walks its table with the general kernels,
+    untuned.  Strides other than 1 and 2, even kernels at stride 1 and per-axis tuples raise NotImplementedError."""
 
     def forward(self, x: SparseTensor, residual: SparseTensor = None, skip=None):
         """`residual` (same coordinate map as the output) is added in the kernel epilogue -- used by ResidualBlock
@@ -125,22 +151,24 @@ class MinkowskiConvolution(_ConvBase):
         gradient through the block's first convolution instead of an elementwise add.  Neither is part of ME's API."""
         cm, ts = x.coordinate_manager, x.tensor_stride
         cin, cout = self.in_channels, self.out_channels
-        if self.kernel_size == 3 and self.stride == 1:
+        ks, stride = self.kernel_size, self.stride
+        # (the three layers of the reference's models first, as they always were: a model step makes this call ~100 times)
+        if ks == 3 and stride == 1 and self.dilation == 1:
             nbr = cm.k3(ts)
             V = cm.size(ts)
             spec = Fn.ConvSpec(nbr, nbr, V, V, 27, cin, cout, True)
             out_ts = ts
-        elif self.kernel_size == 2 and self.stride == 2:
+        elif ks == 2 and stride == 2 and self.dilation == 1:
             down, up = cm.k2(ts)
             spec = Fn.ConvSpec(down, up, cm.size(ts), cm.size(2 * ts), 8, cin, cout, False)
             out_ts = 2 * ts
-        elif self.kernel_size == 1 and self.stride == 1:
+        elif ks == 1 and stride == 1:
             ident = cm.identity(ts)
             V = cm.size(ts)
             spec = Fn.ConvSpec(ident, ident, V, V, 1, cin, cout, False)
             out_ts = ts
         else:
-            raise NotImplementedError((self.kernel_size, self.stride))
+            spec, out_ts = self._spec(cm, ts)
         feats, kernel, pending = x._F, self._kernel(), x._pending
         if cin % 16 != 0 and cin < 16 and self.kernel_volume > 1 and pending is None and spec.vout >= 30000:
             # the network's input convolution (6 channels) at full resolution: zero-padding rows and weights to one
@@ -149,24 +177,31 @@ class MinkowskiConvolution(_ConvBase):
             pad = 16 - cin
             feats = torch.nn.functional.pad(feats, (0, pad))
             kernel = torch.nn.functional.pad(kernel, (0, 0, 0, pad))
-            spec = Fn.ConvSpec(spec.nbr_fwd, spec.nbr_bwd, spec.vin, spec.vout, spec.K, 16, cout, spec.mirror)
+            spec = Fn.ConvSpec(spec.nbr_fwd, spec.nbr_bwd, spec.vin, spec.vout, spec.K, 16, cout, spec.mirror, spec.sub)
         if skip is not None and feats is not x._F:
             skip = None            # (padded input rows: not the skipped tensor any more)
         y, stats = Fn.conv(feats, kernel, spec, pending,
-                           residual=None if residual is None else residual._raw(), want_stats=self.training, skip=skip)
+                           residual=None if residual is None else residual._raw(), want_stats=self.training, skip=skip,
+                           bias=self.bias)
         return x._like(y, tensor_stride=out_ts, stats=stats)
 
 
 class MinkowskiConvolutionTranspose(_ConvBase):
-    """k2 s2 transposed: output lives on the cached coordinate set of stride ts/2 (the encoder's)"""
+    """stride-2 transposed convolution of any kernel size: the output lives on the cached coordinate set of stride ts/2
+    (the encoder's) and the table is the inverse of the matching strided map.  A transposed convolution that would have to
+    CREATE coordinates (stride 1, or an input that was never downsampled from a finer set) is not supported."""
 
     def forward(self, x: SparseTensor):
         cm, ts = x.coordinate_manager, x.tensor_stride
-        assert self.kernel_size == 2 and self.stride == 2 and ts % 2 == 0
+        if self.stride != 2 or ts % 2 != 0 or (ts // 2) not in cm.coords:
+            raise NotImplementedError(f"MinkowskiConvolutionTranspose(kernel_size={self.kernel_size}, stride={self.stride}) on "
+                                      f"tensor stride {ts}: only stride 2 onto a cached finer coordinate set; generating "
+                                      "new coordinates is not supported")
         fine = ts // 2
-        down, up = cm.k2(fine)  # cached by the encoder's strided convolution
-        spec = Fn.ConvSpec(up, down, cm.size(ts), cm.size(fine), 8, self.in_channels, self.out_channels, False)
-        y, stats = Fn.conv(x._F, self._kernel(), spec, x._pending, want_stats=self.training)
+        fwd, _ = self._spec(cm, fine)      # the strided map fine -> ts (cached by the encoder's strided convolution)
+        spec = Fn.ConvSpec(fwd.nbr_bwd, fwd.nbr_fwd, fwd.vout, fwd.vin, fwd.K, self.in_channels, self.out_channels, False,
+                           fwd.sub)
+        y, stats = Fn.conv(x._F, self._kernel(), spec, x._pending, want_stats=self.training, bias=self.bias)
         return x._like(y, tensor_stride=fine, stats=stats)
 
 
@@ -242,3 +277,102 @@ class MinkowskiReLU(nn.Module):
             p["relu"] = True
             return x._like(x._F, pending=p)
         return x._like(torch.relu(x._raw()))
+
+
+class _PoolBase(nn.Module):
+    """pooling over the kernel map of (kernel_size, stride, dilation): same geometries as the convolutions (stride 1 with an
+    odd kernel: output coords = input coords; stride 2: the stride-2 coordinate set).  A pending BatchNorm / ReLU in front
+    is materialised first."""
+    MODE = None
+
+    def __init__(self, kernel_size, stride=1, dilation=1, dimension=3):
+        super().__init__()
+        if dimension != 3:
+            raise NotImplementedError(f"dimension={dimension}: only 3-D sparse tensors are supported")
+        check_geometry(kernel_size, stride, dilation)
+        self.kernel_size, self.stride, self.dilation = kernel_size, stride, dilation
+
+    def forward(self, x: SparseTensor):
+        cm, ts = x.coordinate_manager, x.tensor_stride
+        nbr_fwd, _, vin, vout, K, out_ts, _ = cm.kernel_map(ts, self.kernel_size, self.stride, self.dilation)
+        nbr_inv = cm.kernel_map_inverse(ts, self.kernel_size, self.stride, self.dilation)
+        y = Fn.sparse_pool(x._raw(), nbr_fwd, nbr_inv, vin, vout, K, self.MODE)
+        return x._like(y, tensor_stride=out_ts)
+
+    def extra_repr(self):
+        return f"kernel_size={self.kernel_size}, stride={self.stride}, dilation={self.dilation}"
+
+
+class MinkowskiMaxPooling(_PoolBase):
+    """max over the inputs present under the kernel (lowest offset index wins a tie)"""
+    MODE = 0
+
+
+class MinkowskiAvgPooling(_PoolBase):
+    """mean over the inputs PRESENT under the kernel -- not over the kernel volume (how MinkowskiEngine's average pooling is
+    recalled to behave; see the module docstring)"""
+    MODE = 1
+
+
+class MinkowskiSumPooling(_PoolBase):
+    MODE = 2
+
+
+class _GlobalPoolBase(nn.Module):
+    """one output row per batch index present, in ascending batch order.  The result is a plain tensor wrapper on its own
+    coordinate set (batch index, 0, 0, 0); rows are grouped by batch through a cached stable sort, not assumed contiguous."""
+    MODE = None
+
+    def forward(self, x: SparseTensor):
+        from ..common_ops.functions.common_ops import roipool
+        from ..common_ops.functions.softgroup_ops import global_avg_pool
+        cm, ts = x.coordinate_manager, x.tensor_stride
+        order, inv, offsets, counts = cm.batch_rows(ts)
+        rows = Fn.PermuteRowsFn.apply(x._raw(), order, inv)        # a permutation: the backward is the gather dy[inv]
+        if self.MODE == 0:
+            y = roipool(rows, offsets)
+        else:
+            y = global_avg_pool(rows, offsets)
+            if self.MODE == 2:
+                y = y * counts
+        b = cm.coords[ts][order[offsets[:-1].long()], 0]
+        coords = torch.zeros((b.numel(), 4), dtype=torch.int32, device=b.device)
+        coords[:, 0] = b
+        return SparseTensor(y, coordinates=coords)
+
+
+class MinkowskiGlobalMaxPooling(_GlobalPoolBase):
+    MODE = 0
+
+
+class MinkowskiGlobalAvgPooling(_GlobalPoolBase):
+    MODE = 1
+
+
+class MinkowskiGlobalSumPooling(_GlobalPoolBase):
+    MODE = 2
+
+
+class MinkowskiLinear(nn.Module):
+    """nn.Linear on the rows of .F (`linear.weight`, `linear.bias` as in ME)"""
+
+    def __init__(self, in_features, out_features, bias=True):
+        super().__init__()
+        self.linear = nn.Linear(in_features, out_features, bias=bias)
+
+    def forward(self, x: SparseTensor):
+        feats = x._raw()
+        if feats.is_cuda and feats.dtype == torch.float32:
+            y = Fn.dense_linear(feats, self.linear.weight, self.linear.bias)
+        else:
+            y = self.linear(feats)
+        return x._like(y)
+
+
+class MinkowskiDropout(nn.Module):
+    def __init__(self, p=0.5, inplace=False):
+        super().__init__()
+        self.dropout = nn.Dropout(p)
+
+    def forward(self, x: SparseTensor):
+        return x._like(self.dropout(x._raw()))

@@ -10,10 +10,36 @@ activations.  Touching `.features` of such a tensor materialises it (one element
 """
 import os
 
+import numpy as np
 import torch
 
 from ..backend import get_backend
 from . import functional as Fn
+
+
+def kernel_offsets(kernel_size, dilation=1, tensor_stride=1):
+    """int32 [kernel_size^3, 3] (x, y, z) offsets of a kernel in voxel units, in the order the weights are indexed:
+    k = ix + ks * iy + ks^2 * iz (x fastest).  Odd sizes are centred, (i - (ks - 1) / 2) * dilation * tensor_stride (the
+    3x3x3 table's order); even sizes reach forward from the output coordinate, i * dilation * tensor_stride (the in-cell
+    offsets of the k2 s2 table)."""
+    ks = int(kernel_size)
+    i = np.arange(ks) - ((ks - 1) // 2 if ks % 2 else 0)
+    iz, iy, ix = np.meshgrid(i, i, i, indexing="ij")
+    return (np.stack([ix, iy, iz], -1).reshape(-1, 3) * (int(dilation) * int(tensor_stride))).astype(np.int32)
+
+
+def check_geometry(kernel_size, stride, dilation):
+    """the (kernel size, stride, dilation) triples the engine builds kernel maps for; anything else raises
+    NotImplementedError naming the geometry (at construction of a layer and again in kernel_map)"""
+    geom = f"kernel_size={kernel_size}, stride={stride}, dilation={dilation}"
+    if not all(isinstance(v, int) for v in (kernel_size, stride, dilation)) or kernel_size < 1 or dilation < 1:
+        raise NotImplementedError(f"{geom}: one positive integer per argument (no per-axis tuples)")
+    if stride not in (1, 2):
+        raise NotImplementedError(f"{geom}: strides other than 1 and 2 are not supported")
+    if stride == 1 and kernel_size % 2 == 0:
+        raise NotImplementedError(f"{geom}: an even kernel size needs stride 2 (MinkowskiEngine refuses it as well)")
+    if kernel_size ** 3 > 254:
+        raise NotImplementedError(f"{geom}: at most 254 kernel offsets (kernel_size <= 6)")
 
 
 class CoordinateManager:
@@ -38,6 +64,76 @@ class CoordinateManager:
         self._k3 = {}
         self._k2 = {}       # fine stride -> (nbr_down [8,Vc], nbr_up [8,Vf])
         self._ident = {}
+        self._kmaps = {}    # (ts, kernel_size, stride, dilation) -> kernel_map() tuple of the general geometries
+        self._kinv = {}     # the same key -> inverse table (pooling backward over a submanifold map)
+        self._batch_rows = {}
+
+    def kernel_map(self, ts, kernel_size, stride=1, dilation=1):
+        """-> (nbr_fwd [K, Vout], nbr_bwd [K, Vin], Vin, Vout, K, output tensor stride, mirror) for a layer from the
+        coordinate set of tensor stride ts; built once per key.  (3, 1, 1), (2, 2, 1) and (1, 1, *) are the tables of
+        k3() / k2() / identity().  Stride 1 (odd kernel sizes only): the output set is the input set, the table is its own
+        transpose up to k <-> K-1-k (nbr_bwd = nbr_fwd, mirror = True).  Stride 2: the output set is the stride-2 set of
+        k2() whatever the kernel size, nbr_bwd is the inverse table, mirror = False.  Other strides: NotImplementedError.
+        Offsets: kernel_offsets()."""
+        kernel_size, stride, dilation = int(kernel_size), int(stride), int(dilation)
+        if kernel_size == 1 and stride == 1:
+            ident, V = self.identity(ts), self.size(ts)
+            return ident, ident, V, V, 1, ts, False
+        if (kernel_size, stride, dilation) == (3, 1, 1):
+            nbr, V = self.k3(ts), self.size(ts)
+            return nbr, nbr, V, V, 27, ts, True
+        if (kernel_size, stride, dilation) == (2, 2, 1):
+            down, up = self.k2(ts)
+            return down, up, self.size(ts), self.size(2 * ts), 8, 2 * ts, False
+        key = (ts, kernel_size, stride, dilation)
+        km = self._kmaps.get(key)
+        if km is None:
+            check_geometry(kernel_size, stride, dilation)
+            be = get_backend()
+            if not hasattr(be, "kmap_general"):
+                raise NotImplementedError(f"kernel_size={kernel_size}, stride={stride}, dilation={dilation}: this backend "
+                                          "builds the 3x3x3, 2x2x2 stride-2 and 1x1x1 maps only")
+            offsets = torch.from_numpy(kernel_offsets(kernel_size, dilation, ts))
+            K, vin = offsets.size(0), self.size(ts)
+            if stride == 1:
+                nbr = be.kmap_general(self.coords[ts], self.coords[ts], offsets)
+                km = (nbr, nbr, vin, vin, K, ts, True)
+            else:
+                self.k2(ts)                    # makes the stride-2 coordinate set (every strided layer lands on it)
+                out = self.coords[2 * ts]
+                vout = out.size(0)
+                nbr = be.kmap_general(self.coords[ts], out, offsets)
+                km = (nbr, be.kmap_invert(nbr, K, vout, vin), vin, vout, K, 2 * ts, False)
+            self._kmaps[key] = km
+        return km
+
+    def kernel_map_inverse(self, ts, kernel_size, stride=1, dilation=1):
+        """[K, Vin] table that names, per offset, the OUTPUT row an input row feeds (what a backward gather of a pooling
+        layer walks): nbr_bwd of a strided map; for a submanifold map -- whose nbr_bwd is the forward table, to be read
+        with mirrored offsets -- the inverse is built (and kept) here"""
+        nbr_fwd, nbr_bwd, vin, vout, K, _, mirror = self.kernel_map(ts, kernel_size, stride, dilation)
+        if not mirror and nbr_bwd is not nbr_fwd:
+            return nbr_bwd
+        key = (ts, int(kernel_size), int(stride), int(dilation))
+        if key not in self._kinv:
+            self._kinv[key] = get_backend().kmap_invert(nbr_fwd.contiguous(), K, vout, vin)
+        return self._kinv[key]
+
+    def batch_rows(self, ts):
+        """rows of the coordinate set grouped by batch index -> (order int64 [V]: rows sorted by batch, stable; its inverse
+        permutation; offsets int32 [B + 1] into `order`, one segment per batch index PRESENT, ascending; counts float32
+        [B, 1]).  Rows are batch-contiguous already only for some inputs, so nothing relies on it; one host sync, once."""
+        br = self._batch_rows.get(ts)
+        if br is None:
+            b = self.coords[ts][:, 0].long()
+            sb, order = torch.sort(b, stable=True)
+            inv = torch.empty_like(order)
+            inv[order] = torch.arange(order.numel(), device=order.device)
+            _, counts = torch.unique_consecutive(sb, return_counts=True)
+            offsets = torch.zeros(counts.numel() + 1, dtype=torch.int32, device=b.device)
+            offsets[1:] = torch.cumsum(counts, 0)
+            br = self._batch_rows[ts] = (order, inv, offsets, counts.to(torch.float32).view(-1, 1))
+        return br
 
     def k3(self, ts):
         if ts not in self._k3:

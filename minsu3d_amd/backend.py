@@ -578,6 +578,9 @@ _FAST_ARGTYPES = {
     "ms3d_spconv_layer_forward_p": [_VP] * 3 + [_I] * 5 + [_VP] * 2 + [_I] + [_VP] * 5 + [_VP] * 2 + [_VP] * 2 + [_I, _VP],
     "ms3d_spconv_layer_backward_p": [_VP] * 5 + [_I] * 5 + [_VP] * 4 + [_I] * 3 + [_VP] * 5 + [_VP] * 4 + [_VP] * 4 +
                                     [_VP, _VP, _I, _VP, _VP, _VP, _I, _VP],
+    # the same with the table's kind (submanifold: 1 / 0) behind the precision
+    "ms3d_spconv_layer_backward_g": [_VP] * 5 + [_I] * 5 + [_VP] * 4 + [_I] * 3 + [_VP] * 5 + [_VP] * 4 + [_VP] * 4 +
+                                    [_VP, _VP, _I, _VP, _VP, _VP, _I, _I, _VP],
     "ms3d_bn_finalize": [_VP, _I, C.c_long, _I, C.c_float, C.c_float] + [_VP] * 4 + [_VP] * 4 + [_VP],
 }
 
@@ -844,6 +847,53 @@ class _HipEngine:
         _lib.check(self.lib.ms3d_kmap_k2(_lib.ptr(parent), _lib.ptr(koff), vf, int(vc), _lib.ptr(down), _lib.ptr(up),
                                          _lib.stream_handle()), "ms3d_kmap_k2")
         return down, up
+
+    def kmap_general(self, in_coords, out_coords, offsets):
+        """nbr [K, Vout] of an arbitrary offset list: nbr[k][o] = row of in_coords at out_coords[o] + offsets[k] (same batch
+        index) or -1.  offsets: int32 [K, 3] in voxel units (host or device tensor)."""
+        in_coords, out_coords = self._dev(in_coords), self._dev(out_coords)
+        vin, vout, dev = in_coords.size(0), out_coords.size(0), in_coords.device
+        offsets = offsets.to(device=dev, dtype=torch.int32).contiguous()
+        K = offsets.size(0)
+        assert offsets.dim() == 2 and offsets.size(1) == 3 and K >= 1
+        nbr = torch.empty((K, max(vout, 1)), dtype=torch.int32, device=dev)
+        ws = self._cws(vin, dev)
+        _lib.check(self.lib.ms3d_kmap_general(_lib.ptr(in_coords), vin, _lib.ptr(out_coords), vout, _lib.ptr(offsets), K,
+                                              _lib.ptr(nbr), _lib.ptr(ws), C.c_size_t(ws.numel()), _lib.stream_handle()),
+                   "ms3d_kmap_general")
+        return nbr
+
+    def kmap_invert(self, nbr, K, vout, vin):
+        """inverse table [K, Vin] of nbr [K, Vout]: inv[k][i] = o where nbr[k][o] == i, else -1"""
+        assert nbr.dtype == torch.int32 and nbr.is_contiguous() and nbr.size(0) == K and nbr.size(1) == max(vout, 1)
+        inv = torch.empty((K, max(vin, 1)), dtype=torch.int32, device=nbr.device)
+        if vin <= 0:
+            inv.fill_(-1)
+        _lib.check(self.lib.ms3d_kmap_invert(_lib.ptr(nbr), int(K), int(vout), int(vin), _lib.ptr(inv), _lib.stream_handle()),
+                   "ms3d_kmap_invert")
+        return inv
+
+    # ---- pooling over a kernel map (mode: 0 max, 1 average, 2 sum)
+    def pool_forward(self, mode, x, nbr, vout, K):
+        """-> (out [vout, C], arg uint8 [vout, C] for max else None, count int32 [vout] for average else None)"""
+        x = self._dev(x).contiguous()
+        assert x.dtype == torch.float32 and x.dim() == 2
+        c, dev = x.size(1), x.device
+        out = torch.empty((vout, c), dtype=torch.float32, device=dev)
+        arg = torch.empty((vout, c), dtype=torch.uint8, device=dev) if mode == 0 else None
+        count = torch.empty(vout, dtype=torch.int32, device=dev) if mode == 1 else None
+        _lib.check(self.lib.ms3d_pool_forward(int(mode), _lib.ptr(x), _lib.ptr(nbr), int(vout), int(K), int(c), _lib.ptr(out),
+                                              _lib.ptr(arg), _lib.ptr(count), _lib.stream_handle()), "ms3d_pool_forward")
+        return out, arg, count
+
+    def pool_backward(self, mode, dout, nbr_inv, vin, K, arg, count):
+        dout = self._dev(dout).contiguous()
+        c = dout.size(1)
+        din = torch.empty((vin, c), dtype=torch.float32, device=dout.device)
+        _lib.check(self.lib.ms3d_pool_backward(int(mode), _lib.ptr(dout), _lib.ptr(nbr_inv), int(vin), int(K), int(c),
+                                               _lib.ptr(arg), _lib.ptr(count), _lib.ptr(din), _lib.stream_handle()),
+                   "ms3d_pool_backward")
+        return din
 
     # ---- convolution
     def prep_weights(self, W, K, cin_e, cout_e, transpose=False, mirror=False):
@@ -1159,13 +1209,15 @@ class _HipEngine:
         return y1, y2, st2, o0.unbind(0), o1.unbind(0)
 
     def conv_layer_backward(self, x, dy, wf_buf, nbr_fwd, nbr_bwd, vin, vout, K, cin, cout, bn, need_dx, dx_add=None,
-                            defer=None, join_now=False, precision=0):
+                            defer=None, join_now=False, precision=0, submanifold=None):
         """-> (dx or None, dgb [2,cin] = (dbeta, dgamma) or None, dW [K,cin,cout]).  dx_add [vin, cin]: a gradient that
         reaches x over a skip connection, added to dx inside the BatchNorm-backward pass / the residual epilogue (needs
         training-mode statistics when a BatchNorm is fused: `fuses_dx_add`).  defer: a WgradQueue -- dW is returned
         UNREDUCED and completed by the queue's flush.  join_now: with MS3D_WGRAD_STREAM=2, make the caller's stream wait
         for this layer's backward-weight (somebody consumes dW on it right after this call).  precision: the code the
-        forward call laid wf_buf out with."""
+        forward call laid wf_buf out with.  submanifold: True / False = the table maps one coordinate set onto itself, row
+        for row, or does not (the general geometries say it); None = a 27-offset table with vin == vout is taken for one."""
+        sub = -1 if submanifold is None else int(bool(submanifold))
         x = self._dev(x); dy = self._dev(dy)
         dev = x.device
         ws = self.ws.get("layer", 4 * self._geom("ms3d_spconv_layer_ws_floats", vin, vout, K, cin, cout), dev)
@@ -1190,13 +1242,13 @@ class _HipEngine:
             ev2 = ev3 = None
         if self.ext is not None and mode == 0:
             evs = [(e.value or 0) if e is not None else 0 for e in (ev0, ev1, ev2, ev3)]
-            dx, dgb, dW, slabs, nblk, desc = self.ext.conv_layer_backward(
+            dx, dgb, dW, slabs, nblk, desc = (self.ext.conv_layer_backward_g if sub >= 0 else self.ext.conv_layer_backward)(
                 x, dy, wf_buf, nbr_fwd, nbr_bwd, vin, vout, K, cin, cout,
                 bn["scale"] if has_bn else None, bn["shift"] if has_bn else None, bn["mean"] if has_bn else None,
                 bn["invstd"] if has_bn else None, bool(has_bn and bn["relu"]), bool(has_bn and bn["training"]), bool(need_dx),
                 _f32(dx_add) if (dx_add is not None and need_dx) else None, ws, plf[0], plf[1], plb[0], plb[1], *evs,
                 self._geom("ms3d_spconv_wgrad_ws_floats", vout, K, cin, cout) if defer is not None else 0, batch,
-                int(precision))
+                int(precision), *((sub,) if sub >= 0 else ()))
             if desc:
                 defer.add_launch(desc, (x, dy, nbr_fwd, bn, slabs, dW), timing)
             if nblk > 0:
@@ -1222,7 +1274,7 @@ class _HipEngine:
             slabs = torch.empty(self._geom("ms3d_spconv_wgrad_ws_floats", vout, K, cin, cout), dtype=torch.float32, device=dev)
             n_defer = self._defer_n_addr
         launch = (C.c_char * 128)() if (batch and slabs is not None) else None
-        _lib.check(self._fast("ms3d_spconv_layer_backward_p")(
+        _lib.check(self._fast("ms3d_spconv_layer_backward_g")(
             _p(x), _p(dy), _p(wf_buf), _p(nbr_fwd), _p(nbr_bwd), int(vin), int(vout), int(K),
             int(cin), int(cout), _p(bn["scale"] if has_bn else None), _p(bn["shift"] if has_bn else None),
             _p(bn["mean"] if has_bn else None), _p(bn["invstd"] if has_bn else None),
@@ -1230,8 +1282,9 @@ class _HipEngine:
             _p(_f32(dx_add) if (dx_add is not None and need_dx) else None), _p(dgb), _p(dW), _p(ws), _p(plf[0]), _p(plf[1]), _p(plb[0]),
             _p(plb[1]), ev0, ev1, ev2, ev3, _p(ws2), side.cuda_stream if side is not None else None,
             int(mode == 1 or (mode == 2 and join_now) or (mode == 3 and defer is None)), _p(slabs), n_defer,
-            C.addressof(launch) if launch is not None else None, int(precision), _lib.stream_handle()),
-            "ms3d_spconv_layer_backward_p")
+            C.addressof(launch) if launch is not None else None, int(precision),
+            sub if sub >= 0 else int(K == 27 and vin == vout), _lib.stream_handle()),
+            "ms3d_spconv_layer_backward_g")
         if launch is not None and np.frombuffer(launch, dtype=np.int32, count=6)[4] != 0:
             defer.add_launch(bytes(launch), (x, dy, nbr_fwd, bn, slabs, dW), timing)
         if slabs is not None and self._defer_n.value > 0:
@@ -1284,13 +1337,21 @@ class _HipEngine:
         except RuntimeError:            # not inside a backward pass (a direct call): join now
             join()
 
-    def conv_backward_weight(self, x, dout, nbr, vout, K, cin, cout, pre=None, pre_relu=False, precision=0):
+    def conv_backward_weight(self, x, dout, nbr, vout, K, cin, cout, pre=None, pre_relu=False, precision=0, submanifold=None):
+        """submanifold: None = a 27-offset table is a submanifold map (x has vout rows); True / False: said by the caller
+        (the general geometries), x may then have any number of rows"""
         x = self._dev(x); dout = self._dev(dout)
         dW = torch.empty((K, cin, cout), dtype=torch.float32, device=x.device)
         ps, pb = (pre if pre is not None else (None, None))
         self.lib.ms3d_spconv_wgrad_ws_floats.restype = C.c_size_t
         ws = self.ws.get("wgrad", 4 * self.lib.ms3d_spconv_wgrad_ws_floats(int(vout), int(K), int(cin), int(cout)), x.device)
         ol = self.offsetlist(nbr, K, vout)
+        if submanifold is not None:
+            _lib.check(self.lib.ms3d_spconv_backward_weight_g(
+                _lib.ptr(x), _lib.ptr(dout), _lib.ptr(nbr), int(x.size(0)), int(vout), int(K), int(cin), int(cout), _lib.ptr(dW),
+                _lib.ptr(_f32(ps)), _lib.ptr(_f32(pb)), int(bool(pre_relu)), _lib.ptr(ws), _lib.ptr(ol[0]), _lib.ptr(ol[1]),
+                int(bool(submanifold)), int(precision), _lib.stream_handle()), "ms3d_spconv_backward_weight_g")
+            return dW
         _lib.check(self.lib.ms3d_spconv_backward_weight_p(
             _lib.ptr(x), _lib.ptr(dout), _lib.ptr(nbr), int(vout), int(K), int(cin), int(cout), _lib.ptr(dW),
             _lib.ptr(_f32(ps)), _lib.ptr(_f32(pb)), int(bool(pre_relu)), _lib.ptr(ws), _lib.ptr(ol[0]), _lib.ptr(ol[1]),

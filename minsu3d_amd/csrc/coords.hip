@@ -10,6 +10,8 @@
 //     16 output rows a wave owns read 64 contiguous bytes per offset:
 //       k3 s1 : nbr[k][i] = row at c_i + o_k*ts            (k = ix + 3*iy + 9*iz, x fastest)
 //       k2 s2 : down[k][p] = child of coarse row p at offset k;  up[k][f] = (k == koff[f]) ? parent[f] : -1
+//       general: nbr[k][o] = row at c_o + offsets[k] for any offset list (any kernel size, stride, dilation), and the
+//               inverse table nbr_inv[k][i] = o of a map that is not its own mirror image
 #include <mutex>
 #include <unordered_map>
 #include "common.h"
@@ -158,6 +160,35 @@ __global__ void fill_minus1_kernel(int *p, long n)
 {
     const long t = (long)blockIdx.x * blockDim.x + threadIdx.x;
     if (t < n) p[t] = -1;
+}
+// General kernel map: one thread per (offset, output row), nbr[k][o] = input row at (batch of o, xyz of o + offsets[k]) or
+// -1; consecutive threads -> consecutive rows of one offset (coalesced stores, as kmap_k3_kernel).  A shifted coordinate
+// that leaves the packable range has no key of its own (pack_key would wrap it onto another voxel): -1 without a probe.
+__global__ void kmap_general_kernel(const int *__restrict__ out_coords, int Vout, const int *__restrict__ offsets, int K,
+                                    const unsigned long long *__restrict__ keys, const int *__restrict__ vals, unsigned mask,
+                                    int *__restrict__ nbr)
+{
+    const int o = blockIdx.x * blockDim.x + threadIdx.x;
+    const int k = blockIdx.y;
+    if (o >= Vout || k >= K) return;
+    const int4 c = reinterpret_cast<const int4 *>(out_coords)[o];
+    int r = -1;
+    if (in_range(c.y) && in_range(c.z) && in_range(c.w) && c.x >= 0 && c.x <= 0x7FFFF) {
+        const int x = c.y + offsets[3 * k], y = c.z + offsets[3 * k + 1], z = c.w + offsets[3 * k + 2];
+        if (in_range(x) && in_range(y) && in_range(z)) r = table_lookup(keys, vals, mask, pack_key(c.x, x, y, z));
+    }
+    nbr[(size_t)k * Vout + o] = r;
+}
+
+// nbr_inv[k][nbr[k][o]] = o: for one offset an input row feeds at most one output row (distinct output coordinates), so
+// the stores of one launch never meet; entries that name no row of [0, Vin) are skipped
+__global__ void kmap_invert_kernel(const int *__restrict__ nbr, int Vout, int Vin, int *__restrict__ nbr_inv)
+{
+    const int o = blockIdx.x * blockDim.x + threadIdx.x;
+    const int k = blockIdx.y;
+    if (o >= Vout) return;
+    const int i = nbr[(size_t)k * Vout + o];
+    if (i >= 0 && i < Vin) nbr_inv[(size_t)k * Vin + i] = o;
 }
 __global__ void kmap_k2_kernel(const int *__restrict__ parent, const int *__restrict__ koff, int Vf, int Vc,
                                int *__restrict__ nbr_down, int *__restrict__ nbr_up)
@@ -510,6 +541,41 @@ int ms3d_kmap_k2(const int *parent, const int *koff, int Vf, int Vc, int *nbr_do
     fill_minus1_kernel<<<ms3d_divup((long)Vf * 8, 256), 256, 0, stream>>>(nbr_up, (long)Vf * 8);
     MS3D_LAUNCH_CHECK();
     kmap_k2_kernel<<<ms3d_divup(Vf, 256), 256, 0, stream>>>(parent, koff, Vf, Vc, nbr_down, nbr_up);
+    MS3D_LAUNCH_CHECK();
+    return 0;
+}
+
+int ms3d_kmap_general(const int *in_coords, int Vin, const int *out_coords, int Vout, const int *offsets, int K, int *nbr,
+                      void *workspace, size_t workspace_bytes, ms3d_stream_t stream_)
+{
+    hipStream_t stream = (hipStream_t)stream_;
+    if (K < 1 || K > 65535) return MS3D_E_UNSUPPORTED;
+    if (Vout <= 0) return 0;
+    if (Vin <= 0) {
+        fill_minus1_kernel<<<ms3d_divup((long)Vout * K, 256), 256, 0, stream>>>(nbr, (long)Vout * K);
+        MS3D_LAUNCH_CHECK();
+        return 0;
+    }
+    CoordWs w;
+    if (carve(w, Vin, workspace) > workspace_bytes) return MS3D_E_WORKSPACE;
+    int rc = build_table(w, in_coords, Vin, 1, stream);
+    if (rc) return rc;
+    dim3 grid(ms3d_divup(Vout, 256), K);
+    kmap_general_kernel<<<grid, 256, 0, stream>>>(out_coords, Vout, offsets, K, w.keys, w.vals, (unsigned)w.H - 1u, nbr);
+    MS3D_LAUNCH_CHECK();
+    return 0;
+}
+
+int ms3d_kmap_invert(const int *nbr, int K, int Vout, int Vin, int *nbr_inv, ms3d_stream_t stream_)
+{
+    hipStream_t stream = (hipStream_t)stream_;
+    if (K < 1 || K > 65535) return MS3D_E_UNSUPPORTED;
+    if (Vin <= 0) return 0;
+    fill_minus1_kernel<<<ms3d_divup((long)Vin * K, 256), 256, 0, stream>>>(nbr_inv, (long)Vin * K);
+    MS3D_LAUNCH_CHECK();
+    if (Vout <= 0) return 0;
+    dim3 grid(ms3d_divup(Vout, 256), K);
+    kmap_invert_kernel<<<grid, 256, 0, stream>>>(nbr, Vout, Vin, nbr_inv);
     MS3D_LAUNCH_CHECK();
     return 0;
 }

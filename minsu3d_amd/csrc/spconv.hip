@@ -3591,7 +3591,9 @@ FwdGeom fwd_geometry(int Vout, int K, int Cin, int Cout, bool with_bn_partial, i
         return e ? atoi(e) : SMALL_TILES;
     }();
     if (ws_geometry(Vout, K, Cin, Cout, g)) return g;
-    if (ntiles <= small_tiles && (size_t)NCH * NBtot >= 4) {
+    // (ks <= 4 offset groups is all a small-level workgroup holds: K <= 36.  Larger kernels -- 4x4x4, 5x5x5 -- walk the
+    // table with the general kernel below at every level size.)
+    if (ntiles <= small_tiles && (size_t)NCH * NBtot >= 4 && ms3d_divup(K, OG) <= 4) {
         // one block per (tile, column slice); waves = offset groups; enough column splits for ~1024+ waves
         const int ks = ms3d_divup(K, OG);
         int ny = ms3d_divup(NBtot, MAX_NBT);
@@ -3982,8 +3984,10 @@ static bool wgrad_list_cols_ok(int K, int nb)
     return nb <= 4 || (k8 && K == 8 && nb <= 14);
 }
 
-static bool wgrad_bf3_ok(int Vout, int K, int Cin, int Cout, bool use_list)
+static bool wgrad_bf3_ok(int Vout, int K, int Cin, int Cout, bool use_list, bool submanifold = true)
 {
+    // the operand pass splits Vout rows of `in`: only a table whose input row set IS its output row set may come here
+    if (!submanifold) return false;
     // below ~30 M row x channel x channel products the operand pass and the coarser row chunks cost more than the shorter
     // MFMA sequence saves (measured: 80 ch @ 2.5k rows and 48 ch @ 11.7k rows lose, 128 @ 2.5k and 64 @ 11.7k win)
     if ((double)Vout * Cin * Cout < 30e6) return false;
@@ -3997,6 +4001,10 @@ static bool wgrad_bf3_ok(int Vout, int K, int Cin, int Cout, bool use_list)
            Cout % 16 == 0;
 }
 int ms3d_spconv_wgrad_is_bf16x3(int Vout, int K, int Cin, int Cout, int offset_list) { return wgrad_bf3_ok(Vout, K, Cin, Cout, offset_list != 0) ? 1 : 0; }
+int ms3d_spconv_wgrad_is_bf16x3_g(int Vout, int K, int Cin, int Cout, int offset_list, int submanifold)
+{
+    return wgrad_bf3_ok(Vout, K, Cin, Cout, offset_list != 0, submanifold != 0) ? 1 : 0;
+}
 // 1 when a backward-weight call of this shape takes the f32 table walk -- the kernel ms3d_spconv_layer_backward can leave
 // to a batched launch (offset_list: an offset list of the table is passed)
 int ms3d_spconv_wgrad_is_table_walk(int Vout, int K, int Cin, int Cout, int offset_list)
@@ -4058,7 +4066,8 @@ int ms3d_spconv_wgrad_row_chunks(int Vout)
 static int spconv_backward_weight_impl(const float *in, const float *dout, const int *nbr, int Vout, int K, int Cin, int Cout,
                                        float *dW, const float *pre_scale, const float *pre_shift, int pre_relu,
                                        float *partial_ws, const int *ol_kt_start, const int *ol_entries, int *defer_nblk,
-                                       ms3d_stream_t stream_, void *defer_launch = nullptr, int precision = 0);
+                                       ms3d_stream_t stream_, void *defer_launch = nullptr, int precision = 0,
+                                       bool submanifold = true);
 
 int ms3d_spconv_backward_weight_p(const float *in, const float *dout, const int *nbr, int Vout, int K, int Cin, int Cout,
                                   float *dW, const float *pre_scale, const float *pre_shift, int pre_relu,
@@ -4068,6 +4077,19 @@ int ms3d_spconv_backward_weight_p(const float *in, const float *dout, const int 
     if (precision < 0 || precision > 2) return MS3D_E_UNSUPPORTED;
     return spconv_backward_weight_impl(in, dout, nbr, Vout, K, Cin, Cout, dW, pre_scale, pre_shift, pre_relu, partial_ws,
                                        ol_kt_start, ol_entries, nullptr, stream_, nullptr, precision);
+}
+
+// the same for a table of any geometry: submanifold = 0 keeps the call off every route that takes the input row set for the
+// output row set (the table walk and the offset-list kernel read `in` through the table only)
+int ms3d_spconv_backward_weight_g(const float *in, const float *dout, const int *nbr, int Vin, int Vout, int K, int Cin,
+                                  int Cout, float *dW, const float *pre_scale, const float *pre_shift, int pre_relu,
+                                  float *partial_ws, const int *ol_kt_start, const int *ol_entries, int submanifold,
+                                  int precision, ms3d_stream_t stream_)
+{
+    if (precision < 0 || precision > 2 || Vin < 0) return MS3D_E_UNSUPPORTED;
+    if (submanifold && Vin != Vout) return MS3D_E_UNSUPPORTED;
+    return spconv_backward_weight_impl(in, dout, nbr, Vout, K, Cin, Cout, dW, pre_scale, pre_shift, pre_relu, partial_ws,
+                                       ol_kt_start, ol_entries, nullptr, stream_, nullptr, precision, submanifold != 0);
 }
 
 int ms3d_spconv_backward_weight(const float *in, const float *dout, const int *nbr, int Vout, int K, int Cin, int Cout,
@@ -4081,7 +4103,7 @@ int ms3d_spconv_backward_weight(const float *in, const float *dout, const int *n
 static int spconv_backward_weight_impl(const float *in, const float *dout, const int *nbr, int Vout, int K, int Cin, int Cout,
                                        float *dW, const float *pre_scale, const float *pre_shift, int pre_relu,
                                        float *partial_ws, const int *ol_kt_start, const int *ol_entries, int *defer_nblk,
-                                       ms3d_stream_t stream_, void *defer_launch, int precision)
+                                       ms3d_stream_t stream_, void *defer_launch, int precision, bool submanifold)
 {
     hipStream_t stream = (hipStream_t)stream_;
     const long n = (long)K * Cin * Cout;
@@ -4128,7 +4150,7 @@ static int spconv_backward_weight_impl(const float *in, const float *dout, const
         p.rows_per_block = shift;  // the list kernel reads this field as the merge shift
         nblk = MS3D_PL_PARTS >> shift;
     } else {
-        if (!wgrad_bf3_ok(Vout, K, Cin, Cout, false)) {
+        if (!wgrad_bf3_ok(Vout, K, Cin, Cout, false, submanifold)) {
             // the f32 table walk: no more row chunks than fill the chip once (every chunk costs a slab of |dW|; measured:
             // 64 -> 96, K = 8, 50k rows 103 -> 86 us, 160 -> 160 at 2.5k rows 76 -> 69; everything else has fewer anyway)
             static const int rounds = [] { const char *e = getenv("MS3D_WGRAD_F32_ROUNDS"); return e ? atoi(e) : 1; }();
@@ -4164,7 +4186,7 @@ static int spconv_backward_weight_impl(const float *in, const float *dout, const
         MS3D_LAUNCH_CHECK();
         return 0;
     }
-    if (wgrad_bf3_ok(Vout, K, Cin, Cout, use_list)) {
+    if (wgrad_bf3_ok(Vout, K, Cin, Cout, use_list, submanifold)) {
         // wide submanifold layers: both operands pre-split into P = 3 (2, 1 at the lower precisions) bf16 pieces by two
         // elementwise passes
         const int P = 3 - precision;
@@ -4505,15 +4527,17 @@ static hipEvent_t order_event()
     return pool[dev][i];
 }
 
-int ms3d_spconv_layer_backward_p(const float *x, const float *dy, const float *wf_buf, const int *nbr_fwd,
+int ms3d_spconv_layer_backward_g(const float *x, const float *dy, const float *wf_buf, const int *nbr_fwd,
                                  const int *nbr_bwd, int Vin, int Vout, int K, int Cin, int Cout, const float *scale,
                                  const float *shift, const float *mean, const float *invstd, int pre_relu, int training,
                                  int need_dx, float *dx, const float *dx_add, float *dgb, float *dW, float *ws,
                                  const int *ol_fwd_kt_start, const int *ol_fwd_entries, const int *pl_bwd_tile_start,
                                  const int *pl_bwd_entries, void *ev_start, void *ev_stop, void *ev_wg_start, void *ev_wg_stop,
                                  float *ws_wgrad, ms3d_stream_t wgrad_stream, int join, float *wgrad_slabs,
-                                 int *wgrad_deferred_nblk, void *wgrad_deferred_launch, int precision, ms3d_stream_t stream)
+                                 int *wgrad_deferred_nblk, void *wgrad_deferred_launch, int precision, int submanifold,
+                                 ms3d_stream_t stream)
 {
+    if (submanifold && Vin != Vout) return MS3D_E_UNSUPPORTED;
     const size_t nwf = ms3d_spconv_wf_floats(K, Cin, Cout);
     const float *wft = wf_buf + 3 * nwf, *wfts = wf_buf + 4 * nwf;
     const int aux_kind = ms3d_spconv_aux_kind_p(K, Cin, Cout, precision);   // the kind layer_forward_p laid out
@@ -4533,7 +4557,8 @@ int ms3d_spconv_layer_backward_p(const float *x, const float *dy, const float *w
         int r = spconv_backward_weight_impl(x, dy, nbr_fwd, Vout, K, Cin, Cout, dW, scale, shift, pre_relu,
                                             wgrad_slabs ? wgrad_slabs : slabs, ol_fwd_kt_start, ol_fwd_entries,
                                             wgrad_slabs ? wgrad_deferred_nblk : nullptr, (ms3d_stream_t)side,
-                                            (wgrad_slabs && !ev_wg_start) ? wgrad_deferred_launch : nullptr, precision);
+                                            (wgrad_slabs && !ev_wg_start) ? wgrad_deferred_launch : nullptr, precision,
+                                            submanifold != 0);
         if (ev_wg_stop) MS3D_CHECK(hipEventRecord((hipEvent_t)ev_wg_stop, side));
         return r;
     };
@@ -4598,6 +4623,23 @@ int ms3d_spconv_layer_backward_p(const float *x, const float *dy, const float *w
     const int pb2 = ms3d_spconv_partial_blocks(Vin, K, Cout, Cin, ms3d_spconv_pairlist_rows_dense(Vin, K, Cout, Cin));
     slabs = ws + (size_t)(pb0 > pb1 ? (pb0 > pb2 ? pb0 : pb2) : (pb1 > pb2 ? pb1 : pb2)) * 2 * Cin;
     return run_wgrad();
+}
+
+// the form every caller had before the general geometries: a 27-offset table is taken for a submanifold map
+int ms3d_spconv_layer_backward_p(const float *x, const float *dy, const float *wf_buf, const int *nbr_fwd,
+                                 const int *nbr_bwd, int Vin, int Vout, int K, int Cin, int Cout, const float *scale,
+                                 const float *shift, const float *mean, const float *invstd, int pre_relu, int training,
+                                 int need_dx, float *dx, const float *dx_add, float *dgb, float *dW, float *ws,
+                                 const int *ol_fwd_kt_start, const int *ol_fwd_entries, const int *pl_bwd_tile_start,
+                                 const int *pl_bwd_entries, void *ev_start, void *ev_stop, void *ev_wg_start, void *ev_wg_stop,
+                                 float *ws_wgrad, ms3d_stream_t wgrad_stream, int join, float *wgrad_slabs,
+                                 int *wgrad_deferred_nblk, void *wgrad_deferred_launch, int precision, ms3d_stream_t stream)
+{
+    return ms3d_spconv_layer_backward_g(x, dy, wf_buf, nbr_fwd, nbr_bwd, Vin, Vout, K, Cin, Cout, scale, shift, mean, invstd,
+                                        pre_relu, training, need_dx, dx, dx_add, dgb, dW, ws, ol_fwd_kt_start, ol_fwd_entries,
+                                        pl_bwd_tile_start, pl_bwd_entries, ev_start, ev_stop, ev_wg_start, ev_wg_stop, ws_wgrad,
+                                        wgrad_stream, join, wgrad_slabs, wgrad_deferred_nblk, wgrad_deferred_launch, precision,
+                                        K == 27 && Vin == Vout, stream);
 }
 
 int ms3d_spconv_layer_backward(const float *x, const float *dy, const float *wf_buf, const int *nbr_fwd,

@@ -68,8 +68,11 @@ std::tuple<OptT, OptT, at::Tensor, OptT, int64_t, py::bytes> conv_layer_backward
     int64_t vin, int64_t vout, int64_t K, int64_t cin, int64_t cout, const OptT &scale, const OptT &shift, const OptT &mean,
     const OptT &invstd, bool relu, bool training, bool need_dx, const OptT &dx_add, at::Tensor ws, const OptT &ol_kt_start,
     const OptT &ol_entries, const OptT &pl_tile_start, const OptT &pl_entries, int64_t ev0, int64_t ev1, int64_t ev2,
-    int64_t ev3, int64_t defer_floats, bool defer_launch, int64_t precision)
+    int64_t ev3, int64_t defer_floats, bool defer_launch, int64_t precision, int64_t submanifold)
 {
+    // submanifold: 1 / 0 = the table maps a coordinate set onto itself or not (the *_g entry point); < 0 = not said: a
+    // 27-offset table with as many input as output rows is taken for one, as before the general geometries
+    if (submanifold < 0) submanifold = (K == 27 && vin == vout) ? 1 : 0;
     TORCH_CHECK(x.is_cuda() && x.is_contiguous() && dy.is_contiguous(), "x / dy: contiguous device tensors");
     const bool has_bn = scale.has_value() && scale->defined();
     OptT dx, dgb, slabs;
@@ -80,7 +83,7 @@ std::tuple<OptT, OptT, at::Tensor, OptT, int64_t, py::bytes> conv_layer_backward
     alignas(16) unsigned char launch[128];
     reinterpret_cast<int *>(launch)[4] = 0;
     if (defer_floats > 0) slabs = at::empty({defer_floats}, x.options());
-    check(ms3d_spconv_layer_backward_p(
+    check(ms3d_spconv_layer_backward_g(
               x.data_ptr<float>(), dy.data_ptr<float>(), wf_buf.data_ptr<float>(), nbr_fwd.data_ptr<int>(),
               nbr_bwd.data_ptr<int>(), (int)vin, (int)vout, (int)K, (int)cin, (int)cout, fptr(scale), fptr(shift), fptr(mean),
               fptr(invstd), (has_bn && relu) ? 1 : 0, (has_bn && training) ? 1 : 0, need_dx ? 1 : 0,
@@ -89,8 +92,8 @@ std::tuple<OptT, OptT, at::Tensor, OptT, int64_t, py::bytes> conv_layer_backward
               iptr(ol_entries), iptr(pl_tile_start), iptr(pl_entries), (void *)ev0, (void *)ev1, (void *)ev2, (void *)ev3,
               nullptr, nullptr, 0, slabs.has_value() ? slabs->data_ptr<float>() : nullptr,
               slabs.has_value() ? &nblk : nullptr, (slabs.has_value() && defer_launch) ? (void *)launch : nullptr,
-              (int)precision, cur()),
-          "ms3d_spconv_layer_backward_p");
+              (int)precision, (int)submanifold, cur()),
+          "ms3d_spconv_layer_backward_g");
     if (!need_dx) dx = c10::nullopt;
     const bool described = reinterpret_cast<int *>(launch)[4] != 0;
     return {dx, dgb, dW, slabs, (int64_t)nblk, py::bytes(reinterpret_cast<const char *>(launch), described ? 128 : 0)};
@@ -174,7 +177,19 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m)
               return conv_layer_forward(x, W, nbr_fwd, vout, K, cin, cout, mirror_bwd, pre_scale, pre_shift, pre_relu, residual,
                                         bias, wf_buf, nparts, pl_tile_start, pl_entries, ev_start, ev_stop, 0);
           });
-    m.def("conv_layer_backward", &conv_layer_backward);
+    // the same with the table's kind behind the precision (submanifold: 1 / 0; the forms below: a 27-offset table is one)
+    m.def("conv_layer_backward_g", &conv_layer_backward);
+    m.def("conv_layer_backward",
+          [](const at::Tensor &x, const at::Tensor &dy, const at::Tensor &wf_buf, const at::Tensor &nbr_fwd,
+             const at::Tensor &nbr_bwd, int64_t vin, int64_t vout, int64_t K, int64_t cin, int64_t cout, const OptT &scale,
+             const OptT &shift, const OptT &mean, const OptT &invstd, bool relu, bool training, bool need_dx,
+             const OptT &dx_add, at::Tensor ws, const OptT &ol_kt_start, const OptT &ol_entries, const OptT &pl_tile_start,
+             const OptT &pl_entries, int64_t ev0, int64_t ev1, int64_t ev2, int64_t ev3, int64_t defer_floats,
+             bool defer_launch, int64_t precision) {
+              return conv_layer_backward(x, dy, wf_buf, nbr_fwd, nbr_bwd, vin, vout, K, cin, cout, scale, shift, mean, invstd,
+                                         relu, training, need_dx, dx_add, ws, ol_kt_start, ol_entries, pl_tile_start,
+                                         pl_entries, ev0, ev1, ev2, ev3, defer_floats, defer_launch, precision, -1);
+          });
     m.def("conv_layer_backward",
           [](const at::Tensor &x, const at::Tensor &dy, const at::Tensor &wf_buf, const at::Tensor &nbr_fwd,
              const at::Tensor &nbr_bwd, int64_t vin, int64_t vout, int64_t K, int64_t cin, int64_t cout, const OptT &scale,
@@ -184,7 +199,7 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m)
              bool defer_launch) {
               return conv_layer_backward(x, dy, wf_buf, nbr_fwd, nbr_bwd, vin, vout, K, cin, cout, scale, shift, mean, invstd,
                                          relu, training, need_dx, dx_add, ws, ol_kt_start, ol_entries, pl_tile_start,
-                                         pl_entries, ev0, ev1, ev2, ev3, defer_floats, defer_launch, 0);
+                                         pl_entries, ev0, ev1, ev2, ev3, defer_floats, defer_launch, 0, -1);
           });
     m.def("bn_finalize", &bn_finalize);
     m.def("gather_rows", &gather_rows);

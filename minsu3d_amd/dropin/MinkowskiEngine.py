@@ -1,6 +1,7 @@
 """`import MinkowskiEngine as ME` for the reference's call sites (SparseTensor,
 MinkowskiConvolution, MinkowskiConvolutionTranspose, MinkowskiBatchNorm, MinkowskiReLU, cat,
-utils.sparse_quantize, utils.sparse_collate) -- an alias of minsu3d_amd.MinkowskiEngine."""
+utils.sparse_quantize, utils.sparse_collate) and the general convolution / pooling / linear layers beside them -- an
+alias of minsu3d_amd.MinkowskiEngine."""
 import sys
 
 import minsu3d_amd.MinkowskiEngine as _me
