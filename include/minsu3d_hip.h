@@ -135,6 +135,10 @@ int ms3d_global_avg_pool_bp_rows(int nProposal, int C, long n_rows, float *d_fea
  * ms3d_scatter_add_rows (`features[v2p_map]`, backbone.py:40; `feats[p2v]`, pointgroup.py:89) */
 int ms3d_gather_rows(const float *x, const long long *idx /* int64 */, long n, int C, float *out, ms3d_stream_t stream);
 
+/* dst[idx[i], :] = src[i, :] for an index that names no row twice (dst pre-zeroed by the caller): the backward of a row
+ * selection such as pruning -- one writer per row, plain stores, bit-reproducible */
+int ms3d_scatter_rows(const float *src, const long long *idx /* int64 */, long n, int C, float *dst, ms3d_stream_t stream);
+
 /* dst[idx[i], :] += src[i, :] (dst pre-zeroed by the caller): backward of the row gathers features[v2p_map],
  * feats[c_idxs], features[p2v_map] (reference backbone.py:40, general_model.py:156, pointgroup.py:88) */
 int ms3d_scatter_add_rows(const float *src, const long long *idx /* int64 */, long n, int C, float *dst,
@@ -202,6 +206,26 @@ int ms3d_kmap_general(const int *in_coords, int Vin, const int *out_coords, int 
  * scatter is collision free: plain stores).  Backward-data of a strided convolution, pooling backward and transposed
  * convolutions onto a cached coordinate set walk it. */
 int ms3d_kmap_invert(const int *nbr, int K, int Vout, int Vin, int *nbr_inv, ms3d_stream_t stream);
+
+/* ---- coordinate sets that are not derived by flooring: generation and pruning.
+ * ms3d_coords_expand: the set of distinct (batch of row i, xyz of row i + offsets[k]) over all input rows i and offsets k, in
+ * first-occurrence order of the candidate sequence c = i * K + k (input row major, offset minor) -- the rule
+ * ms3d_sparse_quantize and ms3d_downsample follow; deterministic, no sort.  Input rows may repeat.  offsets: DEVICE int[K][3]
+ * in voxel units.  Candidates are computed from (i, k) where they are needed; no [Vin * K, 4] array of them is written.
+ * out_coords: capacity Vin * K rows of (b, x, y, z); *n_out -> [host] (one sync).  A candidate (or an input row) outside the
+ * packable range [-16384, 16384) / batch index outside [0, 524288), or Vin * K > 2^31 - 1: MS3D_E_UNSUPPORTED (never dropped,
+ * never aliased; out_coords is then not to be used).  Vin == 0: *n_out = 0, nothing is launched.  workspace:
+ * ms3d_coords_expand_workspace_bytes(Vin, K) -- a table of the next power of two >= 2 Vin K slots of 12 bytes plus 8 bytes
+ * per candidate (0 when Vin * K is out of range). */
+size_t ms3d_coords_expand_workspace_bytes(int Vin, int K);
+int ms3d_coords_expand(const int *in_coords, int Vin, const int *offsets, int K, int *out_coords, int *n_out /*[host]*/,
+                       void *workspace, size_t workspace_bytes, ms3d_stream_t stream);
+/* ms3d_coords_prune: the rows of coords [V, 4] with keep[i] != 0, in their relative order (flag -> scan -> emit).
+ * src_row [n_kept] (capacity V): kept row -> source row, ascending; dst_row [V]: source row -> kept row or -1; out_coords
+ * capacity V rows; *n_kept -> [host] (one sync).  V == 0: nothing is launched.  workspace: ms3d_coord_workspace_bytes(V).
+ * The feature rows move with ms3d_gather_rows over src_row, their gradient with ms3d_scatter_rows. */
+int ms3d_coords_prune(const int *coords, int V, const unsigned char *keep, int *out_coords, int *src_row, int *dst_row,
+                      int *n_kept /*[host]*/, void *workspace, size_t workspace_bytes, ms3d_stream_t stream);
 
 /* ---- pooling over a kernel map (float32, any C; 16-byte row accesses when C % 4 == 0).  mode: 0 max, 1 average, 2 sum.
  * forward: out[o] = reduce over the PRESENT inputs in[nbr[k][o]] in ascending k; max writes arg [Vout][C] = the winning k

@@ -10,8 +10,17 @@ with an optional bias, and
     MinkowskiMaxPooling, MinkowskiAvgPooling, MinkowskiSumPooling, MinkowskiGlobalMaxPooling,
     MinkowskiGlobalAvgPooling, MinkowskiGlobalSumPooling, MinkowskiLinear, MinkowskiDropout
 
-Not supported (each raises NotImplementedError naming it): strides other than 1 and 2, transposed convolutions or
-pooling that create coordinates, dimension != 3, per-axis kernel tuples.
+and the layers of networks that create and drop coordinates (completion, reconstruction, decoders without an encoder of
+the same shape):
+
+    MinkowskiGenerativeConvolutionTranspose, MinkowskiPruning, SparseTensor.features_at_coordinates
+    (+ SparseTensor.coordinate_rows, CoordinateManager.rooted: engine extras)
+
+A generated or pruned tensor lives on a coordinate manager rooted at its own tensor stride; every layer above works on it.
+
+Not supported (each raises NotImplementedError naming it): strides other than 1 and 2, a generative layer at stride 2 on an odd
+tensor stride, MinkowskiConvolutionTranspose onto a coordinate set that is not cached, convolutions (expand_coordinates) or
+pooling that create coordinates, MinkowskiUnion / MinkowskiBroadcast, dimension != 3, per-axis kernel tuples.
 
 Module/parameter names match ME so reference state_dicts keep their keys (`kernel`, `bn.weight`, ...).
 """
@@ -20,7 +29,8 @@ from .tensor import SparseTensor, CoordinateManager, cat, prefetch_coordinates  
 from .modules import (MinkowskiConvolution, MinkowskiConvolutionTranspose, MinkowskiBatchNorm,  # noqa: F401
                       MinkowskiReLU, prepare_conv_weights, release_conv_weights,
                       MinkowskiMaxPooling, MinkowskiAvgPooling, MinkowskiSumPooling, MinkowskiGlobalMaxPooling,
-                      MinkowskiGlobalAvgPooling, MinkowskiGlobalSumPooling, MinkowskiLinear, MinkowskiDropout)
+                      MinkowskiGlobalAvgPooling, MinkowskiGlobalSumPooling, MinkowskiLinear, MinkowskiDropout,
+                      MinkowskiGenerativeConvolutionTranspose, MinkowskiPruning)
 from .tensor import kernel_offsets  # noqa: F401  (engine extra: the offset list of a kernel, in weight order)
 from .functional import gather_rows  # noqa: F401  (engine extra: x[idx] with a scatter-add backward)
 from .functional import SkipLink  # noqa: F401  (engine extra: a residual block's skip gradient, see functional.py)

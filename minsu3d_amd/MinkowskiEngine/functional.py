@@ -510,6 +510,33 @@ class PermuteRowsFn(torch.autograd.Function):
         return _rows(dy, perm), None, None
 
 
+class SelectRowsFn(torch.autograd.Function):
+    """y = x[idx] for an int64 index that names no row twice (pruning): the backward stores dy through the same index into a
+    zeroed buffer -- one writer per row, no atomics, dropped rows get exactly zero"""
+
+    @staticmethod
+    def forward(ctx, x, idx):
+        be = get_backend()
+        if not hasattr(be, "scatter_rows"):
+            raise NotImplementedError("pruning needs the HIP backend (ms3d_coords_prune / ms3d_scatter_rows)")
+        ctx.save_for_backward(idx)
+        ctx.n_rows = x.size(0)
+        if idx.numel() == 0:             # an all-false mask: no launch on an empty grid
+            return x.new_empty((0, x.size(1)))
+        return be.gather_rows(x.contiguous(), idx)
+
+    @staticmethod
+    def backward(ctx, dy):
+        (idx,) = ctx.saved_tensors
+        if idx.numel() == 0:
+            return dy.new_zeros((ctx.n_rows, dy.size(1))), None
+        return get_backend().scatter_rows(dy.contiguous(), idx, ctx.n_rows), None
+
+
+def select_rows(x, idx):
+    return SelectRowsFn.apply(x, idx)
+
+
 def gather_rows(x, idx, max_dup=None):
     """differentiable x[idx] for 2-D float features and an int64 row index.  max_dup: the caller's bound on how many
     NON-ZERO addends one element of the gradient can collect -- how many entries of idx name the same row, or fewer when

@@ -20,6 +20,8 @@ from .tensor import SparseTensor, check_geometry
 
 
 class _ConvBase(nn.Module):
+    _two_sets = False     # True: input and output coordinate sets differ at every stride (no mirrored backward-data weights)
+
     def __init__(self, in_channels, out_channels, kernel_size=-1, stride=1, dilation=1, bias=False, dimension=3):
         super().__init__()
         if dimension != 3:
@@ -109,7 +111,8 @@ def prepare_conv_weights(root, precision=None):
             if buf is None or buf.device != m.kernel.device:
                 buf = m.__dict__["_wf_buf"] = torch.empty(be.wf_floats(K, cin, cout), dtype=torch.float32, device=m.kernel.device)
             # same orientation rule as the forward() of the module: 3x3x3 maps mirror their offsets in backward-data
-            layers.append((m.kernel, buf, K, cin, cout, m.kernel_size % 2 == 1 and m.kernel_size > 1 and m.stride == 1, m, grp))
+            layers.append((m.kernel, buf, K, cin, cout,
+                           m.kernel_size % 2 == 1 and m.kernel_size > 1 and m.stride == 1 and not m._two_sets, m, grp))
     prec = Fn.conv_precision(be) if precision is None else precision
     be.prep_weights_multi([l[:6] for l in layers], **Fn._pk(prec))
     token = be.weight_token
@@ -203,6 +206,48 @@ class MinkowskiConvolutionTranspose(_ConvBase):
                            fwd.sub)
         y, stats = Fn.conv(x._F, self._kernel(), spec, x._pending, want_stats=self.training, bias=self.bias)
         return x._like(y, tensor_stride=fine, stats=stats)
+
+
+class MinkowskiGenerativeConvolutionTranspose(_ConvBase):
+    """transposed convolution that CREATES its output coordinates: out[c + off_k] += x[c] @ W[k] over every input row c and
+    every kernel offset, off = kernel_offsets(kernel_size, dilation, ts // stride) -- the arithmetic of
+    MinkowskiConvolutionTranspose, on the set of all coordinates the kernel reaches instead of a cached one.  Stride 1 (odd
+    kernel sizes) keeps the tensor stride, stride 2 halves it (the input's must be even).  The output lives on its own
+    coordinate manager, rooted at the output tensor stride and shared by every generative layer of the same geometry on the
+    same input; it is usually followed by MinkowskiPruning."""
+    _two_sets = True
+
+    def forward(self, x: SparseTensor):
+        cm, ts = x.coordinate_manager, x.tensor_stride
+        out_cm, nbr_fwd, nbr_bwd, vin, vout, K, out_ts = cm.generate(ts, self.kernel_size, self.stride, self.dilation)
+        # (sub = False: a K = 27 table between two different sets stays off the submanifold backward-weight route)
+        spec = Fn.ConvSpec(nbr_fwd, nbr_bwd, vin, vout, K, self.in_channels, self.out_channels, False, False)
+        y, stats = Fn.conv(x._F, self._kernel(), spec, x._pending, want_stats=self.training, bias=self.bias)
+        return SparseTensor(y, coordinate_manager=out_cm, tensor_stride=out_ts, _stats=stats)
+
+
+class MinkowskiPruning(nn.Module):
+    """forward(x, mask): the rows of x whose entry of the bool mask [V] is set -- mask in the order of x.features /
+    x.coordinates -- on a coordinate manager of their own, rooted at x's tensor stride.  .features is x.features[mask] and
+    .coordinates is x.coordinates[mask] bit for bit; dropped rows receive a zero gradient.  A pending BatchNorm / ReLU is
+    materialised first."""
+
+    def forward(self, x: SparseTensor, mask):
+        cm, ts = x.coordinate_manager, x.tensor_stride
+        be = get_backend()
+        if not hasattr(be, "coords_prune"):
+            raise NotImplementedError("MinkowskiPruning needs the HIP backend (ms3d_coords_prune)")
+        coords = x.coordinates
+        if mask.dtype != torch.bool or mask.dim() != 1 or mask.numel() != coords.size(0):
+            raise ValueError(f"MinkowskiPruning: the mask must be bool [{coords.size(0)}], one entry per row of the input")
+        out_coords, src_row, _ = be.coords_prune(coords, mask.to(coords.device))
+        idx = src_row.long()
+        if ts == 1 and cm.inv is not None:
+            # the mask (and the rows that come out) are in the caller's order, the features are held in the engine's: one
+            # gather through the composed index instead of un-permuting all rows first
+            idx = cm.inv[idx]
+        y = Fn.select_rows(x._raw(), idx)
+        return SparseTensor(y, coordinate_manager=type(cm).rooted(out_coords, ts), tensor_stride=ts)
 
 
 class MinkowskiBatchNorm(nn.Module):

@@ -68,6 +68,51 @@ class CoordinateManager:
         self._kinv = {}     # the same key -> inverse table (pooling backward over a submanifold map)
         self._batch_rows = {}
 
+    @classmethod
+    def rooted(cls, coordinates, tensor_stride):
+        """a manager whose FIRST coordinate set lives at `tensor_stride` (a generated or pruned set: nothing finer exists
+        below it).  No Morton permutation -- the rows stay in the order they were made in, which is the order callers see.
+        k3 / k2 / identity / kernel_map / kernel_map_inverse / batch_rows work from that stride upward."""
+        assert coordinates.dtype == torch.int32 and coordinates.dim() == 2 and coordinates.size(1) == 4
+        cm = cls.__new__(cls)
+        cm.perm = cm.inv = None
+        cm.root = int(tensor_stride)
+        cm.coords = {cm.root: coordinates.contiguous()}
+        cm._k3, cm._k2, cm._ident, cm._kmaps, cm._kinv, cm._batch_rows = {}, {}, {}, {}, {}, {}
+        return cm
+
+    def generate(self, ts, kernel_size, stride=1, dilation=1):
+        """what a generative transposed convolution from tensor stride ts needs -> (manager rooted at ts // stride on the
+        generated set, nbr_fwd [K, Vout], nbr_bwd [K, Vin], Vin, Vout, K, output tensor stride); built once per (ts, kernel
+        size, stride, dilation), so two layers of one geometry on one input share the output manager.  The set is every
+        c + offsets[k] over the input rows c and kernel_offsets(kernel_size, dilation, ts // stride), in first-occurrence
+        order (backend.coords_expand); nbr_fwd[k][o] = input row at out[o] - offsets[k], nbr_bwd its inverse."""
+        kernel_size, stride, dilation = int(kernel_size), int(stride), int(dilation)
+        check_geometry(kernel_size, stride, dilation)
+        geom = f"kernel_size={kernel_size}, stride={stride}, dilation={dilation}"
+        if ts % stride != 0:
+            raise NotImplementedError(f"{geom} on tensor stride {ts}: a generative stride-2 layer needs an even tensor stride")
+        cache = self.__dict__.setdefault("_generated", {})
+        key = (ts, kernel_size, stride, dilation)
+        gen = cache.get(key)
+        if gen is None:
+            be = get_backend()
+            if not (hasattr(be, "coords_expand") and hasattr(be, "kmap_general")):
+                raise NotImplementedError(f"{geom}: generating coordinates needs the HIP backend (ms3d_coords_expand)")
+            out_ts = ts // stride
+            offsets = kernel_offsets(kernel_size, dilation, out_ts)
+            cin = self.coords[ts]
+            vin, K = cin.size(0), offsets.shape[0]
+            # first occurrence counts in the order of the rows the CALLER sees (x.coordinates): on a Morton-sorted manager
+            # the set is expanded from the external rows, the tables below are built over the engine's
+            ext = self.coords_external if (ts == 1 and self.perm is not None) else cin
+            out = be.coords_expand(ext, torch.from_numpy(offsets))
+            vout = out.size(0)
+            nbr_fwd = be.kmap_general(cin, out, torch.from_numpy(-offsets))
+            nbr_bwd = be.kmap_invert(nbr_fwd, K, vout, vin)
+            gen = cache[key] = (CoordinateManager.rooted(out, out_ts), nbr_fwd, nbr_bwd, vin, vout, K, out_ts)
+        return gen
+
     def kernel_map(self, ts, kernel_size, stride=1, dilation=1):
         """-> (nbr_fwd [K, Vout], nbr_bwd [K, Vin], Vin, Vout, K, output tensor stride, mirror) for a layer from the
         coordinate set of tensor stride ts; built once per key.  (3, 1, 1), (2, 2, 1) and (1, 1, *) are the tables of
@@ -341,6 +386,35 @@ class SparseTensor:
         return SparseTensor(features, coordinate_manager=self.coordinate_manager,
                             tensor_stride=self.tensor_stride if tensor_stride is None else tensor_stride,
                             _pending=pending, _stats=stats)
+
+    # ---- rows by coordinate
+    def coordinate_rows(self, query):
+        """int32 [N]: the row of `.features` / `.coordinates` that holds each coordinate of `query` (int [N, 4]: b, x, y, z),
+        -1 where the tensor has no such voxel.  A lookup in the hash table of the coordinate set (the K = 1, offset-0 kernel
+        map); not part of ME's API."""
+        assert query.dim() == 2 and query.size(1) == 4
+        cm, ts = self.coordinate_manager, self.tensor_stride
+        be = get_backend()
+        if not hasattr(be, "kmap_general"):
+            raise NotImplementedError("coordinate_rows needs the HIP backend (ms3d_kmap_general)")
+        n = query.size(0)
+        if n == 0:
+            return torch.empty(0, dtype=torch.int32, device=self.device)
+        q = query.to(device=self.device, dtype=torch.int32).contiguous()
+        rows = be.kmap_general(cm.coords[ts], q, torch.zeros((1, 3), dtype=torch.int32)).view(-1)[:n]
+        if ts == 1 and cm.perm is not None:      # the set is held in the engine's row order: name the caller's rows
+            rows = torch.where(rows >= 0, cm.perm[rows.clamp(min=0).long()], rows.long()).to(torch.int32)
+        return rows
+
+    def features_at_coordinates(self, query):
+        """float [N, C]: the feature row at each coordinate of `query` (int [N, 4]), zeros where the tensor has no such voxel;
+        differentiable (a coordinate asked for twice sends both gradients to its row, summed in a fixed order)"""
+        rows = self.coordinate_rows(query).long()
+        feats = self.features
+        if rows.numel() == 0:
+            return feats.new_zeros((0, feats.size(1)))
+        padded = torch.cat([feats, feats.new_zeros((1, feats.size(1)))])      # absent -> the zero row behind the last one
+        return Fn.gather_rows(padded, torch.where(rows < 0, torch.full_like(rows, feats.size(0)), rows))
 
     def __iadd__(self, other):      # `x += identity` (common.py:48)
         self._F = self._raw() + other._raw()

@@ -873,6 +873,62 @@ class _HipEngine:
                    "ms3d_kmap_invert")
         return inv
 
+    # ---- coordinate sets that are generated or pruned
+    def coords_expand(self, in_coords, offsets):
+        """-> int32 [n, 4]: the distinct (b, xyz + offsets[k]) over all rows of in_coords and all offsets, in first-occurrence
+        order of the candidates (input row major, offset minor).  offsets: int32 [K, 3] in voxel units (host or device
+        tensor).  A candidate outside the packable range raises HipLibraryError (MS3D_E_UNSUPPORTED).  One host sync."""
+        in_coords = self._dev(in_coords)
+        assert in_coords.dtype == torch.int32 and in_coords.dim() == 2 and in_coords.size(1) == 4
+        vin, dev = in_coords.size(0), in_coords.device
+        offsets = offsets.to(device=dev, dtype=torch.int32).contiguous()
+        K = offsets.size(0)
+        assert offsets.dim() == 2 and offsets.size(1) == 3 and K >= 1
+        n_cand = vin * K
+        if vin == 0:
+            return torch.empty((0, 4), dtype=torch.int32, device=dev)
+        if n_cand > 2 ** 31 - 1:
+            # (refused here as the entry point refuses it: Vin * K would not even fit its int arguments' product)
+            _lib.check(_lib.E_UNSUPPORTED, f"ms3d_coords_expand ({vin} rows x {K} offsets: more than 2^31 - 1 candidates)")
+        out = torch.empty((n_cand, 4), dtype=torch.int32, device=dev)
+        # (not the grow-only scratch: the table is sized by the candidates, tens of bytes each, and is needed once per set)
+        ws = torch.empty(self.lib.ms3d_coords_expand_workspace_bytes(vin, K) + 256, dtype=torch.uint8, device=dev)
+        n = C.c_int(0)
+        _lib.check(self.lib.ms3d_coords_expand(_lib.ptr(in_coords), vin, _lib.ptr(offsets), K, _lib.ptr(out), C.byref(n),
+                                               _lib.ptr(ws), C.c_size_t(ws.numel()), _lib.stream_handle()),
+                   "ms3d_coords_expand")
+        return out[:n.value].clone() if n.value < n_cand else out      # (a slice would keep all Vin * K rows alive)
+
+    def coords_prune(self, coords, keep):
+        """rows of coords [V, 4] with keep [V] (bool / uint8) set, in their order -> (out_coords int32 [n, 4], src_row int32
+        [n]: kept row -> source row, dst_row int32 [V]: source row -> kept row or -1).  One host sync."""
+        coords, keep = self._dev(coords), self._dev(keep)
+        assert coords.dtype == torch.int32 and coords.dim() == 2 and coords.size(1) == 4
+        V, dev = coords.size(0), coords.device
+        assert keep.dim() == 1 and keep.numel() == V and keep.dtype in (torch.bool, torch.uint8)
+        if keep.dtype == torch.bool:
+            keep = keep.view(torch.uint8)
+        out = torch.empty((max(V, 1), 4), dtype=torch.int32, device=dev)
+        src = torch.empty(max(V, 1), dtype=torch.int32, device=dev)
+        dst = torch.empty(V, dtype=torch.int32, device=dev)
+        ws = self._cws(V, dev)
+        n = C.c_int(0)
+        _lib.check(self.lib.ms3d_coords_prune(_lib.ptr(coords), V, _lib.ptr(keep), _lib.ptr(out), _lib.ptr(src), _lib.ptr(dst),
+                                              C.byref(n), _lib.ptr(ws), C.c_size_t(ws.numel()), _lib.stream_handle()),
+                   "ms3d_coords_prune")
+        if n.value == V:
+            return out[:V], src[:V], dst
+        return out[:n.value].clone(), src[:n.value].clone(), dst
+
+    def scatter_rows(self, src, idx, n_rows):
+        """dst [n_rows, C] = 0; dst[idx[i]] = src[i] for an int64 index without repeats (plain stores, one writer per row)"""
+        src = self._dev(src); idx = self._dev(idx)
+        assert idx.dtype == torch.int64 and src.dtype == torch.float32 and src.dim() == 2 and idx.numel() == src.size(0)
+        dst = torch.zeros((n_rows, src.size(1)), dtype=torch.float32, device=src.device)
+        _lib.check(self.lib.ms3d_scatter_rows(_lib.ptr(src), _lib.ptr(idx), C.c_long(src.size(0)), int(src.size(1)),
+                                              _lib.ptr(dst), _lib.stream_handle()), "ms3d_scatter_rows")
+        return dst
+
     # ---- pooling over a kernel map (mode: 0 max, 1 average, 2 sum)
     def pool_forward(self, mode, x, nbr, vout, K):
         """-> (out [vout, C], arg uint8 [vout, C] for max else None, count int32 [vout] for average else None)"""

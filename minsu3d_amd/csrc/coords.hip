@@ -12,6 +12,7 @@
 //       k2 s2 : down[k][p] = child of coarse row p at offset k;  up[k][f] = (k == koff[f]) ? parent[f] : -1
 //       general: nbr[k][o] = row at c_o + offsets[k] for any offset list (any kernel size, stride, dilation), and the
 //               inverse table nbr_inv[k][i] = o of a map that is not its own mirror image
+#include <algorithm>
 #include <mutex>
 #include <unordered_map>
 #include "common.h"
@@ -198,6 +199,143 @@ __global__ void kmap_k2_kernel(const int *__restrict__ parent, const int *__rest
     const int p = parent[f], k = koff[f];
     nbr_down[(size_t)k * Vc + p] = f;
     nbr_up[(size_t)k * Vf + f] = p;
+}
+
+// ------------------------------------------------------------------ coordinate generation / pruning
+// Candidate c = i * K + k of ms3d_coords_expand is (batch of input row i, xyz of row i + offsets[k]); it is computed where it
+// is needed, never stored.  The launches below are grid-stride over the candidates with a bounded grid (EXPAND_MAX_BLOCKS
+// workgroups); every index that can pass 2^31 is 64 bits wide, slots are unsigned (a table of up to 2^32 slots).
+constexpr int EXPAND_MAX_BLOCKS = 8192;
+
+__device__ __forceinline__ int4 expand_candidate(const int *__restrict__ coords, const int *__restrict__ offsets, int K,
+                                                 long long c, bool *ok)
+{
+    const long long i = c / K;
+    const int k = (int)(c - i * K);
+    const int4 p = reinterpret_cast<const int4 *>(coords)[i];
+    // the sums in 64 bits: an input row or an offset that is garbage must raise the flag, not overflow an int (and the input
+    // row itself is checked too: a sum of two out-of-range values could land back inside the range)
+    const long long x = (long long)p.y + offsets[3 * k], y = (long long)p.z + offsets[3 * k + 1],
+                    z = (long long)p.w + offsets[3 * k + 2];
+    *ok = in_range(p.y) && in_range(p.z) && in_range(p.w) && p.x >= 0 && p.x <= 0x7FFFF && x >= -16384 && x < 16384 &&
+          y >= -16384 && y < 16384 && z >= -16384 && z < 16384;
+    const int4 q = make_int4(p.x, (int)x, (int)y, (int)z);
+    return q;
+}
+
+__global__ __launch_bounds__(256) void expand_clear_kernel(unsigned long long *keys, int *vals, size_t H, int *range_flag)
+{
+    const size_t step = (size_t)gridDim.x * blockDim.x;
+    for (size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x; t < H; t += step) {
+        keys[t] = EMPTY_KEY;
+        vals[t] = 0x7fffffff;
+    }
+    if (blockIdx.x == 0 && threadIdx.x == 0) *range_flag = 0;
+}
+
+// the insert of table_insert_kernel (64-bit CAS on the key, atomicMin of the candidate index on the value) per candidate.  A
+// candidate that does not fit the key raises range_flag and is left out of the table (slot = none): the entry point then
+// returns MS3D_E_UNSUPPORTED, nothing is aliased onto another voxel.
+__global__ __launch_bounds__(256) void expand_insert_kernel(const int *__restrict__ coords, const int *__restrict__ offsets,
+                                                            int K, long long N, unsigned long long *keys, int *vals,
+                                                            unsigned mask, unsigned *__restrict__ slot_of_cand,
+                                                            int *range_flag)
+{
+    const long long step = (long long)gridDim.x * blockDim.x;
+    for (long long c = (long long)blockIdx.x * blockDim.x + threadIdx.x; c < N; c += step) {
+        bool ok;
+        const int4 q = expand_candidate(coords, offsets, K, c, &ok);
+        if (!ok) {
+            if (*range_flag == 0) atomicOr(range_flag, 1);
+            slot_of_cand[c] = 0xFFFFFFFFu;
+            continue;
+        }
+        const unsigned long long key = pack_key(q.x, q.y, q.z, q.w);
+        unsigned slot = (unsigned)mix64(key) & mask;
+        for (;;) {
+            const unsigned long long prev = atomicCAS(&keys[slot], EMPTY_KEY, key);
+            if (prev == EMPTY_KEY || prev == key) break;
+            slot = (slot + 1) & mask;
+        }
+        atomicMin(&vals[slot], (int)c);
+        slot_of_cand[c] = slot;
+    }
+}
+
+// has_range: the table of up to 2^32 slots needs every slot number, so "no slot" is told by the flag of the whole call: the
+// flag kernel only runs its lookups when no candidate was out of range (otherwise every flag is 0 and nothing is emitted)
+__global__ __launch_bounds__(256) void expand_flag_kernel(long long N, const unsigned *__restrict__ slot_of_cand,
+                                                          const int *__restrict__ vals, const int *__restrict__ range_flag,
+                                                          int *__restrict__ flag)
+{
+    const bool bad = *range_flag != 0;
+    const long long step = (long long)gridDim.x * blockDim.x;
+    for (long long c = (long long)blockIdx.x * blockDim.x + threadIdx.x; c < N; c += step)
+        flag[c] = (!bad && vals[slot_of_cand[c]] == (int)c) ? 1 : 0;
+}
+
+__global__ __launch_bounds__(256) void expand_emit_kernel(const int *__restrict__ coords, const int *__restrict__ offsets,
+                                                          int K, long long N, const unsigned *__restrict__ slot_of_cand,
+                                                          const int *__restrict__ vals, const int *__restrict__ rank,
+                                                          int *__restrict__ out_coords)
+{
+    const long long step = (long long)gridDim.x * blockDim.x;
+    for (long long c = (long long)blockIdx.x * blockDim.x + threadIdx.x; c < N; c += step) {
+        if (vals[slot_of_cand[c]] != (int)c) continue;
+        bool ok;
+        const int4 q = expand_candidate(coords, offsets, K, c, &ok);
+        reinterpret_cast<int4 *>(out_coords)[rank[c]] = q;     // rank[c] < number of distinct candidates <= capacity
+    }
+}
+
+struct ExpandWs {
+    unsigned long long *keys;
+    int *vals, *rank, *total;
+    unsigned *slot_of_cand;
+    void *scan_ws;
+    size_t H;
+};
+size_t carve_expand(ExpandWs &w, long long N, void *base)
+{
+    size_t off = 0;
+    auto take = [&](size_t bytes) {
+        void *r = base ? (void *)((char *)base + off) : nullptr;
+        off += ms3d_align(bytes);
+        return r;
+    };
+    w.H = 1024;
+    while (w.H < 2 * (size_t)N) w.H <<= 1;                      // load factor <= 1/2, as table_size(); at most 2^32 slots
+    w.keys = (unsigned long long *)take(sizeof(unsigned long long) * w.H);
+    w.vals = (int *)take(sizeof(int) * w.H);
+    w.slot_of_cand = (unsigned *)take(sizeof(unsigned) * (size_t)N);
+    w.rank = (int *)take(sizeof(int) * (size_t)N);             // first-occurrence flags, scanned in place
+    w.total = (int *)take(sizeof(int) * 2);
+    w.scan_ws = take(ms3d_scan_workspace_bytes());
+    return off;
+}
+inline int expand_grid(long long n) { return (int)std::min<long long>((n + 255) / 256, EXPAND_MAX_BLOCKS); }
+
+__global__ __launch_bounds__(256) void prune_flag_kernel(int V, const unsigned char *__restrict__ keep, int *__restrict__ flag)
+{
+    const long long step = (long long)gridDim.x * blockDim.x;
+    for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < V; i += step) flag[i] = keep[i] ? 1 : 0;
+}
+// kept rows keep their relative order: kept row rank[i] <- source row i
+__global__ __launch_bounds__(256) void prune_emit_kernel(int V, const int *__restrict__ coords,
+                                                         const unsigned char *__restrict__ keep, const int *__restrict__ rank,
+                                                         int *__restrict__ out_coords, int *__restrict__ src_row,
+                                                         int *__restrict__ dst_row)
+{
+    const long long step = (long long)gridDim.x * blockDim.x;
+    for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < V; i += step) {
+        const bool k = keep[i] != 0;
+        const int r = rank[i];
+        if (k) {
+            reinterpret_cast<int4 *>(out_coords)[r] = reinterpret_cast<const int4 *>(coords)[i];
+            src_row[r] = (int)i;
+        }
+        dst_row[i] = k ? r : -1;
+    }
 }
 
 // 64-bit spatial sort key: batch index, then the 45-bit Morton code of the biased (x,y,z)
@@ -577,6 +715,65 @@ int ms3d_kmap_invert(const int *nbr, int K, int Vout, int Vin, int *nbr_inv, ms3
     dim3 grid(ms3d_divup(Vout, 256), K);
     kmap_invert_kernel<<<grid, 256, 0, stream>>>(nbr, Vout, Vin, nbr_inv);
     MS3D_LAUNCH_CHECK();
+    return 0;
+}
+
+size_t ms3d_coords_expand_workspace_bytes(int Vin, int K)
+{
+    ExpandWs w;
+    const long long N = (long long)(Vin > 0 ? Vin : 0) * (K > 0 ? K : 0);
+    if (N > 0x7fffffffll) return 0;
+    return carve_expand(w, N > 0 ? N : 1, nullptr);
+}
+
+int ms3d_coords_expand(const int *in_coords, int Vin, const int *offsets, int K, int *out_coords, int *n_out, void *workspace,
+                       size_t workspace_bytes, ms3d_stream_t stream_)
+{
+    hipStream_t stream = (hipStream_t)stream_;
+    *n_out = 0;
+    if (K < 1) return MS3D_E_UNSUPPORTED;
+    if (Vin <= 0) return 0;
+    const long long N = (long long)Vin * K;
+    if (N > 0x7fffffffll) return MS3D_E_UNSUPPORTED;       // candidate indices are the int values of the table
+    ExpandWs w;
+    if (carve_expand(w, N, workspace) > workspace_bytes) return MS3D_E_WORKSPACE;
+    const int grid = expand_grid(N);
+    expand_clear_kernel<<<expand_grid((long long)w.H), 256, 0, stream>>>(w.keys, w.vals, w.H, w.total + 1);
+    MS3D_LAUNCH_CHECK();
+    expand_insert_kernel<<<grid, 256, 0, stream>>>(in_coords, offsets, K, N, w.keys, w.vals, (unsigned)(w.H - 1), w.slot_of_cand,
+                                                   w.total + 1);
+    MS3D_LAUNCH_CHECK();
+    expand_flag_kernel<<<grid, 256, 0, stream>>>(N, w.slot_of_cand, w.vals, w.total + 1, w.rank);
+    MS3D_LAUNCH_CHECK();
+    int rc = ms3d_exclusive_scan_i32(w.rank, w.rank, (int)N, w.total, w.scan_ws, stream);
+    if (rc) return rc;
+    int h[2] = {0, 0};   // [0] number of distinct candidates  [1] a candidate did not fit the key
+    MS3D_CHECK(hipMemcpyAsync(h, w.total, sizeof(int) * 2, hipMemcpyDeviceToHost, stream));
+    MS3D_CHECK(hipStreamSynchronize(stream));
+    if (h[1]) return MS3D_E_UNSUPPORTED;
+    *n_out = h[0];
+    expand_emit_kernel<<<grid, 256, 0, stream>>>(in_coords, offsets, K, N, w.slot_of_cand, w.vals, w.rank, out_coords);
+    MS3D_LAUNCH_CHECK();
+    return 0;
+}
+
+int ms3d_coords_prune(const int *coords, int V, const unsigned char *keep, int *out_coords, int *src_row, int *dst_row,
+                      int *n_kept, void *workspace, size_t workspace_bytes, ms3d_stream_t stream_)
+{
+    hipStream_t stream = (hipStream_t)stream_;
+    *n_kept = 0;
+    if (V <= 0) return 0;
+    CoordWs w;
+    if (carve(w, V, workspace) > workspace_bytes) return MS3D_E_WORKSPACE;
+    const int grid = expand_grid(V);
+    prune_flag_kernel<<<grid, 256, 0, stream>>>(V, keep, w.rank);
+    MS3D_LAUNCH_CHECK();
+    int rc = ms3d_exclusive_scan_i32(w.rank, w.rank, V, w.total, w.scan_ws, stream);
+    if (rc) return rc;
+    MS3D_CHECK(hipMemcpyAsync(n_kept, w.total, sizeof(int), hipMemcpyDeviceToHost, stream));
+    prune_emit_kernel<<<grid, 256, 0, stream>>>(V, coords, keep, w.rank, out_coords, src_row, dst_row);
+    MS3D_LAUNCH_CHECK();
+    MS3D_CHECK(hipStreamSynchronize(stream));
     return 0;
 }
 

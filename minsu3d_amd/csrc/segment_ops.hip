@@ -318,6 +318,26 @@ __global__ void gather_rows_scalar_kernel(const float *__restrict__ x, const lon
     out[t] = x[idx[i] * C + (t - i * C)];
 }
 
+// dst[idx[i], :] = src[i, :] for an index WITHOUT repeats (the backward of a row selection: one writer per row, plain stores
+// into the caller's zeroed buffer)
+__global__ void scatter_rows_kernel(const float *__restrict__ src, const long long *__restrict__ idx, long n, int C4,
+                                    float *__restrict__ dst)
+{
+    const long t = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (t >= n * C4) return;
+    const long i = t / C4;
+    const int c = (int)(t - i * C4);
+    reinterpret_cast<float4 *>(dst)[idx[i] * C4 + c] = reinterpret_cast<const float4 *>(src)[t];
+}
+__global__ void scatter_rows_scalar_kernel(const float *__restrict__ src, const long long *__restrict__ idx, long n, int C,
+                                           float *__restrict__ dst)
+{
+    const long t = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (t >= n * C) return;
+    const long i = t / C;
+    dst[idx[i] * C + (t - i * C)] = src[t];
+}
+
 __global__ void scatter_add_rows_kernel(const float *__restrict__ src, const long long *__restrict__ idx, long n, int C,
                                         float *__restrict__ dst)
 {
@@ -591,6 +611,17 @@ int ms3d_gather_rows(const float *x, const long long *idx, long n, int C, float 
         gather_rows_kernel<<<ms3d_divup(n * (C / 4), 256), 256, 0, (hipStream_t)stream>>>(x, idx, n, C / 4, out);
     else
         gather_rows_scalar_kernel<<<ms3d_divup(n * C, 256), 256, 0, (hipStream_t)stream>>>(x, idx, n, C, out);
+    MS3D_LAUNCH_CHECK();
+    return 0;
+}
+
+int ms3d_scatter_rows(const float *src, const long long *idx, long n, int C, float *dst, ms3d_stream_t stream)
+{
+    if (n <= 0 || C <= 0) return 0;
+    if (C % 4 == 0 && ((uintptr_t)src % 16) == 0 && ((uintptr_t)dst % 16) == 0)
+        scatter_rows_kernel<<<ms3d_divup(n * (C / 4), 256), 256, 0, (hipStream_t)stream>>>(src, idx, n, C / 4, dst);
+    else
+        scatter_rows_scalar_kernel<<<ms3d_divup(n * C, 256), 256, 0, (hipStream_t)stream>>>(src, idx, n, C, dst);
     MS3D_LAUNCH_CHECK();
     return 0;
 }
