@@ -227,6 +227,59 @@ int ms3d_coords_expand(const int *in_coords, int Vin, const int *offsets, int K,
 int ms3d_coords_prune(const int *coords, int V, const unsigned char *keep, int *out_coords, int *src_row, int *dst_row,
                       int *n_kept /*[host]*/, void *workspace, size_t workspace_bytes, ms3d_stream_t stream);
 
+/* ---- arithmetic across coordinate sets: union of sets, feature combine, broadcast of one row per batch index.
+ * ms3d_coords_union: the distinct coordinates of N sets (1 <= N <= 16) of one tensor stride, handed over back to back as coords
+ * [set_start[N], 4] with HOST offsets set_start [N + 1] (set_start[0] = 0, ascending; set i = rows set_start[i] ..
+ * set_start[i + 1]).  Order: first occurrence in the concatenation -- all rows of set 0 in their order, then the rows of set 1
+ * that set 0 lacks, and so on (the rule of ms3d_sparse_quantize / ms3d_downsample / ms3d_coords_expand; 64-bit CAS on the key,
+ * atomicMin of the row, flag -> scan -> emit at rank; no sort, no float atomics, the same bytes on every run).
+ *   out_coords [n_out, 4]   capacity set_start[N] rows
+ *   out_row [set_start[N]]  input row of the concatenation -> union row
+ *   in_row [N][n_out]       union row -> row of set i (counted from the set's first row) or -1; PACKED with the row length
+ *                           n_out that the call returns, capacity N * set_start[N] ints; plain stores, one writer per cell
+ *   *n_out -> [host]        one sync
+ * A coordinate that repeats INSIDE one set (every slot keeps one bit per set; a row that finds its set's bit raised), a row outside the packable range
+ * [-16384, 16384) / batch index outside [0, 524288), N outside 1..16, a NULL or descending set_start, or more than 2^30 - 1
+ * rows: MS3D_E_UNSUPPORTED (repeats are never merged silently; the outputs are then not to be used).  An empty set is legal;
+ * all sets empty: *n_out = 0 and nothing is launched.  workspace: ms3d_coords_union_workspace_bytes(set_start[N]) -- a table of
+ * the next power of two >= 2 rows slots of 16 bytes (key, row, set bits: 32 .. 64 bytes per row) plus 12 bytes per row (0 when
+ * out of range). */
+size_t ms3d_coords_union_workspace_bytes(int total_rows);
+int ms3d_coords_union(const int *coords, const int *set_start /*[host] N + 1*/, int n_sets, int *out_coords, int *out_row,
+                      int *in_row, int *n_out /*[host]*/, void *workspace, size_t workspace_bytes, ms3d_stream_t stream);
+/* ms3d_union_combine (float32, any C; 16-byte row accesses when C % 4 == 0 and the rows are 16-byte aligned): out [n_out, C]
+ * from the N feature arrays in_feats (HOST array of N device pointers; set i is [V_i, C]) gathered through in_row [N][n_out]
+ * in ASCENDING input order.  op 0 sum (any N): out[o] = sum over the inputs present; op 1 subtract, op 2 multiply (N = 2).
+ * A coordinate one operand lacks: the result is zero-filled, receives a at a's rows and is then set to fn(out, b) at b's rows
+ * -- a - b gives -b where only b is, a * b gives a where only a is and 0 * b where only b is.  The in_row entries name rows of
+ * the arrays as they are passed (the caller composes any row permutation of its own into them).
+ * backward (operand `which`): a gather, din [V, C] with din[r] = dout[out_row[r]] -- negated for the second operand of
+ * subtract; for multiply scaled by the other operand's row other[other_row[o]] (other_row = in_row[1 - which]), passed through
+ * unscaled for operand 0 where the other is absent, zero for operand 1 where the other is absent (the derivative of 0 * b).
+ * other / other_row may be NULL unless op == 2. */
+int ms3d_union_combine(int op, const float *const *in_feats /*[host] N*/, int n_sets, const int *in_row, int n_out, int C,
+                       float *out, ms3d_stream_t stream);
+int ms3d_union_combine_backward(int op, int which, const float *dout, const int *out_row, int V, const float *other,
+                                const int *other_row, int C, float *din, ms3d_stream_t stream);
+/* ms3d_broadcast_forward: out[r] = x[r] (mode) g[grow[r]] for x [V, C], g [G, Cg], grow [V] = the row of g that carries the
+ * voxel's batch index.  mode 0 add, 1 multiply (C == Cg, out [V, C]); 2 concatenate (out [V, C + Cg], x in front); 3 copy (out
+ * [V, Cg]; x and C are not read).  grow[r] = -1 (no global row for that batch index): the voxel sees the zero vector -- the
+ * caller's map says so, nothing is checked per call.  The gradient of x is the identity (add), a column slice (concatenate) or
+ * this kernel with dout in place of x (multiply).
+ * ms3d_broadcast_reduce: the gradient of g, dg [G, C] with dg[j] = sum over the rows r of g row j's batch of dout[r, col_off :
+ * col_off + C] (times x[r] when x != NULL: multiply, never materialised).  dout has leading dimension ldd (a column slice of a
+ * wider gradient is read in place).  The rows of a batch are order[seg_start[s] .. seg_start[s + 1]) (int64 rows, int32
+ * offsets: CoordinateManager.batch_rows), s = seg_of_g[j] or -1 (dg[j] = 0).  Fixed order: the segment is cut into 64 slices
+ * of ceil(len / 64) rows, a block sums one slice (each thread its rows in ascending order, the threads of a column in ascending
+ * order), a second kernel adds the 64 partial sums in slice order.  workspace: ms3d_broadcast_reduce_workspace_bytes(G, C) = 64
+ * G C floats.  G <= 65535. */
+int ms3d_broadcast_forward(int mode, const float *x, const float *g, const int *grow, int V, int C, int Cg, float *out,
+                           ms3d_stream_t stream);
+size_t ms3d_broadcast_reduce_workspace_bytes(int G, int C);
+int ms3d_broadcast_reduce(const float *dout, int ldd, int col_off, const float *x, int C, const long long *order,
+                          const int *seg_start, const int *seg_of_g, int G, float *dg, void *workspace, size_t workspace_bytes,
+                          ms3d_stream_t stream);
+
 /* ---- pooling over a kernel map (float32, any C; 16-byte row accesses when C % 4 == 0).  mode: 0 max, 1 average, 2 sum.
  * forward: out[o] = reduce over the PRESENT inputs in[nbr[k][o]] in ascending k; max writes arg [Vout][C] = the winning k
  * (lowest k on ties; 255 and out = 0 for a row without input), average divides by the number of present inputs and writes

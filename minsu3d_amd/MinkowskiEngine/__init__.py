@@ -18,9 +18,17 @@ the same shape):
 
 A generated or pruned tensor lives on a coordinate manager rooted at its own tensor stride; every layer above works on it.
 
+Tensors on DIFFERENT coordinate sets of one tensor stride meet on the union of their sets (a manager rooted at that stride),
+and one row per batch index meets every voxel of its batch:
+
+    MinkowskiUnion, SparseTensor + - * (SparseTensors, Python scalars, torch tensors that broadcast to the rows),
+    MinkowskiBroadcastAddition, MinkowskiBroadcastMultiplication, MinkowskiBroadcastConcatenation, MinkowskiBroadcast,
+    MinkowskiSigmoid  (+ CoordinateManager.union / broadcast_map: engine extras)
+
 Not supported (each raises NotImplementedError naming it): strides other than 1 and 2, a generative layer at stride 2 on an odd
 tensor stride, MinkowskiConvolutionTranspose onto a coordinate set that is not cached, convolutions (expand_coordinates) or
-pooling that create coordinates, MinkowskiUnion / MinkowskiBroadcast, dimension != 3, per-axis kernel tuples.
+pooling that create coordinates, `+=` and ME.cat across different coordinate sets, a union of more than 16 tensors,
+MinkowskiPoolingTranspose / MinkowskiInterpolation / TensorField, dimension != 3, per-axis kernel tuples.
 
 Module/parameter names match ME so reference state_dicts keep their keys (`kernel`, `bn.weight`, ...).
 """
@@ -30,7 +38,9 @@ from .modules import (MinkowskiConvolution, MinkowskiConvolutionTranspose, Minko
                       MinkowskiReLU, prepare_conv_weights, release_conv_weights,
                       MinkowskiMaxPooling, MinkowskiAvgPooling, MinkowskiSumPooling, MinkowskiGlobalMaxPooling,
                       MinkowskiGlobalAvgPooling, MinkowskiGlobalSumPooling, MinkowskiLinear, MinkowskiDropout,
-                      MinkowskiGenerativeConvolutionTranspose, MinkowskiPruning)
+                      MinkowskiGenerativeConvolutionTranspose, MinkowskiPruning,
+                      MinkowskiUnion, MinkowskiBroadcastAddition, MinkowskiBroadcastMultiplication,
+                      MinkowskiBroadcastConcatenation, MinkowskiBroadcast, MinkowskiSigmoid)
 from .tensor import kernel_offsets  # noqa: F401  (engine extra: the offset list of a kernel, in weight order)
 from .functional import gather_rows  # noqa: F401  (engine extra: x[idx] with a scatter-add backward)
 from .functional import SkipLink  # noqa: F401  (engine extra: a residual block's skip gradient, see functional.py)

@@ -568,3 +568,84 @@ class SparsePoolFn(torch.autograd.Function):
 
 def sparse_pool(x, nbr_fwd, nbr_inv, vin, vout, K, mode):
     return SparsePoolFn.apply(x, nbr_fwd, nbr_inv, vin, vout, K, mode)
+
+
+class UnionCombineFn(torch.autograd.Function):
+    """out [n_out, C] = combine of the operands' rows on the union of their coordinate sets (op 0 sum of any number, 1
+    subtract, 2 multiply of two; csrc/setops.hip).  maps: per operand (in_row int32 [n_out]: union row -> operand row in the
+    order the operand's rows are HELD in, or -1; out_row int32 [V_i]: the other way), in_rows their [N, n_out] stack.  Both
+    directions are gathers in a fixed order."""
+
+    @staticmethod
+    def forward(ctx, op, in_rows, out_rows, n_out, *feats):
+        be = get_backend()
+        ctx.op, ctx.in_rows, ctx.out_rows = op, in_rows, out_rows
+        ctx.save_for_backward(*(feats if op == 2 else ()))
+        if n_out == 0:
+            return feats[0].new_empty((0, feats[0].size(1)))
+        return be.union_combine(op, feats, in_rows, n_out)
+
+    @staticmethod
+    def backward(ctx, dout):
+        be = get_backend()
+        op, feats = ctx.op, ctx.saved_tensors
+        grads = []
+        for i, out_row in enumerate(ctx.out_rows):
+            if not ctx.needs_input_grad[4 + i]:
+                grads.append(None)
+            elif out_row.numel() == 0:
+                grads.append(dout.new_empty((0, dout.size(1))))
+            elif op == 2:
+                grads.append(be.union_combine_backward(op, i, dout, out_row, feats[1 - i], ctx.in_rows[1 - i]))
+            else:
+                grads.append(be.union_combine_backward(op, i, dout, out_row))
+        return (None, None, None, None, *grads)
+
+
+def union_combine(op, in_rows, out_rows, n_out, feats):
+    return UnionCombineFn.apply(op, in_rows, out_rows, n_out, *feats)
+
+
+class BroadcastFn(torch.autograd.Function):
+    """y[r] = x[r] (mode) g[grow[r]]: mode 0 add, 1 multiply, 2 concatenate, 3 copy (x = None).  red = (order, seg_start,
+    seg_of_g): the rows of x grouped by batch index and the segment of every row of g -- the fixed summation order of g's
+    gradient (ms3d_broadcast_reduce).  x's gradient is dy itself, a column slice of it, or dy * g[grow]."""
+
+    @staticmethod
+    def forward(ctx, mode, x, g, grow, red):
+        be = get_backend()
+        ctx.mode, ctx.grow, ctx.red = mode, grow, red
+        ctx.cx = 0 if x is None else x.size(1)
+        ctx.save_for_backward(*((x, g) if mode == 1 else ()))
+        if grow.numel() == 0:
+            return g.new_empty((0, ctx.cx + g.size(1) if mode == 2 else g.size(1)))
+        return be.broadcast(mode, x, g, grow)
+
+    @staticmethod
+    def backward(ctx, dy):
+        be = get_backend()
+        mode, cx = ctx.mode, ctx.cx
+        dx = dg = None
+        dy = dy.contiguous()
+        if mode != 3 and ctx.needs_input_grad[1]:
+            if mode == 0:
+                dx = dy
+            elif mode == 2:
+                dx = dy[:, :cx]
+            elif dy.size(0) == 0:
+                dx = dy
+            else:
+                dx = be.broadcast(1, dy, ctx.saved_tensors[1], ctx.grow)
+        if ctx.needs_input_grad[2]:
+            cg = dy.size(1) - (cx if mode == 2 else 0)
+            order, seg_start, seg_of_g = ctx.red
+            if dy.size(0) == 0:
+                dg = dy.new_zeros((seg_of_g.numel(), cg))
+            else:
+                dg = be.broadcast_reduce(dy, cx if mode == 2 else 0, cg, ctx.saved_tensors[0] if mode == 1 else None, order,
+                                         seg_start, seg_of_g)
+        return None, dx, dg, None, None
+
+
+def broadcast(mode, x, g, grow, red):
+    return BroadcastFn.apply(mode, x, g, grow, red)

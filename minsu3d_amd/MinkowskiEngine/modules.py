@@ -16,7 +16,7 @@ import torch.nn as nn
 
 from ..backend import get_backend
 from . import functional as Fn
-from .tensor import SparseTensor, check_geometry
+from .tensor import SparseTensor, check_geometry, union_op
 
 
 class _ConvBase(nn.Module):
@@ -421,3 +421,72 @@ class MinkowskiDropout(nn.Module):
 
     def forward(self, x: SparseTensor):
         return x._like(self.dropout(x._raw()))
+
+
+class MinkowskiSigmoid(nn.Module):
+    """elementwise on the rows (the gate of a squeeze-and-excitation block)"""
+
+    def forward(self, x: SparseTensor):
+        return x._like(torch.sigmoid(x._raw()))
+
+
+class MinkowskiUnion(nn.Module):
+    """forward(*inputs): the sum of up to 16 tensors of one tensor stride and channel count on the UNION of their coordinate
+    sets -- the first input's rows in their order, then the rows of the second that the first lacks, and so on; an input that
+    lacks a coordinate adds nothing there.  The result lives on a coordinate manager rooted at that tensor stride, shared by
+    every union / + / - / * of the same operands.  Inputs on one set are added row by row; one input comes back as an equal
+    tensor."""
+
+    def forward(self, *inputs):
+        if not inputs:
+            raise ValueError("MinkowskiUnion needs at least one input")
+        first = inputs[0]
+        for t in inputs[1:]:
+            if t.tensor_stride != first.tensor_stride:
+                raise ValueError(f"MinkowskiUnion: tensor strides {first.tensor_stride} and {t.tensor_stride} differ")
+            if t._F.size(1) != first._F.size(1):
+                raise ValueError(f"MinkowskiUnion: channel counts {first._F.size(1)} and {t._F.size(1)} differ")
+        if len(inputs) > 16:
+            raise NotImplementedError(f"MinkowskiUnion of {len(inputs)} inputs: at most 16")
+        if all(t.coordinate_manager is first.coordinate_manager for t in inputs[1:]):
+            y = first._raw()
+            for t in inputs[1:]:
+                y = y + t._raw()
+            return first._like(y)
+        return union_op(0, *inputs)
+
+
+class _BroadcastBase(nn.Module):
+    """forward(x, x_glob): x_glob holds one row per batch index (what the global poolings return; only the batch column of
+    its coordinates is read), every voxel of x meets the row of its batch index.  The result lives on x's coordinate manager
+    and tensor stride.  A batch index of x without a row in x_glob sees the zero vector; a batch index that occurs twice in
+    x_glob raises ValueError.  A pending BatchNorm / ReLU is materialised first."""
+    MODE = None
+
+    def forward(self, x: SparseTensor, x_glob: SparseTensor):
+        cx, cg = x._F.size(1), x_glob._F.size(1)
+        if self.MODE in (0, 1) and cx != cg:
+            raise ValueError(f"{type(self).__name__}: channel counts {cx} and {cg} differ")
+        grow, red = x.coordinate_manager.broadcast_map(x.tensor_stride, x_glob.coordinate_manager, x_glob.tensor_stride)
+        if not hasattr(get_backend(), "broadcast"):
+            raise NotImplementedError(f"{type(self).__name__} needs the HIP backend (ms3d_broadcast_forward)")
+        y = Fn.broadcast(self.MODE, None if self.MODE == 3 else x._raw(), x_glob._raw(), grow, red)
+        return x._like(y)
+
+
+class MinkowskiBroadcastAddition(_BroadcastBase):
+    MODE = 0
+
+
+class MinkowskiBroadcastMultiplication(_BroadcastBase):
+    MODE = 1
+
+
+class MinkowskiBroadcastConcatenation(_BroadcastBase):
+    """[V, C + Cg]: x's channels in front"""
+    MODE = 2
+
+
+class MinkowskiBroadcast(_BroadcastBase):
+    """[V, Cg]: the global row of every voxel's batch index, on x's coordinates"""
+    MODE = 3

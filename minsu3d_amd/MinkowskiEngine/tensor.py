@@ -113,6 +113,77 @@ class CoordinateManager:
             gen = cache[key] = (CoordinateManager.rooted(out, out_ts), nbr_fwd, nbr_bwd, vin, vout, K, out_ts)
         return gen
 
+    def visible_coords(self, ts):
+        """the coordinates of tensor stride ts in the order the CALLER sees them (x.coordinates)"""
+        if ts == 1 and self.inv is not None:
+            return self.coords_external
+        return self.coords[ts]
+
+    def union(self, ts, others):
+        """the union of this manager's coordinate set of tensor stride ts with the sets of the same stride of the managers
+        `others` (at most 15) -> (manager rooted at ts on the union set, in_rows int32 [N, n]: union row -> row of operand i or
+        -1, out_rows: per operand int32 [V_i] row -> union row, n); operand 0 is this manager.  The set is in first-occurrence
+        order of the rows the caller sees (x.coordinates): this set's rows, then the rows of others[0] it lacks, and so on
+        (backend.coords_union).  The maps name rows as the operands HOLD them: on a Morton-sorted manager at stride 1 the
+        engine's permutation is composed into them, so the feature kernels gather straight from the held rows.  Built once per
+        (ts, others) and kept on this manager together with the other managers (their ids cannot be reused while the entry
+        lives): a + b and a * b share one output manager."""
+        mans = [self] + list(others)
+        if len(mans) > 16:
+            raise NotImplementedError(f"a union of {len(mans)} coordinate sets: at most 16")
+        cache = self.__dict__.setdefault("_unions", {})
+        key = (ts,) + tuple(id(m) for m in others)
+        hit = cache.get(key)
+        if hit is None:
+            be = get_backend()
+            if not hasattr(be, "coords_union"):
+                raise NotImplementedError("arithmetic across coordinate sets needs the HIP backend (ms3d_coords_union)")
+            out, out_rows, in_rows = be.coords_union([m.visible_coords(ts) for m in mans])
+            n = out.size(0)
+            if ts == 1 and any(m.inv is not None for m in mans):
+                in_rows, out_rows = in_rows.clone(), list(out_rows)
+                for i, m in enumerate(mans):
+                    if m.inv is not None and m.size(1) > 0:
+                        if n > 0:
+                            r = in_rows[i].long()
+                            in_rows[i] = torch.where(r >= 0, m.inv[r.clamp(min=0)], r).to(torch.int32)
+                        out_rows[i] = out_rows[i][m.perm]
+            out_rows = [r.contiguous() for r in out_rows]
+            hit = cache[key] = (CoordinateManager.rooted(out, ts), in_rows.contiguous(), out_rows, n, tuple(others))
+        return hit[:4]
+
+    def broadcast_map(self, ts, gcm, gts):
+        """what broadcasting one row per batch index (the set of tensor stride gts of the manager gcm: what a global pooling
+        returns; only its batch column is read) onto this manager's set of tensor stride ts needs -> (grow int32 [V]: per held
+        row the held row of the global tensor that carries its batch index, or -1 -- such a voxel sees the zero vector; (order,
+        seg_start, seg_of_g): batch_rows' grouping and the segment of every global row, the summation order of the global
+        operand's gradient).  A batch index that occurs twice in the global set raises ValueError.  Built once per pair (two
+        small host reads) and kept with gcm."""
+        cache = self.__dict__.setdefault("_broadcasts", {})
+        key = (ts, id(gcm), gts)
+        hit = cache.get(key)
+        if hit is None:
+            gb = gcm.__dict__.setdefault("_batch_index", {}).get(gts)
+            if gb is None:
+                gb = gcm.coords[gts][:, 0].cpu().numpy()
+                if len(np.unique(gb)) != len(gb):
+                    gb = ValueError("broadcast: a batch index occurs twice in the global tensor (batch indices "
+                                    f"{gb.tolist()}); it must hold one row per batch index")
+                gcm._batch_index[gts] = gb
+            if isinstance(gb, ValueError):
+                raise gb
+            order, _, offsets, _ = self.batch_rows(ts)
+            dev = self.coords[ts].device
+            first = order[offsets[:-1].long()] if order.numel() else order[:0]
+            present = self.coords[ts][first, 0].cpu().numpy()          # batch index of every segment, ascending
+            seg = {int(b): s for s, b in enumerate(present)}
+            seg_of_g = torch.tensor([seg.get(int(b), -1) for b in gb], dtype=torch.int32, device=dev)
+            lut = torch.full((int(max([-1] + gb.tolist() + present.tolist())) + 2,), -1, dtype=torch.int32, device=dev)
+            lut[torch.as_tensor(gb, device=dev).long()] = torch.arange(len(gb), dtype=torch.int32, device=dev)
+            grow = lut[self.coords[ts][:, 0].long()].contiguous()
+            hit = cache[key] = (grow, (order.contiguous(), offsets.contiguous(), seg_of_g), gcm)
+        return hit[:2]
+
     def kernel_map(self, ts, kernel_size, stride=1, dilation=1):
         """-> (nbr_fwd [K, Vout], nbr_bwd [K, Vin], Vin, Vout, K, output tensor stride, mirror) for a layer from the
         coordinate set of tensor stride ts; built once per key.  (3, 1, 1), (2, 2, 1) and (1, 1, *) are the tables of
@@ -417,13 +488,74 @@ class SparseTensor:
         return Fn.gather_rows(padded, torch.where(rows < 0, torch.full_like(rows, feats.size(0)), rows))
 
     def __iadd__(self, other):      # `x += identity` (common.py:48)
-        self._F = self._raw() + other._raw()
+        if not isinstance(other, SparseTensor):
+            self._F = self._dense_op(other, torch.add)
+        elif other.coordinate_manager is not self.coordinate_manager or other.tensor_stride != self.tensor_stride:
+            raise ValueError("+= across two coordinate sets: an in-place operation cannot change the set of its left operand "
+                             "(write a = a + b)")
+        else:
+            self._F = self._raw() + other._raw()
         self._stats = None
         self._F_ext = None
         return self
 
     def __add__(self, other):
+        if not isinstance(other, SparseTensor):
+            return self._like(self._dense_op(other, torch.add))
+        if other.coordinate_manager is not self.coordinate_manager or other.tensor_stride != self.tensor_stride:
+            return union_op(0, self, other)
         return self._like(self._raw() + other._raw())
+
+    def __sub__(self, other):
+        if not isinstance(other, SparseTensor):
+            return self._like(self._dense_op(other, torch.sub))
+        if other.coordinate_manager is not self.coordinate_manager or other.tensor_stride != self.tensor_stride:
+            return union_op(1, self, other)
+        return self._like(self._raw() - other._raw())
+
+    def __mul__(self, other):
+        if not isinstance(other, SparseTensor):
+            return self._like(self._dense_op(other, torch.mul))
+        if other.coordinate_manager is not self.coordinate_manager or other.tensor_stride != self.tensor_stride:
+            return union_op(2, self, other)
+        return self._like(self._raw() * other._raw())
+
+    __radd__ = __add__      # scalar + tensor, scalar * tensor (a SparseTensor on the left is handled by its own method)
+    __rmul__ = __mul__
+
+    def _dense_op(self, other, fn):
+        """fn(rows, other) for a Python scalar or a torch.Tensor broadcastable to [V, C].  A tensor with one row per voxel is
+        in the CALLER's row order (that of .features) and is permuted into the engine's where one is held."""
+        rows = self._raw()
+        if torch.is_tensor(other):
+            if other.dim() > 2 or (other.dim() == 2 and other.size(0) not in (1, rows.size(0))):
+                raise ValueError(f"a tensor operand must broadcast to the rows [{rows.size(0)}, {rows.size(1)}], got "
+                                 f"{list(other.shape)}")
+            other = other.to(rows.device)
+            perm = self.coordinate_manager.perm if self.tensor_stride == 1 else None
+            if perm is not None and other.dim() == 2 and other.size(0) == rows.size(0) and rows.size(0) > 1:
+                other = other[perm]
+        elif not isinstance(other, (int, float)):
+            raise TypeError(f"unsupported operand for a SparseTensor: {type(other).__name__}")
+        return fn(rows, other)
+
+
+def union_op(op, *tensors):
+    """op 0 sum (up to 16 operands), 1 subtract, 2 multiply (two) of SparseTensors on DIFFERENT coordinate sets of one tensor
+    stride: the result lives on the union of the sets (CoordinateManager.union); where an operand lacks a coordinate the rule
+    of csrc/setops.hip holds.  A pending BatchNorm / ReLU is materialised first."""
+    first = tensors[0]
+    ts, c = first.tensor_stride, first._F.size(1)
+    for t in tensors[1:]:
+        if t.tensor_stride != ts:
+            raise ValueError(f"tensor strides {ts} and {t.tensor_stride} differ: operands of a union live on one tensor stride")
+        if t._F.size(1) != c:
+            raise ValueError(f"channel counts {c} and {t._F.size(1)} differ")
+    if len(tensors) > 16:
+        raise NotImplementedError(f"a union of {len(tensors)} tensors: at most 16")
+    cm, in_rows, out_rows, n = first.coordinate_manager.union(ts, [t.coordinate_manager for t in tensors[1:]])
+    y = Fn.union_combine(op, in_rows, out_rows, n, [t._raw() for t in tensors])
+    return SparseTensor(y, coordinate_manager=cm, tensor_stride=ts)
 
 
 def cat(*tensors):

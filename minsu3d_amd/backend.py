@@ -920,6 +920,109 @@ class _HipEngine:
             return out[:V], src[:V], dst
         return out[:n.value].clone(), src[:n.value].clone(), dst
 
+    # ---- arithmetic across coordinate sets (csrc/coords.hip: union; csrc/setops.hip: the feature kernels)
+    UNION_MAX_SETS = 16
+
+    def coords_union(self, sets):
+        """sets: 1..16 int32 [V_i, 4] coordinate sets of one tensor stride -> (out int32 [n, 4]: the distinct coordinates in
+        first-occurrence order of the concatenation, out_rows: per set int32 [V_i] input row -> union row, in_row int32 [N, n]:
+        union row -> row of set i or -1).  A row that repeats inside one set or lies outside the packable range raises
+        HipLibraryError (MS3D_E_UNSUPPORTED).  One host sync."""
+        sets = [self._dev(c) for c in sets]
+        n_sets = len(sets)
+        if not 1 <= n_sets <= self.UNION_MAX_SETS:
+            _lib.check(_lib.E_UNSUPPORTED, f"ms3d_coords_union ({n_sets} sets: 1 to {self.UNION_MAX_SETS})")
+        for c in sets:
+            assert c.dtype == torch.int32 and c.dim() == 2 and c.size(1) == 4
+        dev = sets[0].device
+        sizes = [c.size(0) for c in sets]
+        start = np.zeros(n_sets + 1, np.int32)
+        start[1:] = np.cumsum(sizes)
+        total = int(start[-1])
+        if total == 0:
+            return (torch.empty((0, 4), dtype=torch.int32, device=dev),
+                    [torch.empty(0, dtype=torch.int32, device=dev) for _ in sets],
+                    torch.empty((n_sets, 0), dtype=torch.int32, device=dev))
+        allc = sets[0] if n_sets == 1 else torch.cat(sets)
+        out = torch.empty((total, 4), dtype=torch.int32, device=dev)
+        out_row = torch.empty(total, dtype=torch.int32, device=dev)
+        in_row = torch.empty(n_sets * total, dtype=torch.int32, device=dev)
+        ws = torch.empty(self.lib.ms3d_coords_union_workspace_bytes(total) + 256, dtype=torch.uint8, device=dev)
+        n = C.c_int(0)
+        _lib.check(self.lib.ms3d_coords_union(_lib.ptr(allc), start.ctypes.data_as(C.c_void_p), n_sets, _lib.ptr(out),
+                                              _lib.ptr(out_row), _lib.ptr(in_row), C.byref(n), _lib.ptr(ws),
+                                              C.c_size_t(ws.numel()), _lib.stream_handle()), "ms3d_coords_union")
+        nu = n.value
+        out = out if nu == total else out[:nu].clone()
+        in_row = in_row[:n_sets * nu].view(n_sets, nu)
+        if n_sets > 1:
+            in_row = in_row.clone()      # (a slice would keep all N * total ints alive)
+        return out, [out_row[int(start[i]):int(start[i + 1])] for i in range(n_sets)], in_row
+
+    def union_combine(self, op, feats, in_row, n_out):
+        """op 0 sum (any N), 1 subtract, 2 multiply (N = 2) of the float32 [V_i, C] rows `feats` gathered through in_row
+        [N, n_out] in ascending input order -> [n_out, C]"""
+        feats = [self._dev(f).contiguous() for f in feats]
+        c, dev = feats[0].size(1), feats[0].device
+        assert all(f.dtype == torch.float32 and f.dim() == 2 and f.size(1) == c for f in feats)
+        assert in_row.dtype == torch.int32 and in_row.is_contiguous() and tuple(in_row.shape) == (len(feats), n_out)
+        out = torch.empty((n_out, c), dtype=torch.float32, device=dev)
+        ptrs = (C.c_void_p * len(feats))(*[f.data_ptr() for f in feats])
+        _lib.check(self.lib.ms3d_union_combine(int(op), ptrs, len(feats), _lib.ptr(in_row), int(n_out), int(c), _lib.ptr(out),
+                                               _lib.stream_handle()), "ms3d_union_combine")
+        return out
+
+    def union_combine_backward(self, op, which, dout, out_row, other=None, other_row=None):
+        """gradient of operand `which`: dout[out_row] (negated / scaled by other[other_row[.]], see ms3d_union_combine)"""
+        dout = self._dev(dout).contiguous()
+        v, c = out_row.numel(), dout.size(1)
+        assert out_row.dtype == torch.int32 and out_row.is_contiguous()
+        if other is not None:
+            other = other.contiguous()
+            assert other.dtype == torch.float32 and other.size(1) == c and other_row.dtype == torch.int32
+            assert other_row.is_contiguous() and other_row.numel() == dout.size(0)
+        din = torch.empty((v, c), dtype=torch.float32, device=dout.device)
+        _lib.check(self.lib.ms3d_union_combine_backward(int(op), int(which), _lib.ptr(dout), _lib.ptr(out_row), int(v),
+                                                        _lib.ptr(other), _lib.ptr(other_row), int(c), _lib.ptr(din),
+                                                        _lib.stream_handle()), "ms3d_union_combine_backward")
+        return din
+
+    def broadcast(self, mode, x, g, grow):
+        """mode 0 add, 1 multiply, 2 concatenate, 3 copy: out[r] = x[r] (mode) g[grow[r]]; grow int32 [V], -1 = the zero
+        vector.  x may be None for copy."""
+        g = self._dev(g).contiguous()
+        assert g.dtype == torch.float32 and g.dim() == 2 and grow.dtype == torch.int32 and grow.is_contiguous()
+        v, cg = grow.numel(), g.size(1)
+        c = 0
+        if mode != 3:
+            x = self._dev(x).contiguous()
+            assert x.dtype == torch.float32 and x.dim() == 2 and x.size(0) == v
+            c = x.size(1)
+        else:
+            x = None
+        out = torch.empty((v, c + cg if mode == 2 else cg), dtype=torch.float32, device=g.device)
+        _lib.check(self.lib.ms3d_broadcast_forward(int(mode), _lib.ptr(x), _lib.ptr(g), _lib.ptr(grow), int(v), int(c), int(cg),
+                                                   _lib.ptr(out), _lib.stream_handle()), "ms3d_broadcast_forward")
+        return out
+
+    def broadcast_reduce(self, dout, col_off, c, x, order, seg_start, seg_of_g):
+        """dg [G, c] = per global row the sum over its batch's rows of dout[:, col_off : col_off + c] (* x when given), in a
+        fixed order; dout is read in place through its leading dimension"""
+        dout = self._dev(dout).contiguous()
+        assert dout.dtype == torch.float32 and dout.dim() == 2 and order.dtype == torch.int64 and order.is_contiguous()
+        assert seg_start.dtype == torch.int32 and seg_of_g.dtype == torch.int32 and order.numel() == dout.size(0)
+        if x is not None:
+            x = x.contiguous()
+            assert x.dtype == torch.float32 and tuple(x.shape) == (dout.size(0), c)
+        G = seg_of_g.numel()
+        dg = torch.empty((G, c), dtype=torch.float32, device=dout.device)
+        ws = self.ws.get("bcast_reduce", self.lib.ms3d_broadcast_reduce_workspace_bytes(G, int(c)), dout.device)
+        _lib.check(self.lib.ms3d_broadcast_reduce(_lib.ptr(dout), int(dout.size(1)), int(col_off), _lib.ptr(x), int(c),
+                                                  _lib.ptr(order), _lib.ptr(seg_start), _lib.ptr(seg_of_g), int(G), _lib.ptr(dg),
+                                                  _lib.ptr(ws), C.c_size_t(ws.numel()), _lib.stream_handle()),
+                   "ms3d_broadcast_reduce")
+        return dg
+
     def scatter_rows(self, src, idx, n_rows):
         """dst [n_rows, C] = 0; dst[idx[i]] = src[i] for an int64 index without repeats (plain stores, one writer per row)"""
         src = self._dev(src); idx = self._dev(idx)

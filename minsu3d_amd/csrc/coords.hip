@@ -338,6 +338,51 @@ __global__ __launch_bounds__(256) void prune_emit_kernel(int V, const int *__res
     }
 }
 
+// ------------------------------------------------------------------ union of coordinate sets
+// The sets lie back to back in one array; set_start (by value, N <= 16) names their first rows.  Row r of the concatenation
+// belongs to the last set whose start is <= r (empty sets share a start with their successor and own nothing).
+constexpr int UNION_MAX_SETS = 16;
+struct UnionSets {
+    int n;
+    int start[UNION_MAX_SETS + 1];
+};
+__device__ __forceinline__ int union_set_of(const UnionSets &s, int r)
+{
+    int i = 0;
+#pragma unroll
+    for (int j = 1; j < UNION_MAX_SETS; j++) i += (j < s.n && s.start[j] <= r) ? 1 : 0;
+    return i;
+}
+// first-occurrence flag per row.  Every slot keeps one bit per set (N <= 16): the row that finds its set's bit already raised
+// repeats a coordinate of its own set -- whichever set won the slot.
+__global__ __launch_bounds__(256) void union_flag_kernel(int n, UnionSets sets, const int *__restrict__ slot_of_row,
+                                                         const int *__restrict__ vals, int *__restrict__ seen,
+                                                         int *__restrict__ flag, int *__restrict__ dup_flag)
+{
+    const int r = blockIdx.x * blockDim.x + threadIdx.x;
+    if (r >= n) return;
+    const int slot = slot_of_row[r];
+    flag[r] = (vals[slot] == r) ? 1 : 0;
+    const int bit = 1 << union_set_of(sets, r);
+    if ((atomicOr(&seen[slot], bit) & bit) && *dup_flag == 0) atomicOr(dup_flag, 1);
+}
+// out_row[r] = union row of input row r; in_row[i][u] = row of set i at union row u (plain stores: rows are distinct inside
+// a set, so (i, u) has one writer); the first occurrence also writes the coordinate
+__global__ __launch_bounds__(256) void union_emit_kernel(int n, int n_out, UnionSets sets, const int *__restrict__ coords,
+                                                         const int *__restrict__ slot_of_row, const int *__restrict__ vals,
+                                                         const int *__restrict__ rank, int *__restrict__ out_coords,
+                                                         int *__restrict__ out_row, int *__restrict__ in_row)
+{
+    const int r = blockIdx.x * blockDim.x + threadIdx.x;
+    if (r >= n) return;
+    const int rep = vals[slot_of_row[r]];
+    const int u = rank[rep];                                   // < n_out: rank counts the first occurrences in front of rep
+    const int i = union_set_of(sets, r);
+    out_row[r] = u;
+    in_row[(size_t)i * n_out + u] = r - sets.start[i];
+    if (rep == r) reinterpret_cast<int4 *>(out_coords)[u] = reinterpret_cast<const int4 *>(coords)[r];
+}
+
 // 64-bit spatial sort key: batch index, then the 45-bit Morton code of the biased (x,y,z)
 __device__ __forceinline__ unsigned long long spread3(unsigned v)
 {
@@ -413,6 +458,17 @@ int rank_first(CoordWs &w, int n, int *count_host, hipStream_t stream)
         if (h[1]) return MS3D_E_UNSUPPORTED;
     }
     return 0;
+}
+
+
+constexpr int UNION_MAX_ROWS = 0x3fffffff;      // the table of >= 2 n slots is indexed by ints
+size_t carve_union(CoordWs &w, int **seen, int **dup_flag, int n, void *base)
+{
+    size_t off = carve(w, n, base);
+    *seen = base ? (int *)((char *)base + off) : nullptr;      // one int per slot: the sets that hold the slot's coordinate
+    off += ms3d_align(sizeof(int) * (size_t)w.H);
+    *dup_flag = base ? (int *)((char *)base + off) : nullptr;
+    return off + ms3d_align(sizeof(int));
 }
 
 // ------------------------------------------------------------------ pair lists (tile-compacted kernel maps)
@@ -774,6 +830,55 @@ int ms3d_coords_prune(const int *coords, int V, const unsigned char *keep, int *
     prune_emit_kernel<<<grid, 256, 0, stream>>>(V, coords, keep, w.rank, out_coords, src_row, dst_row);
     MS3D_LAUNCH_CHECK();
     MS3D_CHECK(hipStreamSynchronize(stream));
+    return 0;
+}
+
+size_t ms3d_coords_union_workspace_bytes(int total_rows)
+{
+    if (total_rows > UNION_MAX_ROWS) return 0;
+    CoordWs w;
+    int *seen, *dup;
+    return carve_union(w, &seen, &dup, total_rows > 0 ? total_rows : 1, nullptr);
+}
+
+int ms3d_coords_union(const int *coords, const int *set_start, int n_sets, int *out_coords, int *out_row, int *in_row,
+                      int *n_out, void *workspace, size_t workspace_bytes, ms3d_stream_t stream_)
+{
+    hipStream_t stream = (hipStream_t)stream_;
+    *n_out = 0;
+    if (n_sets < 1 || n_sets > UNION_MAX_SETS || !set_start) return MS3D_E_UNSUPPORTED;
+    UnionSets sets;
+    sets.n = n_sets;
+    for (int i = 0; i <= UNION_MAX_SETS; i++) sets.start[i] = set_start[i <= n_sets ? i : n_sets];
+    if (sets.start[0] != 0) return MS3D_E_UNSUPPORTED;
+    for (int i = 0; i < n_sets; i++)
+        if (sets.start[i + 1] < sets.start[i]) return MS3D_E_UNSUPPORTED;
+    const int n = sets.start[n_sets];
+    if (n > UNION_MAX_ROWS) return MS3D_E_UNSUPPORTED;
+    if (n == 0) return 0;                                      // every set is empty: the empty set, nothing is launched
+    CoordWs w;
+    int *seen, *dup;
+    if (carve_union(w, &seen, &dup, n, workspace) > workspace_bytes) return MS3D_E_WORKSPACE;
+    MS3D_CHECK(hipMemsetAsync(seen, 0, sizeof(int) * (size_t)w.H, stream));
+    MS3D_CHECK(hipMemsetAsync(dup, 0, sizeof(int), stream));
+    int rc = build_table(w, coords, n, 1, stream);
+    if (rc) return rc;
+    union_flag_kernel<<<ms3d_divup(n, 256), 256, 0, stream>>>(n, sets, w.slot_of_row, w.vals, seen, w.flag, dup);
+    MS3D_LAUNCH_CHECK();
+    rc = ms3d_exclusive_scan_i32(w.flag, w.rank, n, w.total, w.scan_ws, stream);
+    if (rc) return rc;
+    int h[3] = {0, 0, 0};   // [0] distinct coordinates  [1] a row did not fit the key  [2] a row repeats inside its set
+    MS3D_CHECK(hipMemcpyAsync(h, w.total, sizeof(int) * 2, hipMemcpyDeviceToHost, stream));
+    MS3D_CHECK(hipMemcpyAsync(h + 2, dup, sizeof(int), hipMemcpyDeviceToHost, stream));
+    MS3D_CHECK(hipStreamSynchronize(stream));
+    if (h[1] || h[2]) return MS3D_E_UNSUPPORTED;
+    *n_out = h[0];
+    const long cells = (long)n_sets * h[0];
+    fill_minus1_kernel<<<ms3d_divup(cells, 256), 256, 0, stream>>>(in_row, cells);
+    MS3D_LAUNCH_CHECK();
+    union_emit_kernel<<<ms3d_divup(n, 256), 256, 0, stream>>>(n, h[0], sets, coords, w.slot_of_row, w.vals, w.rank, out_coords,
+                                                            out_row, in_row);
+    MS3D_LAUNCH_CHECK();
     return 0;
 }
 
