@@ -388,8 +388,25 @@ int ms3d_bn_finalize(const float *partial, int nparts, long V, int C, float eps,
 /* dW[k] = sum_i act(in[nbr[k][i],:])^T dout[i,:].  Deterministic: per-row-chunk partial slabs reduced in a fixed
  * order.  partial_ws MUST hold ms3d_spconv_wgrad_ws_floats(Vout, K, Cin, Cout) floats: the slab count depends on the
  * kernel that serves the shape (K = 1 heads: up to 1024 slabs; bf16x3 layers: the operand images behind the slabs).
- * ms3d_spconv_wgrad_row_chunks(Vout) * K*Cin*Cout is only a LOWER bound (the f32 table walk's slab count). */
+ * ms3d_spconv_wgrad_row_chunks(Vout) is the row count's share of that decision only: a route may take fewer slabs or
+ * more (the two-chunk list kernel: 128 parts from 65 row chunks on) -- size nothing from it. */
 int ms3d_spconv_wgrad_row_chunks(int Vout);
+/* Backward-weight workspace.  Every workgroup along the rows leaves one partial dW slab of n = K*Cin*Cout floats at
+ * partial_ws + slab * n; the slabs are then summed in slab order.  Layout of partial_ws, in floats:
+ *   [0, ms3d_spconv_wgrad_slab_floats)     the slabs; a call writes the first ms3d_spconv_wgrad_slabs() * n of them
+ *   [slab_floats, slab_floats + 64)        alignment slack
+ *   only when ms3d_spconv_wgrad_is_bf16x3_g(Vout, K, Cin, Cout, 0, 1), from the next 16-byte boundary behind slab_floats:
+ *     divup(Vout, 32) * divup(Cout, 16) * P * 64 * 4 + 8    the dout operand image (P = 3 - precision bf16 pieces)
+ *     Vout * Cin * P / 2 + 8                                the activated input in P bf16 pieces
+ * ms3d_spconv_wgrad_ws_floats_p is the sum of these, ms3d_spconv_wgrad_ws_floats its precision-0 value.
+ * ms3d_spconv_wgrad_slabs: the slabs a call of this shape leaves (offset_list: an offset list is passed; submanifold: as
+ * the *_g entry points take it, 1 for the entry points without the flag); 0 for Vout <= 0, MS3D_E_UNSUPPORTED where the
+ * launch returns it.  With wgrad_deferred_nblk this is the value the layer entry point reports.
+ * ms3d_spconv_wgrad_slab_floats: the largest slab count over offset_list 0 / 1 and submanifold 0 / 1, times n.
+ * The launch and these queries read ONE plan, so the chunk knobs (MS3D_WGRAD_*_CHUNKS, MS3D_WGRAD_*_ROUNDS) may be
+ * raised above their defaults without outgrowing the workspace: the sizes follow. */
+int ms3d_spconv_wgrad_slabs(int Vout, int K, int Cin, int Cout, int offset_list, int submanifold, int precision);
+size_t ms3d_spconv_wgrad_slab_floats(int Vout, int K, int Cin, int Cout);
 /* floats of partial_ws a backward-weight call may use (slabs; wide K = 27 layers add the three-piece bf16 images of both
  * operands).  K = 27 is the SUBMANIFOLD case: `in` and `dout` have the same Vout rows -- a 27-offset table whose input row
  * set differs from its output row set is outside this entry point's contract (the bf16x3 path splits Vout rows of `in`). */

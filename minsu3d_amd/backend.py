@@ -699,6 +699,7 @@ class WgradQueue:
         self.timer = timer
 
     def add(self, slabs, dW, n, nblk):
+        assert int(nblk) * int(n) <= slabs.numel(), "more slabs to reduce than the slab tensor holds"
         self.items.append((slabs, dW, int(n), int(nblk)))
 
     def add_launch(self, desc, keep, timing=None):

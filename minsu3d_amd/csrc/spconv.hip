@@ -4000,18 +4000,6 @@ static bool wgrad_bf3_ok(int Vout, int K, int Cin, int Cout, bool use_list, bool
     return bf3_enabled() && wg && !use_list && K == 27 && nb >= 3 && nb <= 8 && Cin >= 48 && Cin <= 256 && Cin % 16 == 0 &&
            Cout % 16 == 0;
 }
-int ms3d_spconv_wgrad_is_bf16x3(int Vout, int K, int Cin, int Cout, int offset_list) { return wgrad_bf3_ok(Vout, K, Cin, Cout, offset_list != 0) ? 1 : 0; }
-int ms3d_spconv_wgrad_is_bf16x3_g(int Vout, int K, int Cin, int Cout, int offset_list, int submanifold)
-{
-    return wgrad_bf3_ok(Vout, K, Cin, Cout, offset_list != 0, submanifold != 0) ? 1 : 0;
-}
-// 1 when a backward-weight call of this shape takes the f32 table walk -- the kernel ms3d_spconv_layer_backward can leave
-// to a batched launch (offset_list: an offset list of the table is passed)
-int ms3d_spconv_wgrad_is_table_walk(int Vout, int K, int Cin, int Cout, int offset_list)
-{
-    const bool use_list = offset_list && wgrad_list_cols_ok(K, ms3d_divup(Cout, 16)) && K <= 27 && Cin % 16 == 0 && Cout % 16 == 0;
-    return (Vout > 0 && !use_list && !wgrad_bf3_ok(Vout, K, Cin, Cout, use_list) && ms3d_divup(Cout, 16) <= 14) ? 1 : 0;
-}
 // K = 1 with a small weight (the per-point Linear layers of the heads: 575k rows x 16 -> 16 / 20 / 3): the table walk's
 // grid is (row chunks) x 1 x Cin / 16, so 256 chunks are ONE workgroup per CU walking 2200 rows each in dependent trips of 32
 // (107 us per launch); the slabs are a few hundred floats, so the rows are cut 4x finer instead (measured below)
@@ -4032,23 +4020,6 @@ int ms3d_spconv_wgrad_pieces(int Vout, int K, int Cin, int Cout, int offset_list
     return ms3d_spconv_wgrad_is_bf16x3(Vout, K, Cin, Cout, offset_list) ? 3 - precision : 0;
 }
 
-// slabs + (bf16 kernel) the dout operand image and the activated input pieces; 0 for a precision outside 0..2.
-// Fewer pieces need less: the precision-0 size is an upper bound for every precision.
-size_t ms3d_spconv_wgrad_ws_floats_p(int Vout, int K, int Cin, int Cout, int precision)
-{
-    if (precision < 0 || precision > 2) return 0;
-    const int k1 = wgrad_k1_chunks(Vout, K, Cin, Cout), rc = ms3d_spconv_wgrad_row_chunks(Vout);
-    size_t n = (size_t)(k1 > rc ? k1 : rc) * K * Cin * Cout + 64;
-    if (wgrad_bf3_ok(Vout, K, Cin, Cout, false)) {
-        const int P = 3 - precision;
-        n += (size_t)ms3d_divup(Vout, 32) * ms3d_divup(Cout, 16) * P * 64 * 4 + 8;        // dout image, 16 B units
-        n += (size_t)Vout * Cin * P / 2 + 8;                                                 // 2P B per input element
-    }
-    return n;
-}
-
-size_t ms3d_spconv_wgrad_ws_floats(int Vout, int K, int Cin, int Cout) { return ms3d_spconv_wgrad_ws_floats_p(Vout, K, Cin, Cout, 0); }
-
 int ms3d_spconv_wgrad_row_chunks(int Vout)
 {
     // ~1024+ waves in flight at full resolution, at most 256 partial slabs (the slab reduction reads chunks * |dW|)
@@ -4059,6 +4030,155 @@ int ms3d_spconv_wgrad_row_chunks(int Vout)
     int chunks = ms3d_divup(Vout, 256);
     if (chunks > max_chunks) chunks = max_chunks;
     return chunks < 1 ? 1 : chunks;
+}
+
+// ---------------------------------------------------------------------------------------------------------
+// The backward-weight PLAN: which kernel serves a call and how many workgroups along the rows it gets.  Every workgroup
+// along the rows leaves one partial dW slab of K*Cin*Cout floats in the caller's workspace, so this count is also what
+// the workspace must hold: the launch (spconv_backward_weight_impl) and the size queries (ms3d_spconv_wgrad_slabs,
+// ms3d_spconv_wgrad_slab_floats, ms3d_spconv_wgrad_ws_floats_p) all read it here and nowhere else.
+// ---------------------------------------------------------------------------------------------------------
+enum WgradRoute { WGRAD_LIST = 1, WGRAD_BF16 = 2, WGRAD_TABLE = 3 };
+struct WgradPlan {
+    int route;            // WgradRoute
+    int nblk;             // workgroups along the rows = slabs left in partial_ws
+    int rows_per_block;   // table walk / bf16 kernel: rows of a workgroup; list kernel: the merge shift of the list's parts
+    bool wide2;           // list kernel: two input chunks per workgroup on 64 output columns
+};
+
+// have_list: the caller passes an offset list of the table.  0, or MS3D_E_UNSUPPORTED where no kernel serves the shape.
+static int wgrad_plan(int Vout, int K, int Cin, int Cout, bool have_list, bool submanifold, int precision, WgradPlan &pl)
+{
+    if (precision < 0 || precision > 2) return MS3D_E_UNSUPPORTED;
+    const long n = (long)K * Cin * Cout;
+    const int nb = ms3d_divup(Cout, 16);
+    int chunks = ms3d_spconv_wgrad_row_chunks(Vout);
+    // wide layers: the slab reduction reads chunks x |dW| (64 -> 64: 256 x 442 KB = 113 MB per launch, as much as the
+    // gathers); half the slabs still leave every CU several workgroups (K / KG x Cin / 16 of them per chunk)
+    static const int wide_chunks = [] { const char *e = getenv("MS3D_WGRAD_WIDE_CHUNKS"); return e ? atoi(e) : 128; }();
+    static const int xwide_chunks = [] { const char *e = getenv("MS3D_WGRAD_XWIDE_CHUNKS"); return e ? atoi(e) : 128; }();
+    if (n >= 100000 && chunks > wide_chunks) chunks = wide_chunks;
+    if (n >= 400000 && chunks > xwide_chunks) chunks = xwide_chunks;
+    const bool use_list = have_list && wgrad_list_cols_ok(K, nb) && K <= 27 && Cin % 16 == 0 && Cout % 16 == 0;
+    // offset-list kernel at 48 / 64 input channels: 64 parts x 3-4 input chunks is one workgroup per CU, and half the slabs
+    // (us per launch with 256 / 128 / 64 / 32 parts: 64 -> 64 at 196k rows 396 / 343 / 320 / 589, at 50k 143 / 141 / 122 /
+    // 193, 48 -> 48 at 196k 232 / 231 / 215 / 394; the narrow layers want all 256: 32 -> 32 at 417k 124 / 190 / 321)
+    static const int list_wide_chunks = [] { const char *e = getenv("MS3D_WGRAD_LIST_WIDE_CHUNKS"); return e ? atoi(e) : 64; }();
+    // 64 output channels from 64+ input channels (K = 27; round 6): TWO input chunks per workgroup -- the dout rows (256 B per
+    // pair) are fetched once per two chunks instead of once per chunk, 768 instead of 1280 gathered bytes per pair -- on 128
+    // parts (the grid keeps 256 workgroups), one batch per trip (the second chunk's rows take the registers of the second
+    // batch).  us per launch, one chunk x 64 parts | two chunks x 128 parts: 64 -> 64 at 196k rows 320-328 | 269-271, at 51k
+    // rows 122.6 | 112; 48 -> 48 (three column blocks) does not gain (74.5 | 78 at 51k rows) and keeps one chunk.
+    // MS3D_WGRAD_LIST_NCH2=0: one chunk as before.
+    static const int nch2 = env_int("MS3D_WGRAD_LIST_NCH2", 1);
+    const bool wide2 = nch2 && use_list && K == 27 && nb == 4 && Cin % 32 == 0 && Cin >= 64;
+    // (this line can RAISE the count above the row chunks: 65..127 row chunks become 128 parts under wide2 -- the slab
+    // area follows because it is sized from this function)
+    if (use_list && ms3d_divup(Cin, 16) >= 3 && chunks > list_wide_chunks) chunks = wide2 ? 2 * list_wide_chunks : list_wide_chunks;
+    pl.wide2 = wide2;
+    if (nb > 14) return MS3D_E_UNSUPPORTED;
+    if (use_list) {
+        // workgroups = the list's MS3D_PL_PARTS equal-pair-count parts, merged in pairs until there are <= chunks
+        int shift = 0;
+        while ((MS3D_PL_PARTS >> shift) > chunks) shift++;
+        pl.route = WGRAD_LIST;
+        pl.rows_per_block = shift;  // the list kernel reads this field as the merge shift
+        pl.nblk = MS3D_PL_PARTS >> shift;
+        return 0;
+    }
+    if (!wgrad_bf3_ok(Vout, K, Cin, Cout, false, submanifold)) {
+        // the f32 table walk: no more row chunks than fill the chip once (every chunk costs a slab of |dW|; measured:
+        // 64 -> 96, K = 8, 50k rows 103 -> 86 us, 160 -> 160 at 2.5k rows 76 -> 69; everything else has fewer anyway)
+        static const int rounds = [] { const char *e = getenv("MS3D_WGRAD_F32_ROUNDS"); return e ? atoi(e) : 1; }();
+        const int nbq = nb;
+        const int kg = nbq <= 3 ? (K >= 27 ? 9 : 8) : nbq <= 7 ? 4 : nbq == 8 ? 3 : 2;
+        const int yz = ms3d_divup(K, kg) * ms3d_divup(Cin, 16);
+        if (rounds > 0) {
+            int c = (1024 * rounds) / yz;
+            if (c < 4) c = 4;
+            if (c < chunks) chunks = c;
+        }
+        const int k1 = wgrad_k1_chunks(Vout, K, Cin, Cout);
+        if (k1 > chunks) chunks = k1;
+        pl.route = WGRAD_TABLE;
+        pl.rows_per_block = ms3d_divup(ms3d_divup(Vout, chunks), 16) * 16;
+        pl.nblk = ms3d_divup(Vout, pl.rows_per_block);
+        return 0;
+    }
+    // the bf16 kernel (wide submanifold layers)
+    // Row chunks: two workgroups fit a CU (512 slots).  As many chunks as make the grid two whole rounds of them --
+    // every slab is |dW| floats written and read again by the reduction (128 chunks of 128 -> 128: 450 MB, a third
+    // of the launch), while a grid of 1.1 or 1.5 rounds idles half the chip in its last one.  Measured, us per launch
+    // with 128 / 64 / 32 chunks: 128 -> 128 at 50k rows 367 / 327 / 282, 96 -> 96 at 196k rows 776 / 854 / 1075.
+    {
+        const int kg = nb <= 4 ? (nb == 3 ? 14 : 9) : 9;
+        const int yz = ms3d_divup(K, kg) * ms3d_divup(Cin, 16);
+        static const int rounds = [] { const char *e = getenv("MS3D_WGRAD_BF3_ROUNDS"); return e ? atoi(e) : 2; }();
+        int c = (512 * rounds) / yz;
+        if (c < 8) c = 8;
+        if (c < chunks) chunks = c;
+    }
+    pl.route = WGRAD_BF16;
+    pl.rows_per_block = ms3d_divup(ms3d_divup(Vout, chunks), 32) * 32;
+    pl.nblk = ms3d_divup(Vout, pl.rows_per_block);
+    return 0;
+}
+
+// slabs a backward-weight call of this shape leaves in partial_ws (offset_list: a list is passed; submanifold: as the *_g
+// entry points take it; the entry points without the flag are submanifold = 1); 0 for Vout <= 0 (dW is zeroed, nothing is
+// written), MS3D_E_UNSUPPORTED where the launch returns it
+int ms3d_spconv_wgrad_slabs(int Vout, int K, int Cin, int Cout, int offset_list, int submanifold, int precision)
+{
+    if (precision < 0 || precision > 2) return MS3D_E_UNSUPPORTED;
+    if (Vout <= 0) return 0;
+    WgradPlan pl;
+    const int rc = wgrad_plan(Vout, K, Cin, Cout, offset_list != 0, submanifold != 0, precision, pl);
+    return rc ? rc : pl.nblk;
+}
+
+// the slab area: room for the slabs of every route a call of this shape can take (with or without a list, submanifold or
+// not; the slab count does not depend on the precision)
+size_t ms3d_spconv_wgrad_slab_floats(int Vout, int K, int Cin, int Cout)
+{
+    int most = 0;
+    if (Vout > 0)
+        for (int v = 0; v < 4; v++) {
+            WgradPlan pl;
+            if (wgrad_plan(Vout, K, Cin, Cout, (v & 1) != 0, (v & 2) != 0, 0, pl) == 0 && pl.nblk > most) most = pl.nblk;
+        }
+    return (size_t)most * K * Cin * Cout;
+}
+
+// slabs + (bf16 kernel) the dout operand image and the activated input pieces; 0 for a precision outside 0..2.
+// Fewer pieces need less: the precision-0 size is an upper bound for every precision.
+size_t ms3d_spconv_wgrad_ws_floats_p(int Vout, int K, int Cin, int Cout, int precision)
+{
+    if (precision < 0 || precision > 2) return 0;
+    size_t n = ms3d_spconv_wgrad_slab_floats(Vout, K, Cin, Cout) + 64;
+    if (wgrad_bf3_ok(Vout, K, Cin, Cout, false)) {
+        const int P = 3 - precision;
+        n += (size_t)ms3d_divup(Vout, 32) * ms3d_divup(Cout, 16) * P * 64 * 4 + 8;        // dout image, 16 B units
+        n += (size_t)Vout * Cin * P / 2 + 8;                                                 // 2P B per input element
+    }
+    return n;
+}
+
+size_t ms3d_spconv_wgrad_ws_floats(int Vout, int K, int Cin, int Cout) { return ms3d_spconv_wgrad_ws_floats_p(Vout, K, Cin, Cout, 0); }
+
+// 1 when a backward-weight call of this shape runs on bf16 operand pieces.  (A list that is passed but that the list kernel
+// does not serve -- K = 27 beyond 64 output columns -- does not keep the call off this route: the plan says what runs.)
+int ms3d_spconv_wgrad_is_bf16x3_g(int Vout, int K, int Cin, int Cout, int offset_list, int submanifold)
+{
+    WgradPlan pl;
+    return (Vout > 0 && wgrad_plan(Vout, K, Cin, Cout, offset_list != 0, submanifold != 0, 0, pl) == 0 && pl.route == WGRAD_BF16) ? 1 : 0;
+}
+int ms3d_spconv_wgrad_is_bf16x3(int Vout, int K, int Cin, int Cout, int offset_list) { return ms3d_spconv_wgrad_is_bf16x3_g(Vout, K, Cin, Cout, offset_list, 1); }
+// 1 when a backward-weight call of this shape takes the f32 table walk -- the kernel ms3d_spconv_layer_backward can leave
+// to a batched launch (offset_list: an offset list of the table is passed)
+int ms3d_spconv_wgrad_is_table_walk(int Vout, int K, int Cin, int Cout, int offset_list)
+{
+    WgradPlan pl;
+    return (Vout > 0 && wgrad_plan(Vout, K, Cin, Cout, offset_list != 0, true, 0, pl) == 0 && pl.route == WGRAD_TABLE) ? 1 : 0;
 }
 
 // defer_nblk != NULL: the slab reduction is NOT launched; *defer_nblk = number of slabs left in partial_ws (0: dW is
@@ -4120,57 +4240,14 @@ static int spconv_backward_weight_impl(const float *in, const float *dout, const
     WgradArgs p;
     p.in = in; p.dout = dout; p.nbr = nbr; p.partial = partial_ws; p.pre_scale = pre_scale; p.pre_shift = pre_shift;
     p.Vout = Vout; p.K = K; p.Cin = Cin; p.Cout = Cout; p.NBtot = ms3d_divup(Cout, 16); p.pre_relu = pre_relu;
-    int chunks = ms3d_spconv_wgrad_row_chunks(Vout);
-    // wide layers: the slab reduction reads chunks x |dW| (64 -> 64: 256 x 442 KB = 113 MB per launch, as much as the
-    // gathers); half the slabs still leave every CU several workgroups (K / KG x Cin / 16 of them per chunk)
-    static const int wide_chunks = [] { const char *e = getenv("MS3D_WGRAD_WIDE_CHUNKS"); return e ? atoi(e) : 128; }();
-    static const int xwide_chunks = [] { const char *e = getenv("MS3D_WGRAD_XWIDE_CHUNKS"); return e ? atoi(e) : 128; }();
-    if (n >= 100000 && chunks > wide_chunks) chunks = wide_chunks;
-    if (n >= 400000 && chunks > xwide_chunks) chunks = xwide_chunks;
-    const bool use_list = ol_kt_start && ol_entries && wgrad_list_cols_ok(K, p.NBtot) && K <= 27 && Cin % 16 == 0 && Cout % 16 == 0;
+    WgradPlan plan;
+    int rc = wgrad_plan(Vout, K, Cin, Cout, ol_kt_start && ol_entries, submanifold, precision, plan);
+    if (rc) return rc;
+    const bool use_list = plan.route == WGRAD_LIST, wide2 = plan.wide2;
     p.ol_kt_start = ol_kt_start; p.ol_entries = ol_entries;
-    int nblk;
-    // offset-list kernel at 48 / 64 input channels: 64 parts x 3-4 input chunks is one workgroup per CU, and half the slabs
-    // (us per launch with 256 / 128 / 64 / 32 parts: 64 -> 64 at 196k rows 396 / 343 / 320 / 589, at 50k 143 / 141 / 122 /
-    // 193, 48 -> 48 at 196k 232 / 231 / 215 / 394; the narrow layers want all 256: 32 -> 32 at 417k 124 / 190 / 321)
-    static const int list_wide_chunks = [] { const char *e = getenv("MS3D_WGRAD_LIST_WIDE_CHUNKS"); return e ? atoi(e) : 64; }();
-    // 64 output channels from 64+ input channels (K = 27; round 6): TWO input chunks per workgroup -- the dout rows (256 B per
-    // pair) are fetched once per two chunks instead of once per chunk, 768 instead of 1280 gathered bytes per pair -- on 128
-    // parts (the grid keeps 256 workgroups), one batch per trip (the second chunk's rows take the registers of the second
-    // batch).  us per launch, one chunk x 64 parts | two chunks x 128 parts: 64 -> 64 at 196k rows 320-328 | 269-271, at 51k
-    // rows 122.6 | 112; 48 -> 48 (three column blocks) does not gain (74.5 | 78 at 51k rows) and keeps one chunk.
-    // MS3D_WGRAD_LIST_NCH2=0: one chunk as before.
-    static const int nch2 = env_int("MS3D_WGRAD_LIST_NCH2", 1);
-    const bool wide2 = nch2 && use_list && K == 27 && p.NBtot == 4 && Cin % 32 == 0 && Cin >= 64;
-    if (use_list && ms3d_divup(Cin, 16) >= 3 && chunks > list_wide_chunks) chunks = wide2 ? 2 * list_wide_chunks : list_wide_chunks;
-    if (use_list) {
-        // workgroups = the list's MS3D_PL_PARTS equal-pair-count parts, merged in pairs until there are <= chunks
-        int shift = 0;
-        while ((MS3D_PL_PARTS >> shift) > chunks) shift++;
-        p.rows_per_block = shift;  // the list kernel reads this field as the merge shift
-        nblk = MS3D_PL_PARTS >> shift;
-    } else {
-        if (!wgrad_bf3_ok(Vout, K, Cin, Cout, false, submanifold)) {
-            // the f32 table walk: no more row chunks than fill the chip once (every chunk costs a slab of |dW|; measured:
-            // 64 -> 96, K = 8, 50k rows 103 -> 86 us, 160 -> 160 at 2.5k rows 76 -> 69; everything else has fewer anyway)
-            static const int rounds = [] { const char *e = getenv("MS3D_WGRAD_F32_ROUNDS"); return e ? atoi(e) : 1; }();
-            const int nbq = p.NBtot;
-            const int kg = nbq <= 3 ? (K >= 27 ? 9 : 8) : nbq <= 7 ? 4 : nbq == 8 ? 3 : 2;
-            const int yz = ms3d_divup(K, kg) * ms3d_divup(Cin, 16);
-            if (rounds > 0) {
-                int c = (1024 * rounds) / yz;
-                if (c < 4) c = 4;
-                if (c < chunks) chunks = c;
-            }
-            const int k1 = wgrad_k1_chunks(Vout, K, Cin, Cout);
-            if (k1 > chunks) chunks = k1;
-        }
-        p.rows_per_block = ms3d_divup(ms3d_divup(Vout, chunks), 16) * 16;
-        nblk = ms3d_divup(Vout, p.rows_per_block);
-    }
+    p.rows_per_block = plan.rows_per_block;   // (the list kernel reads this field as the merge shift)
+    int nblk = plan.nblk;
     const int nb = p.NBtot;
-    if (nb > 14) return MS3D_E_UNSUPPORTED;
-    int rc;
     if (use_list) {
         // two input chunks per workgroup when Cin allows (entries and dout rows fetched once for both)
         // more than four column blocks (K = 8 layers of the wide levels, round 5): two or more slices of <= 4 blocks on grid.y
@@ -4186,11 +4263,11 @@ static int spconv_backward_weight_impl(const float *in, const float *dout, const
         MS3D_LAUNCH_CHECK();
         return 0;
     }
-    if (wgrad_bf3_ok(Vout, K, Cin, Cout, use_list, submanifold)) {
+    if (plan.route == WGRAD_BF16) {
         // wide submanifold layers: both operands pre-split into P = 3 (2, 1 at the lower precisions) bf16 pieces by two
         // elementwise passes
         const int P = 3 - precision;
-        float *base = partial_ws + (size_t)ms3d_spconv_wgrad_row_chunks(Vout) * K * Cin * Cout;
+        float *base = partial_ws + ms3d_spconv_wgrad_slab_floats(Vout, K, Cin, Cout);   // the operand area starts behind the slab area
         bf16x8 *img = reinterpret_cast<bf16x8 *>((reinterpret_cast<uintptr_t>(base) + 15) & ~(uintptr_t)15);
         const long ntile = ms3d_divup(Vout, 32);
         bf16x8 *xs = img + (size_t)ntile * nb * P * 64;
@@ -4209,20 +4286,7 @@ static int spconv_backward_weight_impl(const float *in, const float *dout, const
         WgradBf3Args q;
         q.xs = xs; q.dout_img = img; q.nbr = nbr; q.partial = partial_ws; q.Vout = Vout; q.K = K; q.Cin = Cin; q.Cout = Cout;
         q.NBtot = nb;
-        // Row chunks: two workgroups fit a CU (512 slots).  As many chunks as make the grid two whole rounds of them --
-        // every slab is |dW| floats written and read again by the reduction (128 chunks of 128 -> 128: 450 MB, a third
-        // of the launch), while a grid of 1.1 or 1.5 rounds idles half the chip in its last one.  Measured, us per launch
-        // with 128 / 64 / 32 chunks: 128 -> 128 at 50k rows 367 / 327 / 282, 96 -> 96 at 196k rows 776 / 854 / 1075.
-        {
-            const int kg = nb <= 4 ? (nb == 3 ? 14 : 9) : 9;
-            const int yz = ms3d_divup(K, kg) * ms3d_divup(Cin, 16);
-            static const int rounds = [] { const char *e = getenv("MS3D_WGRAD_BF3_ROUNDS"); return e ? atoi(e) : 2; }();
-            int c = (512 * rounds) / yz;
-            if (c < 8) c = 8;
-            if (c < chunks) chunks = c;
-        }
-        q.rows_per_block = ms3d_divup(ms3d_divup(Vout, chunks), 32) * 32;
-        nblk = ms3d_divup(Vout, q.rows_per_block);
+        q.rows_per_block = plan.rows_per_block;
         // waves split the output columns (NW waves x NBW blocks of 16), a workgroup takes KG offsets
         // (KG offsets per workgroup, waves, 16-column blocks per wave): the largest tiles that stay inside 256 registers at
         // two workgroups per CU -- every larger one tried spills (profiles/r03_fwd_experiments.txt section 6)
