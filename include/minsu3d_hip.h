@@ -345,6 +345,30 @@ int ms3d_spconv_prep_weights(const float *W, int K, int Cin_eff, int Cout_eff, i
  * and bn_partial [ms3d_spconv_partial_blocks()][2][Cout] receives per-block sums of dz and dz*xhat. */
 int ms3d_spconv_partial_blocks(int Vout, int K, int Cin, int Cout, int with_pairlist /* 0 = no list; 1 = a 64-row list;
                                otherwise the list's rows per tile (ms3d_kmap_pairlist_rows_of) */);
+/* The forward / backward-data plan, read-only: the kernel family ms3d_spconv_forward (and the layer entry points) launch
+ * for a call of this shape, and its launch geometry.  The launch reads the same plan function and nothing else.
+ *   pl_rows     rows per tile of the pair list the call is given: 0 = none, else 32 / 64 / 128 (1 = 64, as above)
+ *   aux_kind    what the call's aux image holds (ms3d_spconv_aux_kind_p; 0 = none, as ms3d_spconv_forward without wf_stream)
+ *   with_stats  the call writes bn_partial (bn_x != NULL, or out_stats with a bn_partial)
+ *   plan8[0]    family, MS3D_FWD_* below
+ *   plan8[1]    nbt: 16-column blocks per wave        plan8[2]  ny: column slices (gridDim.y; weight-stationary: per row part)
+ *   plan8[3]    gridDim.x as launched                 plan8[4]  threads per block
+ *   plan8[5]    dynamic LDS bytes
+ *   plan8[6]    small families: 16-row tiles per block (1 or 3); pair-list / stream family: 16-row tiles per tile of the
+ *               list (2 or 4 / 8); otherwise 1
+ *   plan8[7]    rows of bn_partial a call with statistics writes = ms3d_spconv_partial_blocks(Vout, K, Cin, Cout, pl_rows)
+ * Returns 0, or MS3D_E_UNSUPPORTED exactly where the launch would (plan8 is then all zero).  Vout <= 0: 0 and an all-zero
+ * plan (nothing is launched). */
+#define MS3D_FWD_WS 1            /* spconv_fwd_ws_kernel: weight-stationary, coarse levels */
+#define MS3D_FWD_SMALL 2         /* spconv_fwd_small_kernel: one block per 16-row tile (or per 3 on the bf16 geometry), f32 */
+#define MS3D_FWD_SMALL_BF3 3     /* spconv_fwd_small_bf3_kernel: the same on the bf16 image, one tile per block */
+#define MS3D_FWD_SMALL_BF3_RT 4  /* spconv_fwd_small_bf3_rt_kernel: three tiles per block on the bf16 image */
+#define MS3D_FWD_PAIRSTREAM 5    /* spconv_fwd_pairstream_kernel: 128-row pair list, weights streamed from L2 */
+#define MS3D_FWD_PAIRLIST 6      /* spconv_fwd_pairlist_kernel: 64-row or 32-row pair list, weights in LDS */
+#define MS3D_FWD_BF3 7           /* spconv_fwd_bf3_kernel: table walk on the bf16 image */
+#define MS3D_FWD_RESIDENT 8      /* spconv_fwd_kernel, all weights LDS resident, persistent waves */
+#define MS3D_FWD_STREAMED 9      /* spconv_fwd_kernel, weights streamed through LDS in offset groups */
+int ms3d_spconv_forward_plan(int Vout, int K, int Cin, int Cout, int pl_rows, int aux_kind, int with_stats, int *plan8);
 /* rows per tile of the pair list a forward / backward-data convolution of this shape wants in pl_tile_start / pl_entries:
  * 0 = none, 64 = ms3d_kmap_pairlist_build, 128 = ms3d_kmap_pairlist_build_rows(.., 128, ..) */
 int ms3d_spconv_pairlist_rows(int Vout, int K, int Cin, int Cout);

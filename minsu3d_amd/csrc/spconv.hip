@@ -1241,12 +1241,7 @@ int launch_fwd_small_bf3(const ConvArgs &p, dim3 grid, int threads, size_t lds, 
 template <int NBT>
 int launch_fwd_small(const ConvArgs &p, dim3 grid, int threads, size_t lds, bool aligned, hipStream_t stream)
 {
-    // The geometry may have been laid out for the bf16x3 three-tile kernel (4 waves x RT x nbt KB of LDS, 72-96+ KB at
-    // >= 96 output channels) while this call has no bf16x3 image (the exact-f32 entry point, a BatchNorm without ReLU,
-    // aux kind 1): this kernel parks (waves - 1) x nbt accumulator tiles + the statistics only -- ask for that, not for
-    // the other kernel's footprint (which would exceed the 64 KB a kernel gets without raising its ceiling)
-    const size_t need = ((size_t)(threads / 64 - 1) * NBT * 256 + ((p.bn_x || p.out_stats) ? stat_slot_floats(NBT) : 0)) * sizeof(float) + 16;
-    if (lds > need) lds = need;
+    // (lds: what THIS kernel parks, whichever kernel the geometry was laid out for -- fwd_plan)
     if (aligned)
         spconv_fwd_small_kernel<NBT, true><<<grid, threads, lds, stream>>>(p);
     else
@@ -3723,6 +3718,15 @@ FwdGeom fwd_geometry(int Vout, int K, int Cin, int Cout, bool with_bn_partial, i
         ny++;
         while (NBtot % ny != 0) ny++;
     }
+    // a column slice so wide that not even ONE offset of it fits the LDS (320+ input channels on 7 or 8 column blocks beyond
+    // the small levels) had no kernel: MS3D_E_UNSUPPORTED.  More slices until one offset fits beside the statistics slots of
+    // a call that writes them (ms3d_spconv_partial_blocks asks with them).  Calls that had a kernel keep their geometry: for
+    // them one offset fitted already.
+    while (ny < NBtot && (size_t)NCH * 4 * (NBtot / ny) * 64 * sizeof(float) +
+                             (with_bn_partial ? STAT_MAX_WAVES * stat_slot_floats(NBtot / ny) * sizeof(float) : 0) > LDS_BUDGET) {
+        ny++;
+        while (NBtot % ny != 0) ny++;
+    }
     g.ny = ny;
     g.nbt = NBtot / ny;
     const size_t per_offset = (size_t)NCH * 4 * g.nbt * 64 * sizeof(float);  // LDS bytes per offset (column slice)
@@ -3754,6 +3758,120 @@ FwdGeom fwd_geometry(int Vout, int K, int Cin, int Cout, bool with_bn_partial, i
     if (g.nblk < 1) g.nblk = 1;
     g.ok = g.G >= 1 && g.nbt >= 1 && g.nbt <= MAX_NBT;
     return g;
+}
+
+// ---------------------------------------------------------------------------------------------------------
+// The forward / backward-data PLAN: which kernel family serves a call, with which template arguments, grid, block and
+// LDS.  spconv_forward_impl launches from it and from nothing else; ms3d_spconv_forward_plan exports it read-only.
+// (The statistics partials are sized from fwd_geometry alone -- ms3d_spconv_partial_blocks is not told the aux image --
+// so every family that serves one geometry writes g.nblk x g.ny partial rows.)
+// ---------------------------------------------------------------------------------------------------------
+enum FwdFamily {                  // = MS3D_FWD_* of include/minsu3d_hip.h
+    FWD_WS = 1,                   // spconv_fwd_ws_kernel
+    FWD_SMALL = 2,                // spconv_fwd_small_kernel
+    FWD_SMALL_BF3 = 3,            // spconv_fwd_small_bf3_kernel
+    FWD_SMALL_BF3_RT = 4,         // spconv_fwd_small_bf3_rt_kernel
+    FWD_PAIRSTREAM = 5,           // spconv_fwd_pairstream_kernel
+    FWD_PAIRLIST = 6,             // spconv_fwd_pairlist_kernel (64-row or 32-row tiles)
+    FWD_BF3 = 7,                  // spconv_fwd_bf3_kernel
+    FWD_RESIDENT = 8,             // spconv_fwd_kernel, weights resident in LDS
+    FWD_STREAMED = 9              // spconv_fwd_kernel, weights streamed in groups of G offsets
+};
+struct FwdPlan {
+    int family;       // FwdFamily
+    FwdGeom g;
+    int grid_x;       // gridDim.x as launched (the weight-stationary grid is not g.nblk)
+    int G, GC;        // ConvArgs::G / GC of the launch
+    int rt;           // small families: 16-row tiles per block; list families: 16-row tiles per list tile; else 1
+    size_t lds;       // dynamic LDS of the launch
+    int partial_rows; // rows of bn_partial the launch writes when it is asked for statistics
+};
+
+// pl_rows: rows per tile of the pair list the call is given (0 = none).  aux_kind: what the call's aux image holds (0 = no
+// image).  0, or MS3D_E_UNSUPPORTED where no kernel serves the call.
+int fwd_plan(int Vout, int K, int Cin, int Cout, int pl_rows, int aux_kind, bool with_stats, FwdPlan &pl)
+{
+    pl = FwdPlan{};
+    const FwdGeom g = fwd_geometry(Vout, K, Cin, Cout, with_stats, pl_rows);
+    if (!g.ok) return MS3D_E_UNSUPPORTED;
+    const int pieces = aux_pieces(aux_kind);    // bf16 image of 3 / 2 / 1 pieces, or none
+    const int NCH = ms3d_divup(Cin, 16);
+    pl.g = g;
+    pl.grid_x = g.nblk;
+    pl.G = g.G;
+    pl.GC = 0;
+    pl.rt = 1;
+    pl.lds = g.lds;
+    pl.partial_rows = g.nblk * g.ny;
+    if (g.ws) {
+        if (g.nbt < 1 || g.nbt > 4) return MS3D_E_UNSUPPORTED;
+        pl.family = FWD_WS;
+        pl.grid_x = ms3d_divup(g.ws_R * g.ny, 8) * 8 * g.ws_ng;     // units rounded up to the eight XCDs, times the offset groups
+        return 0;
+    }
+    if (g.stream) {
+        if (aux_kind != 1) return MS3D_E_UNSUPPORTED;  // the geometry (and the caller's partial buffer) assume this kernel
+        if (g.nbt < 1 || g.nbt > 4 || g.cg < 1 || g.cg > 4) return MS3D_E_UNSUPPORTED;
+        pl.family = FWD_PAIRSTREAM;
+        pl.rt = PSR / 16;
+        return 0;
+    }
+    if (g.pairlist) {
+        const bool narrow = g.pl_rows == PL_ROWS_NARROW;
+        const bool have = narrow ? (g.nbt == 2 && NCH == 2)
+                                 : ((g.nbt == 1 && NCH >= 1 && NCH <= 4) || (g.nbt == 2 && (NCH == 1 || NCH == 2)));
+        if (!have) return MS3D_E_UNSUPPORTED;
+        pl.family = FWD_PAIRLIST;
+        pl.rt = g.pl_rows / 16;
+        return 0;
+    }
+    if (g.small) {
+        pl.rt = g.rt;
+        if (g.rt > 1 && pieces) {
+            // the geometry (and the caller's statistics partials) count RT tiles per block
+            if (g.rt != 3 || g.nbt < 2 || g.nbt > 8) return MS3D_E_UNSUPPORTED;
+            pl.family = FWD_SMALL_BF3_RT;
+            return 0;
+        }
+        if (pieces && bf3_dims_ok(K, Cin, Cout) && g.nbt >= 2 && g.nbt <= 8) {
+            pl.family = FWD_SMALL_BF3;
+            return 0;
+        }
+        if (g.nbt < 1 || g.nbt > 8) return MS3D_E_UNSUPPORTED;
+        pl.family = FWD_SMALL;
+        // The geometry may have been laid out for the bf16x3 three-tile kernel (4 waves x RT x nbt KB of LDS, 72-96+ KB at
+        // >= 96 output channels) while this call has no bf16x3 image (the exact-f32 entry point, a BatchNorm without ReLU,
+        // aux kind 1): this kernel parks (waves - 1) x nbt accumulator tiles + the statistics only -- ask for that, not for
+        // the other kernel's footprint (which would exceed the 64 KB a kernel gets without raising its ceiling)
+        const size_t need = ((size_t)(g.threads / 64 - 1) * g.nbt * 256 + (with_stats ? stat_slot_floats(g.nbt) : 0)) * sizeof(float) + 16;
+        if (pl.lds > need) pl.lds = need;
+        return 0;
+    }
+    if (g.nbt < 1 || g.nbt > 8) return MS3D_E_UNSUPPORTED;
+    if (pieces && bf3_dims_ok(K, Cin, Cout) && g.nbt >= 2) {
+        // same grid as the f32 table walk (the statistics partials are sized for it); only the staged group shrinks:
+        // three bf16 pieces are 6 bytes per weight (two 4, one 2: more chunks per stage)
+        const int nc32 = (Cin + 31) / 32;
+        const size_t per_slab = (size_t)g.nbt * pieces * 1024;            // one (offset, 32-channel chunk) of the slice
+        const size_t extra = with_stats ? STAT_MAX_WAVES * stat_slot_floats(g.nbt) * sizeof(float) : 0;
+        const int slabs = (int)((LDS_BUDGET - extra) / per_slab);
+        // a stage = one gather round's offsets x as many chunks as fit beside them.  (Layers whose f32 image is LDS
+        // resident keep the f32 kernel: its grid is the persistent one.)
+        const int og = bf3_round_offsets(g.nbt);
+        int go = K < og ? K : og;       // (2..5 offsets per stage measured within 3 % of each other)
+        if (go > slabs) go = slabs;
+        int gc = go >= 1 ? slabs / go : 0;
+        if (gc > nc32) gc = nc32;
+        if (g.G < K && gc >= 1) {
+            pl.family = FWD_BF3;
+            pl.G = go;
+            pl.GC = gc;
+            pl.lds = per_slab * go * gc + extra;
+            return 0;
+        }
+    }
+    pl.family = g.G >= K ? FWD_RESIDENT : FWD_STREAMED;
+    return 0;
 }
 }  // namespace
 
@@ -3852,126 +3970,115 @@ static int spconv_forward_impl(const float *in, const float *wf, const int *nbr,
     p.residual = residual; p.bn_x = bn_x; p.bn_scale = bn_scale; p.bn_shift = bn_shift; p.bn_mean = bn_mean;
     p.bn_invstd = bn_invstd; p.bn_partial = bn_partial; p.Vout = Vout; p.K = K; p.Cin = Cin; p.Cout = Cout;
     p.NCH = ms3d_divup(Cin, 16); p.NBtot = ms3d_divup(Cout, 16); p.ntiles = ms3d_divup(Vout, 16); p.pre_relu = pre_relu;
-    const FwdGeom g = fwd_geometry(Vout, K, Cin, Cout, bn_x != nullptr || p.out_stats,
-                                   (pl_tile_start && pl_entries) ? ms3d_kmap_pairlist_rows_of(pl_tile_start) : 0);
-    if (!g.ok) return MS3D_E_UNSUPPORTED;
-    p.G = g.G;
-    dim3 grid(g.nblk, g.ny);
+    FwdPlan pl;
+    const int rc = fwd_plan(Vout, K, Cin, Cout, (pl_tile_start && pl_entries) ? ms3d_kmap_pairlist_rows_of(pl_tile_start) : 0,
+                            wf_stream ? aux_kind : 0, bn_x != nullptr || p.out_stats, pl);
+    if (rc != 0) return rc;
+    const FwdGeom &g = pl.g;
+    p.G = pl.G;
+    p.GC = pl.GC;
+    p.RT = g.small ? g.rt : 1;
+    dim3 grid(pl.grid_x, g.ny);
     const bool aligned = (Cin % 16 == 0);
     p.ws_slabs = nullptr; p.ws_cnt = nullptr; p.ws_ng = p.ws_kg = p.ws_R = p.ws_tpp = 0;
-    if (g.ws) {
-        const int units = g.ws_R * g.ny;
-        WsSpace *sp = ws_space(stream, g.ws_ng > 1 ? (size_t)g.ws_ng * p.ntiles * p.NBtot * 256 : 0, units);
-        if (!sp) return (int)hipErrorOutOfMemory;
-        p.ws_slabs = sp->slabs; p.ws_cnt = sp->cnt;
-        p.ws_ng = g.ws_ng; p.ws_kg = g.ws_kg; p.ws_R = g.ws_R; p.ws_tpp = g.ws_tpp;
-        const int nblk = ms3d_divup(units, 8) * 8 * g.ws_ng;
-        switch (g.nbt) {
-            case 1: return launch_fwd_ws<1>(p, nblk, g.threads, g.lds, stream);
-            case 2: return launch_fwd_ws<2>(p, nblk, g.threads, g.lds, stream);
-            case 3: return launch_fwd_ws<3>(p, nblk, g.threads, g.lds, stream);
-            case 4: return launch_fwd_ws<4>(p, nblk, g.threads, g.lds, stream);
-        }
-        return MS3D_E_UNSUPPORTED;
-    }
-    if (g.stream) {
-        if (!wf_stream || aux_kind != 1) return MS3D_E_UNSUPPORTED;  // the geometry (and the caller's partial buffer) assume this kernel
-        p.wfs = wf_stream;
-#define MS3D_PS(NBT_, CG_) \
-    if (g.nbt == NBT_ && g.cg == CG_) return launch_fwd_pairstream<NBT_, CG_>(p, grid, g.threads, g.lds, stream);
-        MS3D_PS(1, 1) MS3D_PS(1, 2) MS3D_PS(1, 3) MS3D_PS(1, 4)
-        MS3D_PS(2, 1) MS3D_PS(2, 2) MS3D_PS(2, 3) MS3D_PS(2, 4)
-        MS3D_PS(3, 1) MS3D_PS(3, 2) MS3D_PS(3, 3) MS3D_PS(3, 4)
-        MS3D_PS(4, 1) MS3D_PS(4, 2) MS3D_PS(4, 3) MS3D_PS(4, 4)
-#undef MS3D_PS
-        return MS3D_E_UNSUPPORTED;
-    }
-    if (g.pairlist) {
-        if (g.nbt == 1 && p.NCH == 1) return launch_fwd_pairlist<1, 1>(p, grid, g.threads, g.lds, stream);
-        if (g.nbt == 1 && p.NCH == 2) return launch_fwd_pairlist<1, 2>(p, grid, g.threads, g.lds, stream);
-        if (g.nbt == 2 && p.NCH == 1) return launch_fwd_pairlist<2, 1>(p, grid, g.threads, g.lds, stream);
-        if (g.nbt == 2 && p.NCH == 2 && g.pl_rows == PL_ROWS_NARROW) return launch_fwd_pairlist<2, 2, PL_ROWS_NARROW>(p, grid, g.threads, g.lds, stream);
-        if (g.nbt == 2 && p.NCH == 2) return launch_fwd_pairlist<2, 2>(p, grid, g.threads, g.lds, stream);
-        if (g.nbt == 1 && p.NCH == 3) return launch_fwd_pairlist<1, 3>(p, grid, g.threads, g.lds, stream);
-        if (g.nbt == 1 && p.NCH == 4) return launch_fwd_pairlist<1, 4>(p, grid, g.threads, g.lds, stream);
-        return MS3D_E_UNSUPPORTED;
-    }
-    p.RT = g.small ? g.rt : 1;
     // (P, NBT) -> the instantiation of a bf16 kernel family
 #define MS3D_BF_NBT(LAUNCH, P_, ...)                                                                                   \
     switch (g.nbt) {                                                                                                   \
-        case 2: return LAUNCH<2, ##__VA_ARGS__, P_>(p, grid, g.threads, LDS_, stream);                                \
-        case 3: return LAUNCH<3, ##__VA_ARGS__, P_>(p, grid, g.threads, LDS_, stream);                                \
-        case 4: return LAUNCH<4, ##__VA_ARGS__, P_>(p, grid, g.threads, LDS_, stream);                                \
-        case 5: return LAUNCH<5, ##__VA_ARGS__, P_>(p, grid, g.threads, LDS_, stream);                                \
-        case 6: return LAUNCH<6, ##__VA_ARGS__, P_>(p, grid, g.threads, LDS_, stream);                                \
-        case 7: return LAUNCH<7, ##__VA_ARGS__, P_>(p, grid, g.threads, LDS_, stream);                                \
-        case 8: return LAUNCH<8, ##__VA_ARGS__, P_>(p, grid, g.threads, LDS_, stream);                                \
+        case 2: return LAUNCH<2, ##__VA_ARGS__, P_>(p, grid, g.threads, pl.lds, stream);                              \
+        case 3: return LAUNCH<3, ##__VA_ARGS__, P_>(p, grid, g.threads, pl.lds, stream);                              \
+        case 4: return LAUNCH<4, ##__VA_ARGS__, P_>(p, grid, g.threads, pl.lds, stream);                              \
+        case 5: return LAUNCH<5, ##__VA_ARGS__, P_>(p, grid, g.threads, pl.lds, stream);                              \
+        case 6: return LAUNCH<6, ##__VA_ARGS__, P_>(p, grid, g.threads, pl.lds, stream);                              \
+        case 7: return LAUNCH<7, ##__VA_ARGS__, P_>(p, grid, g.threads, pl.lds, stream);                              \
+        case 8: return LAUNCH<8, ##__VA_ARGS__, P_>(p, grid, g.threads, pl.lds, stream);                              \
     }
 #define MS3D_BF_P(LAUNCH, ...)                                                                                         \
     if (pieces == 3) { MS3D_BF_NBT(LAUNCH, 3, ##__VA_ARGS__) }                                                         \
     else if (pieces == 2) { MS3D_BF_NBT(LAUNCH, 2, ##__VA_ARGS__) }                                                    \
     else { MS3D_BF_NBT(LAUNCH, 1, ##__VA_ARGS__) }
-    if (g.small && g.rt > 1 && pieces && wf_stream) {
-        // the geometry (and the caller's statistics partials) count RT tiles per block
-        p.wfb = wf_stream;
-        const size_t LDS_ = g.lds;
-        MS3D_BF_P(launch_fwd_small_bf3_rt, 3)
-        return MS3D_E_UNSUPPORTED;
+#define MS3D_F32_NBT(LAUNCH)                                                                                           \
+    switch (g.nbt) {                                                                                                   \
+        case 1: return LAUNCH<1>(p, grid, g.threads, pl.lds, aligned, stream);                                        \
+        case 2: return LAUNCH<2>(p, grid, g.threads, pl.lds, aligned, stream);                                        \
+        case 3: return LAUNCH<3>(p, grid, g.threads, pl.lds, aligned, stream);                                        \
+        case 4: return LAUNCH<4>(p, grid, g.threads, pl.lds, aligned, stream);                                        \
+        case 5: return LAUNCH<5>(p, grid, g.threads, pl.lds, aligned, stream);                                        \
+        case 6: return LAUNCH<6>(p, grid, g.threads, pl.lds, aligned, stream);                                        \
+        case 7: return LAUNCH<7>(p, grid, g.threads, pl.lds, aligned, stream);                                        \
+        case 8: return LAUNCH<8>(p, grid, g.threads, pl.lds, aligned, stream);                                        \
     }
-    if (g.small && pieces && wf_stream && bf3_dims_ok(K, Cin, Cout) && g.nbt >= 2) {
-        p.wfb = wf_stream;
-        const size_t LDS_ = g.lds;
-        MS3D_BF_P(launch_fwd_small_bf3)
-    }
-    if (g.small) {
-        switch (g.nbt) {
-            case 1: return launch_fwd_small<1>(p, grid, g.threads, g.lds, aligned, stream);
-            case 2: return launch_fwd_small<2>(p, grid, g.threads, g.lds, aligned, stream);
-            case 3: return launch_fwd_small<3>(p, grid, g.threads, g.lds, aligned, stream);
-            case 4: return launch_fwd_small<4>(p, grid, g.threads, g.lds, aligned, stream);
-            case 5: return launch_fwd_small<5>(p, grid, g.threads, g.lds, aligned, stream);
-            case 6: return launch_fwd_small<6>(p, grid, g.threads, g.lds, aligned, stream);
-            case 7: return launch_fwd_small<7>(p, grid, g.threads, g.lds, aligned, stream);
-            case 8: return launch_fwd_small<8>(p, grid, g.threads, g.lds, aligned, stream);
+    switch (pl.family) {
+        case FWD_WS: {
+            WsSpace *sp = ws_space(stream, g.ws_ng > 1 ? (size_t)g.ws_ng * p.ntiles * p.NBtot * 256 : 0, g.ws_R * g.ny);
+            if (!sp) return (int)hipErrorOutOfMemory;
+            p.ws_slabs = sp->slabs; p.ws_cnt = sp->cnt;
+            p.ws_ng = g.ws_ng; p.ws_kg = g.ws_kg; p.ws_R = g.ws_R; p.ws_tpp = g.ws_tpp;
+            switch (g.nbt) {
+                case 1: return launch_fwd_ws<1>(p, pl.grid_x, g.threads, pl.lds, stream);
+                case 2: return launch_fwd_ws<2>(p, pl.grid_x, g.threads, pl.lds, stream);
+                case 3: return launch_fwd_ws<3>(p, pl.grid_x, g.threads, pl.lds, stream);
+                case 4: return launch_fwd_ws<4>(p, pl.grid_x, g.threads, pl.lds, stream);
+            }
+            break;
         }
-        return MS3D_E_UNSUPPORTED;
-    }
-    if (pieces && wf_stream && bf3_dims_ok(K, Cin, Cout) && g.nbt >= 2) {
-        // same grid as the f32 table walk (the statistics partials are sized for it); only the staged group shrinks:
-        // three bf16 pieces are 6 bytes per weight (two 4, one 2: more chunks per stage)
-        const int nc32 = (Cin + 31) / 32;
-        const size_t per_slab = (size_t)g.nbt * pieces * 1024;            // one (offset, 32-channel chunk) of the slice
-        const size_t extra = (bn_x != nullptr || p.out_stats) ? STAT_MAX_WAVES * stat_slot_floats(g.nbt) * sizeof(float) : 0;
-        const int slabs = (int)((LDS_BUDGET - extra) / per_slab);
-        // a stage = one gather round's offsets x as many chunks as fit beside them.  (Layers whose f32 image is LDS
-        // resident keep the f32 kernel: its grid is the persistent one.)
-        const int og = bf3_round_offsets(g.nbt);
-        int go = K < og ? K : og;       // (2..5 offsets per stage measured within 3 % of each other)
-        if (go > slabs) go = slabs;
-        int gc = go >= 1 ? slabs / go : 0;
-        if (gc > nc32) gc = nc32;
-        if (g.G < K && gc >= 1) {
+        case FWD_PAIRSTREAM:
+            p.wfs = wf_stream;
+#define MS3D_PS(NBT_, CG_) \
+    if (g.nbt == NBT_ && g.cg == CG_) return launch_fwd_pairstream<NBT_, CG_>(p, grid, g.threads, pl.lds, stream);
+            MS3D_PS(1, 1) MS3D_PS(1, 2) MS3D_PS(1, 3) MS3D_PS(1, 4)
+            MS3D_PS(2, 1) MS3D_PS(2, 2) MS3D_PS(2, 3) MS3D_PS(2, 4)
+            MS3D_PS(3, 1) MS3D_PS(3, 2) MS3D_PS(3, 3) MS3D_PS(3, 4)
+            MS3D_PS(4, 1) MS3D_PS(4, 2) MS3D_PS(4, 3) MS3D_PS(4, 4)
+#undef MS3D_PS
+            break;
+        case FWD_PAIRLIST:
+            if (g.nbt == 1 && p.NCH == 1) return launch_fwd_pairlist<1, 1>(p, grid, g.threads, pl.lds, stream);
+            if (g.nbt == 1 && p.NCH == 2) return launch_fwd_pairlist<1, 2>(p, grid, g.threads, pl.lds, stream);
+            if (g.nbt == 2 && p.NCH == 1) return launch_fwd_pairlist<2, 1>(p, grid, g.threads, pl.lds, stream);
+            if (g.nbt == 2 && p.NCH == 2 && g.pl_rows == PL_ROWS_NARROW) return launch_fwd_pairlist<2, 2, PL_ROWS_NARROW>(p, grid, g.threads, pl.lds, stream);
+            if (g.nbt == 2 && p.NCH == 2) return launch_fwd_pairlist<2, 2>(p, grid, g.threads, pl.lds, stream);
+            if (g.nbt == 1 && p.NCH == 3) return launch_fwd_pairlist<1, 3>(p, grid, g.threads, pl.lds, stream);
+            if (g.nbt == 1 && p.NCH == 4) return launch_fwd_pairlist<1, 4>(p, grid, g.threads, pl.lds, stream);
+            break;
+        case FWD_SMALL_BF3_RT:
             p.wfb = wf_stream;
-            p.G = go;
-            p.GC = gc;
-            const size_t LDS_ = per_slab * p.G * p.GC + extra;
+            MS3D_BF_P(launch_fwd_small_bf3_rt, 3)
+            break;
+        case FWD_SMALL_BF3:
+            p.wfb = wf_stream;
+            MS3D_BF_P(launch_fwd_small_bf3)
+            break;
+        case FWD_SMALL:
+            MS3D_F32_NBT(launch_fwd_small)
+            break;
+        case FWD_BF3:
+            p.wfb = wf_stream;
             MS3D_BF_P(launch_fwd_bf3)
-        }
+            break;
+        case FWD_RESIDENT:
+        case FWD_STREAMED:
+            MS3D_F32_NBT(launch_fwd)
+            break;
     }
+#undef MS3D_F32_NBT
 #undef MS3D_BF_P
 #undef MS3D_BF_NBT
-    switch (g.nbt) {
-        case 1: return launch_fwd<1>(p, grid, g.threads, g.lds, aligned, stream);
-        case 2: return launch_fwd<2>(p, grid, g.threads, g.lds, aligned, stream);
-        case 3: return launch_fwd<3>(p, grid, g.threads, g.lds, aligned, stream);
-        case 4: return launch_fwd<4>(p, grid, g.threads, g.lds, aligned, stream);
-        case 5: return launch_fwd<5>(p, grid, g.threads, g.lds, aligned, stream);
-        case 6: return launch_fwd<6>(p, grid, g.threads, g.lds, aligned, stream);
-        case 7: return launch_fwd<7>(p, grid, g.threads, g.lds, aligned, stream);
-        case 8: return launch_fwd<8>(p, grid, g.threads, g.lds, aligned, stream);
-    }
     return MS3D_E_UNSUPPORTED;
+}
+
+// The plan of a forward / backward-data call, read-only (include/minsu3d_hip.h): what spconv_forward_impl launches.
+int ms3d_spconv_forward_plan(int Vout, int K, int Cin, int Cout, int pl_rows, int aux_kind, int with_stats, int *plan8)
+{
+    if (!plan8) return MS3D_E_UNSUPPORTED;
+    for (int i = 0; i < 8; i++) plan8[i] = 0;
+    if (Vout <= 0) return 0;          // nothing is launched
+    if (pl_rows < 0 || aux_kind < 0 || aux_kind > 4) return MS3D_E_UNSUPPORTED;
+    FwdPlan pl;
+    const int rc = fwd_plan(Vout, K, Cin, Cout, pl_rows == 1 ? MS3D_PL_ROWS : pl_rows, aux_kind, with_stats != 0, pl);
+    if (rc != 0) return rc;
+    plan8[0] = pl.family; plan8[1] = pl.g.nbt; plan8[2] = pl.g.ny; plan8[3] = pl.grid_x; plan8[4] = pl.g.threads;
+    plan8[5] = (int)pl.lds; plan8[6] = pl.rt; plan8[7] = pl.partial_rows;
+    return 0;
 }
 
 // column blocks the offset-list backward-weight kernel serves: up to 4 (one slice); the K = 8 layers (strided / transposed

@@ -18,7 +18,8 @@ def test_header_declares_the_boundary():
                  "ms3d_sec_mean", "ms3d_sec_min", "ms3d_sec_max", "ms3d_roipool_fp", "ms3d_roipool_bp",
                  "ms3d_global_avg_pool_fp", "ms3d_global_avg_pool_bp", "ms3d_get_iou", "ms3d_get_mask_iou_on_cluster",
                  "ms3d_get_mask_iou_on_pred", "ms3d_get_mask_label", "ms3d_sparse_quantize", "ms3d_kmap_k3",
-                 "ms3d_downsample", "ms3d_kmap_k2", "ms3d_spconv_forward", "ms3d_spconv_backward_weight", "ms3d_bn_stats"):
+                 "ms3d_downsample", "ms3d_kmap_k2", "ms3d_spconv_forward", "ms3d_spconv_backward_weight", "ms3d_bn_stats",
+                 "ms3d_spconv_forward_plan"):
         assert must in syms, must
 
 
