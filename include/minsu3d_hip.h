@@ -291,6 +291,48 @@ int ms3d_pool_forward(int mode, const float *in, const int *nbr, int Vout, int K
 int ms3d_pool_backward(int mode, const float *dout, const int *nbr_inv, int Vin, int K, int C, const unsigned char *arg,
                        const int *count, float *din, ms3d_stream_t stream);
 
+/* ---- points <-> voxels: TensorField quantisation and trilinear interpolation (csrc/field.hip; the map: csrc/coords.hip).
+ * float32, any C; 16-byte row accesses when C % 4 == 0 and the rows are 16-byte aligned.  Every direction is a gather with one
+ * writer per output element: no float atomics, the same bytes on every run.  Contracts shared by the five entry points,
+ * decided on the host: an unknown mode returns MS3D_E_UNSUPPORTED; zero output rows return 0 and launch nothing; a NULL pointer
+ * that would be read or written returns MS3D_E_UNSUPPORTED; row counts beyond 2^31 - 1 (points of a map: 8 N entries, so
+ * N <= (2^31 - 1) / 8) return MS3D_E_UNSUPPORTED.  Nothing is allocated inside a call.
+ *
+ * ms3d_interp_map: the eight corners of every query point in the set coords [Vin, 4] (distinct rows of tensor stride ts, a
+ * positive power of two -- anything else returns MS3D_E_UNSUPPORTED).  points: float [N, 4] (batch index, x, y, z in voxel
+ * units of stride 1), 16-byte aligned; the batch column is truncated to an integer.  Per axis q = p / ts, f = floor(q),
+ * r = q - f; corner j = bx + 2 by + 4 bz (x fastest) is the voxel (f + b) * ts with weight (wx * wy) * wz, w = b ? r : 1 - r,
+ * each operation rounded to float32.  rows int32 [8][N] = the row of coords at the corner or -1 (absent; a corner or batch
+ * index outside the packable key range; a point with a non-finite entry), weights float [8][N] (0 for a point with a
+ * non-finite entry; otherwise the weight whether the corner is present or not).  N == 0 or Vin == 0 launches nothing and
+ * returns 0 (with Vin == 0 the caller's tables are left as they are).  workspace: ms3d_coord_workspace_bytes(Vin).
+ *
+ * ms3d_interp_forward: out[n] = sum_j weights[j][n] * x[rows[j][n]] over the corners with rows >= 0, ascending j, one fmaf per
+ * corner and element starting from 0 -- a point on a voxel's own coordinate returns that row bit for bit, a point without any
+ * corner exact zeros.
+ * ms3d_interp_backward: din [Vin, C], din[v] = sum over the entries of row v of weight * dout[point], one fmaf each.  An entry
+ * is e = 8 * point + corner; entry_sorted [number of entries with rows >= 0] holds them grouped by row -- row v owns
+ * entry_sorted[seg_start[v] .. seg_start[v + 1]) (seg_start int32 [Vin + 1]) -- in ascending e inside a row, which is ascending
+ * point because a point names a row at most once (a stable sort of the point-major table by row, built once per map by the
+ * caller).  Entries whose point is outside [0, N) are skipped.
+ *
+ * ms3d_field_reduce: voxel features from point features.  mode 0 average, 1 sum, 2 max.  The points of voxel v are
+ * order[seg_start[v] .. seg_start[v + 1]) (int64 point indices, int32 offsets [V + 1]: a stable sort of the point -> voxel
+ * map), walked in that -- ascending -- order: the sum is a chain of float32 additions from 0, the average that sum divided
+ * once by float(count), the maximum takes the first point and then every strictly greater one (lowest point index on ties)
+ * and writes the winning point to arg int32 [V][C] (read and written for max only; NULL otherwise).
+ * ms3d_field_reduce_backward: dfeat[n] = dvox[v] / float(count of v) (average) | dvox[v] (sum) | dvox[v] where arg[v][c] == n
+ * else 0 (max), v = inverse[n] (int32 [N]); seg_start is read for average only, arg for max only. */
+int ms3d_interp_map(const int *coords, int Vin, const float *points, long N, int tensor_stride, int *rows, float *weights,
+                    void *workspace, size_t workspace_bytes, ms3d_stream_t stream);
+int ms3d_interp_forward(const float *x, const int *rows, const float *weights, long N, int C, float *out, ms3d_stream_t stream);
+int ms3d_interp_backward(const float *dout, const float *weights, const long long *entry_sorted, const int *seg_start, long Vin,
+                         long N, int C, float *din, ms3d_stream_t stream);
+int ms3d_field_reduce(int mode, const float *feats, const long long *order, const int *seg_start, long V, int C, float *out,
+                      int *arg, ms3d_stream_t stream);
+int ms3d_field_reduce_backward(int mode, const float *dvox, const int *inverse, const int *seg_start, const int *arg, long N,
+                               int C, float *dfeat, ms3d_stream_t stream);
+
 /* Pair list = tile-compacted form of an offset-major table, built once per table and shared by every convolution of
  * the level (forward, backward-data, backward-weight).  Output rows are cut into tiles of 64; per tile and offset the
  * valid (input row, output row) pairs are stored contiguously, padded to a multiple of 16 ("batch" = one MFMA group).

@@ -25,22 +25,32 @@ and one row per batch index meets every voxel of its batch:
     MinkowskiBroadcastAddition, MinkowskiBroadcastMultiplication, MinkowskiBroadcastConcatenation, MinkowskiBroadcast,
     MinkowskiSigmoid  (+ CoordinateManager.union / broadcast_map: engine extras)
 
+Points in, points out -- how a network gets from a point cloud to voxels and back:
+
+    TensorField (.sparse / .slice / .cat_slice / .inverse_mapping), SparseTensorQuantizationMode,
+    SparseTensor.slice / .cat_slice / .interpolate, MinkowskiInterpolation, MinkowskiPoolingTranspose
+    (+ CoordinateManager.interpolation_map: engine extra)
+
 Not supported (each raises NotImplementedError naming it): strides other than 1 and 2, a generative layer at stride 2 on an odd
 tensor stride, MinkowskiConvolutionTranspose onto a coordinate set that is not cached, convolutions (expand_coordinates) or
 pooling that create coordinates, `+=` and ME.cat across different coordinate sets, a union of more than 16 tensors,
-MinkowskiPoolingTranspose / MinkowskiInterpolation / TensorField, dimension != 3, per-axis kernel tuples.
+the `quantization_mode` argument of SparseTensor itself (quantise with a field), interpolation gradients with respect to the
+coordinates, pooling transpose at strides other than 1 and 2 or onto a set that is not cached, dimension != 3, per-axis kernel
+tuples.
 
 Module/parameter names match ME so reference state_dicts keep their keys (`kernel`, `bn.weight`, ...).
 """
 from . import utils  # noqa: F401
 from .tensor import SparseTensor, CoordinateManager, cat, prefetch_coordinates  # noqa: F401
+from .tensor import TensorField, SparseTensorQuantizationMode  # noqa: F401
 from .modules import (MinkowskiConvolution, MinkowskiConvolutionTranspose, MinkowskiBatchNorm,  # noqa: F401
                       MinkowskiReLU, prepare_conv_weights, release_conv_weights,
                       MinkowskiMaxPooling, MinkowskiAvgPooling, MinkowskiSumPooling, MinkowskiGlobalMaxPooling,
                       MinkowskiGlobalAvgPooling, MinkowskiGlobalSumPooling, MinkowskiLinear, MinkowskiDropout,
                       MinkowskiGenerativeConvolutionTranspose, MinkowskiPruning,
                       MinkowskiUnion, MinkowskiBroadcastAddition, MinkowskiBroadcastMultiplication,
-                      MinkowskiBroadcastConcatenation, MinkowskiBroadcast, MinkowskiSigmoid)
+                      MinkowskiBroadcastConcatenation, MinkowskiBroadcast, MinkowskiSigmoid,
+                      MinkowskiPoolingTranspose, MinkowskiInterpolation)
 from .tensor import kernel_offsets  # noqa: F401  (engine extra: the offset list of a kernel, in weight order)
 from .functional import gather_rows  # noqa: F401  (engine extra: x[idx] with a scatter-add backward)
 from .functional import SkipLink  # noqa: F401  (engine extra: a residual block's skip gradient, see functional.py)

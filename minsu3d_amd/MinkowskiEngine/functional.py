@@ -649,3 +649,62 @@ class BroadcastFn(torch.autograd.Function):
 
 def broadcast(mode, x, g, grow, red):
     return BroadcastFn.apply(mode, x, g, grow, red)
+
+
+def _field_backend(what, *methods):
+    be = get_backend()
+    if not all(hasattr(be, m) for m in methods):
+        raise NotImplementedError(f"{what} needs the HIP backend (ms3d_{methods[0]})")
+    return be
+
+
+class FieldReduceFn(torch.autograd.Function):
+    """voxel rows from point rows (TensorField.sparse): mode 0 average, 1 sum, 2 max over the points of every voxel in
+    ascending point index (csrc/field.hip).  order / seg_start: the stable sort of `inverse` (int32 [N], point -> voxel row as
+    the engine HOLDS the rows) and its segment offsets.  The backward is a gather per point."""
+
+    @staticmethod
+    def forward(ctx, feats, mode, inverse, order, seg_start, n_vox):
+        be = _field_backend("TensorField.sparse", "field_reduce", "field_reduce_backward")
+        if n_vox == 0:
+            out, arg = feats.new_empty((0, feats.size(1))), None
+        else:
+            out, arg = be.field_reduce(mode, feats, order, seg_start, n_vox)
+        ctx.geom = (mode, inverse, seg_start, arg)
+        return out
+
+    @staticmethod
+    def backward(ctx, dvox):
+        mode, inverse, seg_start, arg = ctx.geom
+        if inverse.numel() == 0:
+            return dvox.new_empty((0, dvox.size(1))), None, None, None, None, None
+        return get_backend().field_reduce_backward(mode, dvox.contiguous(), inverse, seg_start, arg), None, None, None, None, None
+
+
+def field_reduce(feats, mode, inverse, order, seg_start, n_vox):
+    return FieldReduceFn.apply(feats, mode, inverse, order, seg_start, n_vox)
+
+
+class InterpolateFn(torch.autograd.Function):
+    """out [N, C] = trilinear interpolation of the rows x [V, C] (as the engine holds them) through an interpolation map
+    (rows, weights: [8, N]; group = (entry_sorted, seg_start): the map's entries grouped by voxel row, the fixed summation
+    order of the backward).  Gradients flow to x only: the query coordinates get none."""
+
+    @staticmethod
+    def forward(ctx, x, rows, weights, group):
+        be = _field_backend("interpolation", "interp_forward", "interp_backward")
+        ctx.geom = (rows, weights, group, x.size(0))
+        if rows.size(1) == 0 or x.size(0) == 0:
+            return x.new_zeros((rows.size(1), x.size(1)))
+        return be.interp_forward(x, rows, weights)
+
+    @staticmethod
+    def backward(ctx, dout):
+        rows, weights, (entry_sorted, seg_start), vin = ctx.geom
+        if vin == 0 or rows.size(1) == 0:
+            return dout.new_zeros((vin, dout.size(1))), None, None, None
+        return get_backend().interp_backward(dout.contiguous(), weights, entry_sorted, seg_start, vin), None, None, None
+
+
+def interpolate(x, rows, weights, group):
+    return InterpolateFn.apply(x, rows, weights, group)

@@ -363,6 +363,64 @@ class MinkowskiSumPooling(_PoolBase):
     MODE = 2
 
 
+class MinkowskiPoolingTranspose(nn.Module):
+    """parameter-free upsampling: out[o] = sum_k in[nbr_up[k][o]] over the transposed table of the pooling of the same
+    (kernel_size, stride, dilation) -- a SUM, not an average; with kernel 2 stride 2 every fine voxel copies its parent.
+    Stride 2 maps from tensor stride ts onto the CACHED finer set at ts / 2 (the refusals of MinkowskiConvolutionTranspose: an
+    uncached target raises NotImplementedError), stride 1 (odd kernels) stays on the set.  Sum pooling (csrc/pool.hip) over
+    the transposed table forward, through the forward table backward.  Strides other than 1 and 2 are not supported."""
+
+    def __init__(self, kernel_size, stride, dilation=1, dimension=3):
+        super().__init__()
+        if dimension != 3:
+            raise NotImplementedError(f"dimension={dimension}: only 3-D sparse tensors are supported")
+        check_geometry(kernel_size, stride, dilation)
+        self.kernel_size, self.stride, self.dilation = kernel_size, stride, dilation
+
+    def forward(self, x: SparseTensor):
+        cm, ts = x.coordinate_manager, x.tensor_stride
+        geom = (self.kernel_size, self.stride, self.dilation)
+        if self.stride == 1:
+            # the transpose of a submanifold table is its mirror image, and a sum does not care about the offset order
+            nbr, _, vin, vout, K, _, _ = cm.kernel_map(ts, *geom)
+            y = Fn.sparse_pool(x._raw(), nbr, cm.kernel_map_inverse(ts, *geom), vin, vout, K, 2)
+            return x._like(y)
+        if ts % 2 != 0 or (ts // 2) not in cm.coords:
+            raise NotImplementedError(f"MinkowskiPoolingTranspose(kernel_size={self.kernel_size}, stride={self.stride}) on "
+                                      f"tensor stride {ts}: only onto a cached finer coordinate set; generating new "
+                                      "coordinates is not supported")
+        fine = ts // 2
+        down, _, v_fine, v_coarse, K, _, _ = cm.kernel_map(fine, *geom)       # the strided map fine -> ts
+        up = cm.kernel_map_inverse(fine, *geom)                               # [K, v_fine]: the coarse row a fine row feeds
+        y = Fn.sparse_pool(x._raw(), up, down, v_coarse, v_fine, K, 2)
+        return x._like(y, tensor_stride=fine)
+
+    def extra_repr(self):
+        return f"kernel_size={self.kernel_size}, stride={self.stride}, dilation={self.dilation}"
+
+
+class MinkowskiInterpolation(nn.Module):
+    """forward(x, tfield_coordinates) -> the trilinear interpolation of x's rows at the float coordinates [N, 4] (batch index
+    first, voxel units): a tensor [N, C]; with return_kernel_map the table rows int32 [8, N] (corner j = bx + 2 by + 4 bz; the
+    row of x.features / x.coordinates at the corner or -1) and with return_weights the weights float32 [8, N] follow.  Absent
+    voxels count as zeros, nothing is renormalised.  Gradients flow to x's features only: like MinkowskiEngine, the query
+    coordinates get none."""
+
+    def __init__(self, return_kernel_map=False, return_weights=False):
+        super().__init__()
+        self.return_kernel_map, self.return_weights = return_kernel_map, return_weights
+
+    def forward(self, x: SparseTensor, tfield_coordinates):
+        cm, ts = x.coordinate_manager, x.tensor_stride
+        rows, weights, group = cm.interpolation_map(ts, tfield_coordinates)
+        out = [Fn.interpolate(x._raw(), rows, weights, group)]
+        if self.return_kernel_map:
+            out.append(cm.visible_rows(ts, rows))
+        if self.return_weights:
+            out.append(weights)
+        return out[0] if len(out) == 1 else tuple(out)
+
+
 class _GlobalPoolBase(nn.Module):
     """one output row per batch index present, in ascending batch order.  The result is a plain tensor wrapper on its own
     coordinate set (batch index, 0, 0, 0); rows are grouped by batch through a cached stable sort, not assumed contiguous."""

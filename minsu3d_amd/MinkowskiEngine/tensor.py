@@ -8,6 +8,7 @@ a tensor that only records (scale, shift[, relu]); the following convolution app
 input rows, so `Sequential(BN, ReLU, Conv)` is one gather kernel and never materialises the normalised
 activations.  Touching `.features` of such a tensor materialises it (one elementwise kernel).
 """
+import enum
 import os
 
 import numpy as np
@@ -183,6 +184,46 @@ class CoordinateManager:
             grow = lut[self.coords[ts][:, 0].long()].contiguous()
             hit = cache[key] = (grow, (order.contiguous(), offsets.contiguous(), seg_of_g), gcm)
         return hit[:2]
+
+    def interpolation_map(self, ts, points):
+        """the trilinear interpolation map of the float points [N, 4] (batch index, x, y, z in voxel units) into the
+        coordinate set of tensor stride ts -> (rows int32 [8, N], weights float32 [8, N], (entry_sorted int64, seg_start int32
+        [V + 1])); the rules are ms3d_interp_map's (include/minsu3d_hip.h): corner j = bx + 2 by + 4 bz, rows -1 where the set
+        has no voxel.  `rows` names the rows as the engine HOLDS them (the table is built over the held set, so the Morton
+        permutation of a sorted manager is in it already; `visible_rows` turns them into the rows the caller sees).  The
+        grouping is the map's entries e = 8 * point + corner with a row, stably sorted by row: the fixed order in which the
+        backward sums a voxel's gradients.  Built once per points tensor OBJECT and version (the way a sorted index is kept on
+        its tensor) and kept on this manager with the tensor; the four newest maps are kept.  An engine extra."""
+        cache = self.__dict__.setdefault("_interp", {})
+        key = (ts, id(points))
+        hit = cache.get(key)
+        if hit is None or hit[3] is not points or hit[4] != points._version:
+            be = get_backend()
+            if not hasattr(be, "interp_map"):
+                raise NotImplementedError("interpolation needs the HIP backend (ms3d_interp_map)")
+            if points.dim() != 2 or points.size(1) != 4 or not points.is_floating_point():
+                raise ValueError(f"interpolation: float coordinates [N, 4] (batch index, x, y, z), got {list(points.shape)} "
+                                 f"{points.dtype}")
+            coords = self.coords[ts]
+            p = points.detach().to(device=coords.device, dtype=torch.float32).contiguous()
+            rows, weights = be.interp_map(coords, p, ts)
+            v = coords.size(0)
+            flat = rows.t().reshape(-1)                                   # point-major: entry e = 8 * point + corner
+            valid = torch.nonzero(flat >= 0).view(-1)
+            of_row = flat[valid].long()
+            entry_sorted = valid[torch.sort(of_row, stable=True).indices].contiguous()
+            seg_start = torch.zeros(v + 1, dtype=torch.int32, device=rows.device)
+            seg_start[1:] = torch.cumsum(torch.bincount(of_row, minlength=v), 0)
+            hit = cache[key] = (rows, weights, (entry_sorted, seg_start), points, points._version)
+            while len(cache) > 4:
+                cache.pop(next(iter(cache)))
+        return hit[:3]
+
+    def visible_rows(self, ts, rows):
+        """held row numbers (int32, -1 = none) -> the rows of .coordinates / .features the caller sees"""
+        if ts == 1 and self.perm is not None and rows.numel() > 0:
+            return torch.where(rows >= 0, self.perm[rows.clamp(min=0).long()], rows.long()).to(torch.int32)
+        return rows
 
     def kernel_map(self, ts, kernel_size, stride=1, dilation=1):
         """-> (nbr_fwd [K, Vout], nbr_bwd [K, Vin], Vin, Vout, K, output tensor stride, mirror) for a layer from the
@@ -487,6 +528,22 @@ class SparseTensor:
         padded = torch.cat([feats, feats.new_zeros((1, feats.size(1)))])      # absent -> the zero row behind the last one
         return Fn.gather_rows(padded, torch.where(rows < 0, torch.full_like(rows, feats.size(0)), rows))
 
+    # ---- points in, points out (TensorField)
+    def slice(self, field):
+        """TensorField on `field`'s points: every point gets the row of its voxel (TensorField.slice)"""
+        return field.slice(self)
+
+    def cat_slice(self, field):
+        """the same with the field's own features in front (TensorField.cat_slice)"""
+        return field.cat_slice(self)
+
+    def interpolate(self, field):
+        """TensorField on `field`'s points: the trilinear interpolation of this tensor's rows at the points' continuous
+        coordinates, zeros for absent voxels, no renormalisation (ms3d_interp_map / ms3d_interp_forward).  Gradients flow to
+        the features only; like MinkowskiEngine, the coordinates get none."""
+        rows, weights, group = self.coordinate_manager.interpolation_map(self.tensor_stride, field._points())
+        return field._like(Fn.interpolate(self._raw(), rows, weights, group))
+
     def __iadd__(self, other):      # `x += identity` (common.py:48)
         if not isinstance(other, SparseTensor):
             self._F = self._dense_op(other, torch.add)
@@ -538,6 +595,161 @@ class SparseTensor:
         elif not isinstance(other, (int, float)):
             raise TypeError(f"unsupported operand for a SparseTensor: {type(other).__name__}")
         return fn(rows, other)
+
+
+class SparseTensorQuantizationMode(enum.Enum):
+    """what a voxel's feature is when several points fall into it (TensorField.sparse)"""
+    RANDOM_SUBSAMPLE = 0        # the FIRST point of the voxel: "random" is the canonical first occurrence, as everywhere here
+    UNWEIGHTED_AVERAGE = 1      # mean of the voxel's points
+    UNWEIGHTED_SUM = 2          # their sum
+    MAX_POOL = 4                # per-element maximum (lowest point index on ties)
+
+
+_REDUCE_CODE = {SparseTensorQuantizationMode.UNWEIGHTED_AVERAGE: 0, SparseTensorQuantizationMode.UNWEIGHTED_SUM: 1,
+                SparseTensorQuantizationMode.MAX_POOL: 2}
+
+
+def _check_tensor_stride(ts):
+    if not isinstance(ts, int) or ts < 1 or ts & (ts - 1):
+        raise NotImplementedError(f"tensor_stride={ts!r}: one positive power of two (no per-axis tuples)")
+    return ts
+
+
+class TensorField:
+    """Features at continuous positions: `coordinates` [N, 4] (batch index first, x, y, z in voxel units, float or integer),
+    `features` [N, C].  `.sparse()` voxelises, `.slice()` / `.cat_slice()` bring a SparseTensor's rows back to the points,
+    `SparseTensor.interpolate(field)` reads a tensor at the points trilinearly.  The rules (floor, first-occurrence order,
+    ascending-point sums) are MinkowskiEngine's as recalled, not pinned; DESIGN section 4.2 writes them down."""
+
+    def __init__(self, features, coordinates, quantization_mode=SparseTensorQuantizationMode.UNWEIGHTED_AVERAGE, device=None):
+        if not isinstance(quantization_mode, SparseTensorQuantizationMode):
+            raise NotImplementedError(f"quantization_mode={quantization_mode!r}: a SparseTensorQuantizationMode")
+        if coordinates.dim() != 2 or coordinates.size(1) != 4 or features.dim() != 2 or features.size(0) != coordinates.size(0):
+            raise ValueError(f"TensorField: coordinates [N, 4] and features [N, C], got {list(coordinates.shape)} and "
+                             f"{list(features.shape)}")
+        if device is not None:
+            features, coordinates = features.to(device), coordinates.to(device)
+        self._F, self._C = features, coordinates.to(features.device)
+        self.quantization_mode = quantization_mode
+        self._shared = {}        # caches that depend on the coordinates only; fields made by _like() share them
+
+    @property
+    def features(self):
+        return self._F
+
+    F = features
+
+    @property
+    def coordinates(self):
+        return self._C
+
+    C = coordinates
+
+    @property
+    def device(self):
+        return self._F.device
+
+    def _like(self, features):
+        f = TensorField.__new__(TensorField)
+        f._F, f._C, f.quantization_mode, f._shared = features, self._C, self.quantization_mode, self._shared
+        return f
+
+    def _points(self):
+        """the coordinates as ONE float tensor object (an interpolation map is cached per object)"""
+        if self._C.is_floating_point():
+            return self._C
+        p = self._shared.get("points")
+        if p is None:
+            p = self._shared["points"] = self._C.to(torch.float32)
+        return p
+
+    def _quantized(self, ts):
+        """int32 [N, 4]: the voxel of every point at tensor stride ts, floor(p / ts) * ts per axis (floor, not truncation:
+        -0.5 -> -ts); the batch column is taken as an integer"""
+        q = self._shared.get(("q", ts))
+        if q is None:
+            c = self._C
+            if c.is_floating_point():
+                xyz = torch.floor(c[:, 1:] / ts).to(torch.int32) * ts
+            else:
+                xyz = torch.div(c[:, 1:], ts, rounding_mode="floor").to(torch.int32) * ts
+            q = self._shared[("q", ts)] = torch.cat([c[:, :1].to(torch.int32), xyz], 1).contiguous()
+        return q
+
+    def sparse(self, tensor_stride=1, quantization_mode=None):
+        """-> SparseTensor at `tensor_stride` (a power of two) on the voxels floor(p / ts) * ts, in first-occurrence order of
+        the points (ms3d_sparse_quantize); its features per `quantization_mode` (default: the field's): the mean / sum of the
+        voxel's points added in ascending point index, the per-element maximum, or the voxel's first point.  A field of at
+        least _SORT_MIN_ROWS voxels at stride 1 gets a Morton-sorted manager like any SparseTensor.  `.inverse_mapping`
+        afterwards names every point's row in the order of the result's .features / .coordinates."""
+        ts = _check_tensor_stride(tensor_stride)
+        mode = self.quantization_mode if quantization_mode is None else quantization_mode
+        if not isinstance(mode, SparseTensorQuantizationMode):
+            raise NotImplementedError(f"quantization_mode={mode!r}: a SparseTensorQuantizationMode")
+        be = get_backend()
+        if not hasattr(be, "sparse_quantize"):
+            raise NotImplementedError("TensorField.sparse needs the HIP backend (ms3d_sparse_quantize)")
+        if mode in _REDUCE_CODE and not hasattr(be, "field_reduce"):
+            raise NotImplementedError("TensorField.sparse needs the HIP backend (ms3d_field_reduce)")
+        q = self._quantized(ts)
+        uniq, inv = be.sparse_quantize(q)
+        uniq, inverse = uniq.long(), inv.long()
+        coords = q[uniq]
+        v = coords.size(0)
+        cm = (CoordinateManager(coords, spatial_sort=v >= _SORT_MIN_ROWS) if ts == 1 else CoordinateManager.rooted(coords, ts))
+        # the maps below name rows as the engine HOLDS them: the Morton permutation is composed into them once
+        held = cm.inv[inverse] if cm.inv is not None else inverse
+        feats = self._F if self._F.dtype == torch.float32 else self._F.float()
+        if v == 0:
+            y = feats.new_empty((0, feats.size(1)))
+        elif mode is SparseTensorQuantizationMode.RANDOM_SUBSAMPLE:
+            y = Fn.gather_rows(feats, uniq[cm.perm] if cm.perm is not None else uniq, max_dup=1)
+        else:
+            order = torch.sort(held, stable=True).indices.contiguous()
+            seg_start = torch.zeros(v + 1, dtype=torch.int32, device=held.device)
+            seg_start[1:] = torch.cumsum(torch.bincount(held, minlength=v), 0)
+            y = Fn.field_reduce(feats, _REDUCE_CODE[mode], held.to(torch.int32).contiguous(), order, seg_start, v)
+        self._shared["sparse"] = (cm, ts, inverse, held)
+        return SparseTensor(y, coordinate_manager=cm, tensor_stride=ts)
+
+    @property
+    def inverse_mapping(self):
+        """int64 [N]: point -> row of the last .sparse() (in the order of its .features / .coordinates)"""
+        last = self._shared.get("sparse")
+        if last is None:
+            raise ValueError("TensorField.inverse_mapping: call .sparse() first")
+        return last[2]
+
+    def _rows_in(self, x):
+        """int64 [N]: per point the row of x.features its voxel has at x's tensor stride, x.features.size(0) where x lacks
+        the voxel; looked up once per (manager, tensor stride) through SparseTensor.coordinate_rows"""
+        cache = self._shared.setdefault("rows", {})
+        key = (id(x.coordinate_manager), x.tensor_stride)
+        hit = cache.get(key)
+        if hit is None or hit[1] is not x.coordinate_manager:
+            r = x.coordinate_rows(self._quantized(_check_tensor_stride(x.tensor_stride))).long()
+            n_rows = x.coordinate_manager.size(x.tensor_stride)
+            hit = cache[key] = (torch.where(r < 0, torch.full_like(r, n_rows), r), x.coordinate_manager)
+        return hit[0]
+
+    def slice(self, x):
+        """TensorField on these points with out[n] = x.F[row of point n's voxel].  On the tensor `.sparse()` made (same manager
+        and stride) the cached inverse map is used; on any other manager or stride -- the output of a generative layer, a
+        pruned tensor, a coarser level -- the rows are looked up once and a point whose voxel x lacks gets the zero row.  The
+        gradient of a voxel row is the sum of its points' gradients in ascending point index."""
+        if self._C.size(0) == 0:
+            return self._like(x._F.new_zeros((0, x._F.size(1))))
+        last = self._shared.get("sparse")
+        if last is not None and x.coordinate_manager is last[0] and x.tensor_stride == last[1]:
+            return self._like(Fn.gather_rows(x._raw(), last[3]))
+        rows = self._rows_in(x)
+        feats = x.features
+        padded = torch.cat([feats, feats.new_zeros((1, feats.size(1)))])      # absent -> the zero row behind the last one
+        return self._like(Fn.gather_rows(padded, rows))
+
+    def cat_slice(self, x):
+        """.slice(x) with the field's own features concatenated in front"""
+        return self._like(torch.cat([self._F, self.slice(x)._F], 1))
 
 
 def union_op(op, *tensors):

@@ -1055,6 +1055,77 @@ class _HipEngine:
                    "ms3d_pool_backward")
         return din
 
+    # ---- points <-> voxels (csrc/field.hip; the interpolation map: csrc/coords.hip)
+    def interp_map(self, coords, points, tensor_stride):
+        """the eight corners of every point in the coordinate set `coords` (int32 [V, 4], tensor stride `tensor_stride`) ->
+        (rows int32 [8, N]: the row of coords at corner j = bx + 2 by + 4 bz or -1, weights float32 [8, N]); points: float32
+        [N, 4] (batch index, x, y, z).  The rules: ms3d_interp_map."""
+        coords, points = self._dev(coords), self._dev(points)
+        assert coords.dtype == torch.int32 and coords.dim() == 2 and coords.size(1) == 4
+        assert points.dtype == torch.float32 and points.dim() == 2 and points.size(1) == 4
+        coords, points = coords.contiguous(), points.contiguous()
+        v, n, dev = coords.size(0), points.size(0), coords.device
+        rows = torch.empty((8, n), dtype=torch.int32, device=dev)
+        weights = torch.empty((8, n), dtype=torch.float32, device=dev)
+        if v == 0:          # (the entry point launches nothing for an empty set: no corner exists)
+            rows.fill_(-1); weights.zero_()
+        ws = self._cws(v, dev)
+        _lib.check(self.lib.ms3d_interp_map(_lib.ptr(coords), int(v), _lib.ptr(points), C.c_long(n), int(tensor_stride),
+                                            _lib.ptr(rows), _lib.ptr(weights), _lib.ptr(ws), C.c_size_t(ws.numel()),
+                                            _lib.stream_handle()), "ms3d_interp_map")
+        return rows, weights
+
+    def interp_forward(self, x, rows, weights):
+        """out [N, C] = sum over the corners present of weights[j] * x[rows[j]], ascending j"""
+        x = self._dev(x).contiguous()
+        n, c = rows.size(1), x.size(1)
+        assert x.dtype == torch.float32 and x.dim() == 2 and rows.dtype == torch.int32 and rows.is_contiguous()
+        assert weights.dtype == torch.float32 and weights.is_contiguous() and tuple(weights.shape) == tuple(rows.shape) == (8, n)
+        out = torch.empty((n, c), dtype=torch.float32, device=x.device)
+        _lib.check(self.lib.ms3d_interp_forward(_lib.ptr(x), _lib.ptr(rows), _lib.ptr(weights), C.c_long(n), int(c),
+                                                _lib.ptr(out), _lib.stream_handle()), "ms3d_interp_forward")
+        return out
+
+    def interp_backward(self, dout, weights, entry_sorted, seg_start, vin):
+        """din [vin, C]: per voxel row the weighted sum of dout over its entries (entry_sorted int64, seg_start int32
+        [vin + 1]: CoordinateManager.interpolation_map), in ascending point order"""
+        dout = self._dev(dout).contiguous()
+        n, c = dout.size(0), dout.size(1)
+        assert dout.dtype == torch.float32 and weights.dtype == torch.float32 and tuple(weights.shape) == (8, n)
+        assert entry_sorted.dtype == torch.int64 and entry_sorted.is_contiguous() and weights.is_contiguous()
+        assert seg_start.dtype == torch.int32 and seg_start.is_contiguous() and seg_start.numel() == vin + 1
+        din = torch.empty((vin, c), dtype=torch.float32, device=dout.device)
+        _lib.check(self.lib.ms3d_interp_backward(_lib.ptr(dout), _lib.ptr(weights), _lib.ptr(entry_sorted), _lib.ptr(seg_start),
+                                                 C.c_long(vin), C.c_long(n), int(c), _lib.ptr(din), _lib.stream_handle()),
+                   "ms3d_interp_backward")
+        return din
+
+    def field_reduce(self, mode, feats, order, seg_start, v):
+        """voxel features [v, C] from point features: mode 0 average, 1 sum, 2 max over the points order[seg_start[r] ..
+        seg_start[r + 1]) of every voxel row r, in that order -> (out, arg int32 [v, C]: the winning point, for max, else
+        None)"""
+        feats = self._dev(feats).contiguous()
+        c, dev = feats.size(1), feats.device
+        assert feats.dtype == torch.float32 and feats.dim() == 2 and order.dtype == torch.int64 and order.is_contiguous()
+        assert order.numel() == feats.size(0) and seg_start.dtype == torch.int32 and seg_start.numel() == v + 1
+        out = torch.empty((v, c), dtype=torch.float32, device=dev)
+        arg = torch.empty((v, c), dtype=torch.int32, device=dev) if mode == 2 else None
+        _lib.check(self.lib.ms3d_field_reduce(int(mode), _lib.ptr(feats), _lib.ptr(order), _lib.ptr(seg_start), C.c_long(v),
+                                              int(c), _lib.ptr(out), _lib.ptr(arg), _lib.stream_handle()), "ms3d_field_reduce")
+        return out, arg
+
+    def field_reduce_backward(self, mode, dvox, inverse, seg_start, arg):
+        """dfeat [N, C]: per point the gradient of its voxel's row (inverse int32 [N]), divided by the voxel's point count
+        (average), as is (sum), or where the point won the element (max)"""
+        dvox = self._dev(dvox).contiguous()
+        n, c = inverse.numel(), dvox.size(1)
+        assert dvox.dtype == torch.float32 and inverse.dtype == torch.int32 and inverse.is_contiguous()
+        dfeat = torch.empty((n, c), dtype=torch.float32, device=dvox.device)
+        _lib.check(self.lib.ms3d_field_reduce_backward(int(mode), _lib.ptr(dvox), _lib.ptr(inverse), _lib.ptr(seg_start),
+                                                       _lib.ptr(arg), C.c_long(n), int(c), _lib.ptr(dfeat),
+                                                       _lib.stream_handle()), "ms3d_field_reduce_backward")
+        return dfeat
+
     # ---- convolution
     def prep_weights(self, W, K, cin_e, cout_e, transpose=False, mirror=False):
         """-> weight image handle [2, n]: row 0 the fragment-major image, row 1 the same weights in streamed order"""

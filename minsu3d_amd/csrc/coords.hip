@@ -181,6 +181,40 @@ __global__ void kmap_general_kernel(const int *__restrict__ out_coords, int Vout
     nbr[(size_t)k * Vout + o] = r;
 }
 
+// Trilinear interpolation map: one thread per (corner, point), tables corner-major like every kernel map.  Per axis q = p / ts
+// (an exact scaling: ts is a power of two), f = floor(q), r = q - f; corner j = bx + 2 by + 4 bz sits at (f + b) * ts and has
+// weight ((wx * wy) * wz), w = b ? r : 1 - r, every step rounded to float32 on its own.  rows[j][n] = the row of the set at the
+// corner (batch index = the integer part of the point's first column) or -1: no such voxel, a corner or batch index outside
+// the packable range (no probe: pack_key would wrap it onto another voxel), or a point with a non-finite entry -- whose
+// weights are 0 as well.
+__device__ __forceinline__ bool in_range_f(float v) { return v >= -16384.f && v < 16384.f; }
+__global__ __launch_bounds__(256) void interp_map_kernel(const float *__restrict__ points, int N, float ts,
+                                                         const unsigned long long *__restrict__ keys,
+                                                         const int *__restrict__ vals, unsigned mask, int *__restrict__ rows,
+                                                         float *__restrict__ weights)
+{
+    const int n = blockIdx.x * blockDim.x + threadIdx.x;
+    const int j = blockIdx.y;
+    if (n >= N || j >= 8) return;
+    const float4 p = reinterpret_cast<const float4 *>(points)[n];
+    int r = -1;
+    float w = 0.f;
+    if (isfinite(p.x) && isfinite(p.y) && isfinite(p.z) && isfinite(p.w)) {
+        const float qx = __fdiv_rn(p.y, ts), qy = __fdiv_rn(p.z, ts), qz = __fdiv_rn(p.w, ts);
+        const float fx = floorf(qx), fy = floorf(qy), fz = floorf(qz);
+        const float rx = __fsub_rn(qx, fx), ry = __fsub_rn(qy, fy), rz = __fsub_rn(qz, fz);
+        const int bx = j & 1, by = (j >> 1) & 1, bz = j >> 2;
+        const float wx = bx ? rx : __fsub_rn(1.f, rx), wy = by ? ry : __fsub_rn(1.f, ry), wz = bz ? rz : __fsub_rn(1.f, rz);
+        w = __fmul_rn(__fmul_rn(wx, wy), wz);
+        // (exact in float wherever the corner is in range; beyond 2^24 it is out of range whatever the rounding does)
+        const float cx = __fmul_rn(fx + (float)bx, ts), cy = __fmul_rn(fy + (float)by, ts), cz = __fmul_rn(fz + (float)bz, ts);
+        if (in_range_f(cx) && in_range_f(cy) && in_range_f(cz) && p.x >= 0.f && p.x < 524288.f)
+            r = table_lookup(keys, vals, mask, pack_key((int)p.x, (int)cx, (int)cy, (int)cz));
+    }
+    rows[(size_t)j * N + n] = r;
+    weights[(size_t)j * N + n] = w;
+}
+
 // nbr_inv[k][nbr[k][o]] = o: for one offset an input row feeds at most one output row (distinct output coordinates), so
 // the stores of one launch never meet; entries that name no row of [0, Vin) are skipped
 __global__ void kmap_invert_kernel(const int *__restrict__ nbr, int Vout, int Vin, int *__restrict__ nbr_inv)
@@ -756,6 +790,25 @@ int ms3d_kmap_general(const int *in_coords, int Vin, const int *out_coords, int 
     if (rc) return rc;
     dim3 grid(ms3d_divup(Vout, 256), K);
     kmap_general_kernel<<<grid, 256, 0, stream>>>(out_coords, Vout, offsets, K, w.keys, w.vals, (unsigned)w.H - 1u, nbr);
+    MS3D_LAUNCH_CHECK();
+    return 0;
+}
+
+int ms3d_interp_map(const int *coords, int Vin, const float *points, long N, int tensor_stride, int *rows, float *weights,
+                    void *workspace, size_t workspace_bytes, ms3d_stream_t stream_)
+{
+    hipStream_t stream = (hipStream_t)stream_;
+    if (tensor_stride < 1 || (tensor_stride & (tensor_stride - 1)) != 0) return MS3D_E_UNSUPPORTED;
+    if (N < 0 || N > 0x7fffffffL / 8 || Vin < 0) return MS3D_E_UNSUPPORTED;      // 8 N entries are numbered by ints
+    if (N == 0 || Vin == 0) return 0;
+    if (!coords || !points || !rows || !weights || !workspace) return MS3D_E_UNSUPPORTED;
+    CoordWs w;
+    if (carve(w, Vin, workspace) > workspace_bytes) return MS3D_E_WORKSPACE;
+    int rc = build_table(w, coords, Vin, 1, stream);
+    if (rc) return rc;
+    dim3 grid(ms3d_divup(N, 256), 8);
+    interp_map_kernel<<<grid, 256, 0, stream>>>(points, (int)N, (float)tensor_stride, w.keys, w.vals, (unsigned)w.H - 1u, rows,
+                                                weights);
     MS3D_LAUNCH_CHECK();
     return 0;
 }

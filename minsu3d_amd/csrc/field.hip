@@ -1,0 +1,262 @@
+// Points in, points out: the feature kernels of TensorField (points -> voxels), trilinear interpolation (voxels -> points)
+// and their gradients.  The maps they walk come from ms3d_sparse_quantize and ms3d_interp_map (coords.hip).
+//
+// Every direction is a GATHER with a single writer per output element, so nothing here adds floats atomically and a
+// training step stays bit-reproducible:
+//   interp forward    out[n]  = sum_j  w[j][n] * x[rows[j][n]]            the 8 corners in ascending j, one fmaf each
+//   interp backward   din[v]  = sum_e  w[e] * dout[point of e]            over the entries of voxel row v in ascending point
+//                                                                          (entry_sorted / seg_start: a stable sort of the
+//                                                                          table by row, built once per map by the caller)
+//   reduce forward    out[v]  = avg | sum | max over the points of voxel v in ascending point index (order / seg_start: a
+//                               stable sort of the point -> voxel map)
+//   reduce backward   dfeat[n] = dvox[inverse[n]] / count | as is | where arg == n
+// Layout as pool.hip: consecutive lanes take consecutive channels of one row (16 bytes per lane when C % 4 == 0 and the rows
+// are aligned, else one float), the table entry of a row is the same word for all of its lanes.  A voxel that holds
+// thousands of points is walked serially by its thread group: untuned.
+#include "common.h"
+#include "../../include/minsu3d_hip.h"
+
+namespace {
+
+enum { RED_AVG = 0, RED_SUM = 1, RED_MAX = 2 };
+
+template <int VEC>
+__device__ __forceinline__ void load_row(const float *__restrict__ p, size_t row, int C, int cv, float (&v)[VEC])
+{
+    if constexpr (VEC == 4) {
+        const float4 r = reinterpret_cast<const float4 *>(p + row * C)[cv];
+        v[0] = r.x; v[1] = r.y; v[2] = r.z; v[3] = r.w;
+    } else {
+        v[0] = p[row * C + cv];
+    }
+}
+
+template <int VEC>
+__device__ __forceinline__ void store_row(float *__restrict__ p, size_t row, int C, int cv, const float (&v)[VEC])
+{
+    if constexpr (VEC == 4)
+        reinterpret_cast<float4 *>(p + row * C)[cv] = make_float4(v[0], v[1], v[2], v[3]);
+    else
+        p[row * C + cv] = v[0];
+}
+
+// VEC = floats per lane; CV = C / VEC lanes per row
+template <int VEC>
+__global__ __launch_bounds__(256) void interp_forward_kernel(const float *__restrict__ x, const int *__restrict__ rows,
+                                                             const float *__restrict__ weights, int N, int C, int CV,
+                                                             float *__restrict__ out)
+{
+    const long t = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (t >= (long)N * CV) return;
+    const int n = (int)(t / CV), cv = (int)(t - (long)n * CV);
+    float acc[VEC];
+#pragma unroll
+    for (int c = 0; c < VEC; c++) acc[c] = 0.f;
+    for (int j = 0; j < 8; j++) {
+        const int r = rows[(size_t)j * N + n];
+        if (r < 0) continue;
+        const float w = weights[(size_t)j * N + n];
+        float v[VEC];
+        load_row<VEC>(x, (size_t)r, C, cv, v);
+#pragma unroll
+        for (int c = 0; c < VEC; c++) acc[c] = fmaf(w, v[c], acc[c]);
+    }
+    store_row<VEC>(out, (size_t)n, C, cv, acc);
+}
+
+// entry e = 8 * point + corner (the point-major numbering of the table); its weight sits at weights[corner][point]
+template <int VEC>
+__global__ __launch_bounds__(256) void interp_backward_kernel(const float *__restrict__ dout, const float *__restrict__ weights,
+                                                              const long long *__restrict__ entry_sorted,
+                                                              const int *__restrict__ seg_start, int Vin, int N, int C, int CV,
+                                                              float *__restrict__ din)
+{
+    const long t = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (t >= (long)Vin * CV) return;
+    const int v = (int)(t / CV), cv = (int)(t - (long)v * CV);
+    float acc[VEC];
+#pragma unroll
+    for (int c = 0; c < VEC; c++) acc[c] = 0.f;
+    const int end = seg_start[v + 1];
+    for (int s = seg_start[v]; s < end; s++) {
+        const long long e = entry_sorted[s];
+        const long long n = e >> 3;
+        const int j = (int)(e & 7);
+        if (n < 0 || n >= N) continue;           // (a grouping that names no point of this map: nothing is read)
+        const float w = weights[(size_t)j * N + (size_t)n];
+        float g[VEC];
+        load_row<VEC>(dout, (size_t)n, C, cv, g);
+#pragma unroll
+        for (int c = 0; c < VEC; c++) acc[c] = fmaf(w, g[c], acc[c]);
+    }
+    store_row<VEC>(din, (size_t)v, C, cv, acc);
+}
+
+template <int MODE, int VEC>
+__global__ __launch_bounds__(256) void field_reduce_kernel(const float *__restrict__ feats, const long long *__restrict__ order,
+                                                           const int *__restrict__ seg_start, int V, int C, int CV,
+                                                           float *__restrict__ out, int *__restrict__ arg)
+{
+    const long t = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (t >= (long)V * CV) return;
+    const int v = (int)(t / CV), cv = (int)(t - (long)v * CV);
+    float acc[VEC];
+    int win[VEC];
+#pragma unroll
+    for (int c = 0; c < VEC; c++) { acc[c] = 0.f; win[c] = -1; }
+    const int begin = seg_start[v], end = seg_start[v + 1];
+    for (int s = begin; s < end; s++) {
+        const long long n = order[s];
+        float f[VEC];
+        load_row<VEC>(feats, (size_t)n, C, cv, f);
+#pragma unroll
+        for (int c = 0; c < VEC; c++) {
+            if constexpr (MODE == RED_MAX) {
+                if (s == begin || f[c] > acc[c]) { acc[c] = f[c]; win[c] = (int)n; }
+            } else {
+                acc[c] += f[c];
+            }
+        }
+    }
+    if constexpr (MODE == RED_AVG) {
+        if (end > begin) {
+            const float cnt = (float)(end - begin);
+#pragma unroll
+            for (int c = 0; c < VEC; c++) acc[c] = acc[c] / cnt;
+        }
+    }
+    store_row<VEC>(out, (size_t)v, C, cv, acc);
+    if constexpr (MODE == RED_MAX) {
+        if constexpr (VEC == 4)
+            reinterpret_cast<int4 *>(arg + (size_t)v * C)[cv] = make_int4(win[0], win[1], win[2], win[3]);
+        else
+            arg[(size_t)v * C + cv] = win[0];
+    }
+}
+
+template <int MODE, int VEC>
+__global__ __launch_bounds__(256) void field_reduce_backward_kernel(const float *__restrict__ dvox, const int *__restrict__ inverse,
+                                                                    const int *__restrict__ seg_start,
+                                                                    const int *__restrict__ arg, int N, int C, int CV,
+                                                                    float *__restrict__ dfeat)
+{
+    const long t = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (t >= (long)N * CV) return;
+    const int n = (int)(t / CV), cv = (int)(t - (long)n * CV);
+    const int v = inverse[n];
+    float g[VEC];
+    load_row<VEC>(dvox, (size_t)v, C, cv, g);
+    if constexpr (MODE == RED_AVG) {
+        const float cnt = (float)(seg_start[v + 1] - seg_start[v]);      // >= 1: point n itself lies in voxel v
+#pragma unroll
+        for (int c = 0; c < VEC; c++) g[c] = g[c] / cnt;
+    } else if constexpr (MODE == RED_MAX) {
+        int w[VEC];
+        if constexpr (VEC == 4) {
+            const int4 a = reinterpret_cast<const int4 *>(arg + (size_t)v * C)[cv];
+            w[0] = a.x; w[1] = a.y; w[2] = a.z; w[3] = a.w;
+        } else {
+            w[0] = arg[(size_t)v * C + cv];
+        }
+#pragma unroll
+        for (int c = 0; c < VEC; c++) g[c] = (w[c] == n) ? g[c] : 0.f;
+    }
+    store_row<VEC>(dfeat, (size_t)n, C, cv, g);
+}
+
+bool vec4(int C, const void *a, const void *b, const void *c = nullptr)
+{
+    return C % 4 == 0 && (((uintptr_t)a | (uintptr_t)b | (uintptr_t)c) & 15) == 0;
+}
+
+// grid of one thread per (row, lane of the row); false when it does not fit a launch
+bool grid_of(long rows, int CV, unsigned *blocks)
+{
+    const long b = (rows * CV + 255) / 256;
+    if (b > 0x7fffffffL) return false;
+    *blocks = (unsigned)b;
+    return true;
+}
+
+}  // namespace
+
+extern "C" {
+
+int ms3d_interp_forward(const float *x, const int *rows, const float *weights, long N, int C, float *out, ms3d_stream_t stream_)
+{
+    hipStream_t stream = (hipStream_t)stream_;
+    if (C < 1 || N < 0 || N > 0x7fffffffL / 8) return MS3D_E_UNSUPPORTED;
+    if (N == 0) return 0;
+    if (!x || !rows || !weights || !out) return MS3D_E_UNSUPPORTED;
+    const bool v4 = vec4(C, x, out);
+    const int CV = v4 ? C / 4 : C;
+    unsigned blocks;
+    if (!grid_of(N, CV, &blocks)) return MS3D_E_UNSUPPORTED;
+    if (v4) interp_forward_kernel<4><<<blocks, 256, 0, stream>>>(x, rows, weights, (int)N, C, CV, out);
+    else interp_forward_kernel<1><<<blocks, 256, 0, stream>>>(x, rows, weights, (int)N, C, CV, out);
+    MS3D_LAUNCH_CHECK();
+    return 0;
+}
+
+int ms3d_interp_backward(const float *dout, const float *weights, const long long *entry_sorted, const int *seg_start, long Vin,
+                         long N, int C, float *din, ms3d_stream_t stream_)
+{
+    hipStream_t stream = (hipStream_t)stream_;
+    if (C < 1 || N < 0 || N > 0x7fffffffL / 8 || Vin < 0 || Vin > 0x7fffffffL) return MS3D_E_UNSUPPORTED;
+    if (Vin == 0) return 0;
+    if (!seg_start || !din || (N > 0 && (!dout || !weights || !entry_sorted))) return MS3D_E_UNSUPPORTED;
+    const bool v4 = vec4(C, dout, din);
+    const int CV = v4 ? C / 4 : C;
+    unsigned blocks;
+    if (!grid_of(Vin, CV, &blocks)) return MS3D_E_UNSUPPORTED;
+    if (v4) interp_backward_kernel<4><<<blocks, 256, 0, stream>>>(dout, weights, entry_sorted, seg_start, (int)Vin, (int)N, C, CV, din);
+    else interp_backward_kernel<1><<<blocks, 256, 0, stream>>>(dout, weights, entry_sorted, seg_start, (int)Vin, (int)N, C, CV, din);
+    MS3D_LAUNCH_CHECK();
+    return 0;
+}
+
+int ms3d_field_reduce(int mode, const float *feats, const long long *order, const int *seg_start, long V, int C, float *out,
+                      int *arg, ms3d_stream_t stream_)
+{
+    hipStream_t stream = (hipStream_t)stream_;
+    if (mode < RED_AVG || mode > RED_MAX || C < 1 || V < 0 || V > 0x7fffffffL) return MS3D_E_UNSUPPORTED;
+    if (V == 0) return 0;
+    if (!feats || !order || !seg_start || !out || (mode == RED_MAX && !arg)) return MS3D_E_UNSUPPORTED;
+    const bool v4 = vec4(C, feats, out, mode == RED_MAX ? arg : nullptr);
+    const int CV = v4 ? C / 4 : C;
+    unsigned blocks;
+    if (!grid_of(V, CV, &blocks)) return MS3D_E_UNSUPPORTED;
+#define MS3D_FIELD_RED(M)                                                                                              \
+    if (v4) field_reduce_kernel<M, 4><<<blocks, 256, 0, stream>>>(feats, order, seg_start, (int)V, C, CV, out, arg);     \
+    else field_reduce_kernel<M, 1><<<blocks, 256, 0, stream>>>(feats, order, seg_start, (int)V, C, CV, out, arg);
+    if (mode == RED_AVG) { MS3D_FIELD_RED(RED_AVG) }
+    else if (mode == RED_SUM) { MS3D_FIELD_RED(RED_SUM) }
+    else { MS3D_FIELD_RED(RED_MAX) }
+#undef MS3D_FIELD_RED
+    MS3D_LAUNCH_CHECK();
+    return 0;
+}
+
+int ms3d_field_reduce_backward(int mode, const float *dvox, const int *inverse, const int *seg_start, const int *arg, long N,
+                               int C, float *dfeat, ms3d_stream_t stream_)
+{
+    hipStream_t stream = (hipStream_t)stream_;
+    if (mode < RED_AVG || mode > RED_MAX || C < 1 || N < 0 || N > 0x7fffffffL) return MS3D_E_UNSUPPORTED;
+    if (N == 0) return 0;
+    if (!dvox || !inverse || !dfeat || (mode == RED_AVG && !seg_start) || (mode == RED_MAX && !arg)) return MS3D_E_UNSUPPORTED;
+    const bool v4 = vec4(C, dvox, dfeat, mode == RED_MAX ? arg : nullptr);
+    const int CV = v4 ? C / 4 : C;
+    unsigned blocks;
+    if (!grid_of(N, CV, &blocks)) return MS3D_E_UNSUPPORTED;
+#define MS3D_FIELD_RED_BWD(M)                                                                                                    \
+    if (v4) field_reduce_backward_kernel<M, 4><<<blocks, 256, 0, stream>>>(dvox, inverse, seg_start, arg, (int)N, C, CV, dfeat);   \
+    else field_reduce_backward_kernel<M, 1><<<blocks, 256, 0, stream>>>(dvox, inverse, seg_start, arg, (int)N, C, CV, dfeat);
+    if (mode == RED_AVG) { MS3D_FIELD_RED_BWD(RED_AVG) }
+    else if (mode == RED_SUM) { MS3D_FIELD_RED_BWD(RED_SUM) }
+    else { MS3D_FIELD_RED_BWD(RED_MAX) }
+#undef MS3D_FIELD_RED_BWD
+    MS3D_LAUNCH_CHECK();
+    return 0;
+}
+
+}  // extern "C"
