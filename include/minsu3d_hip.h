@@ -291,6 +291,26 @@ int ms3d_pool_forward(int mode, const float *in, const int *nbr, int Vout, int K
 int ms3d_pool_backward(int mode, const float *dout, const int *nbr_inv, int Vin, int K, int C, const unsigned char *arg,
                        const int *count, float *din, ms3d_stream_t stream);
 
+/* ---- channel-wise (depthwise) convolution over a kernel map (csrc/chconv.hip; float32, any C; 16-byte row accesses when
+ * C % 4 == 0 and the rows are 16-byte aligned, scalar otherwise -- both give the same bits forward).  w [K][C], K <= 254.
+ * forward: out[o][c] = (bias ? bias[c] : 0) + sum over the PRESENT inputs in ascending k of w[k][c] * in[nbr[k][o]][c].
+ * backward-data is the same call: din = ms3d_chconv_forward(dout, w, NULL, nbr_inv, Vin, ...) through the inverse table
+ * (nbr_inv[k][i] = the output row that input i feeds through offset k: the offset index is NOT mirrored).
+ * backward-weight: dW[k][c] = sum_o in[nbr[k][o]][c] * dout[o][c] in two stages without atomics: one [K][C] partial per run
+ * of ms3d_chconv_wgrad_rows_per_part() consecutive output rows (a constant of the library, independent of the device, so the
+ * order of the sum is too), then the partials added in ascending part order.  partial_ws: ms3d_chconv_wgrad_ws_floats(Vout,
+ * K, C) = ms3d_chconv_wgrad_parts(Vout) * K * C floats, parts = ceil(Vout / rows_per_part) (pure host arithmetic; 0 for
+ * Vout <= 0).  The bias gradient is ms3d_column_sum(dout).
+ * K < 1, K > 254 or C < 1: MS3D_E_UNSUPPORTED.  Vout <= 0: 0, nothing is launched (dW is not written).  Every direction is
+ * bit-reproducible. */
+int ms3d_chconv_forward(const float *in, const float *w, const float *bias, const int *nbr, int Vout, int K, int C, float *out,
+                        ms3d_stream_t stream);
+int ms3d_chconv_backward_weight(const float *in, const float *dout, const int *nbr, int Vout, int K, int C, float *partial_ws,
+                                float *dW, ms3d_stream_t stream);
+int ms3d_chconv_wgrad_rows_per_part(void);
+int ms3d_chconv_wgrad_parts(int Vout);
+size_t ms3d_chconv_wgrad_ws_floats(int Vout, int K, int C);
+
 /* ---- points <-> voxels: TensorField quantisation and trilinear interpolation (csrc/field.hip; the map: csrc/coords.hip).
  * float32, any C; 16-byte row accesses when C % 4 == 0 and the rows are 16-byte aligned.  Every direction is a gather with one
  * writer per output element: no float atomics, the same bytes on every run.  Contracts shared by the five entry points,

@@ -31,6 +31,11 @@ Points in, points out -- how a network gets from a point cloud to voxels and bac
     SparseTensor.slice / .cat_slice / .interpolate, MinkowskiInterpolation, MinkowskiPoolingTranspose
     (+ CoordinateManager.interpolation_map: engine extra)
 
+The depthwise layer of separable blocks, ConvNeXt-style sparse backbones and large-kernel context blocks:
+
+    MinkowskiChannelwiseConvolution  (kernel (K, C), bias (1, C); the convolutions' geometries; float32 HIP gather kernels,
+    csrc/chconv.hip; outside prepare_conv_weights: it is not a dense-weight convolution)
+
 Not supported (each raises NotImplementedError naming it): strides other than 1 and 2, a generative layer at stride 2 on an odd
 tensor stride, MinkowskiConvolutionTranspose onto a coordinate set that is not cached, convolutions (expand_coordinates) or
 pooling that create coordinates, `+=` and ME.cat across different coordinate sets, a union of more than 16 tensors,
@@ -50,7 +55,7 @@ from .modules import (MinkowskiConvolution, MinkowskiConvolutionTranspose, Minko
                       MinkowskiGenerativeConvolutionTranspose, MinkowskiPruning,
                       MinkowskiUnion, MinkowskiBroadcastAddition, MinkowskiBroadcastMultiplication,
                       MinkowskiBroadcastConcatenation, MinkowskiBroadcast, MinkowskiSigmoid,
-                      MinkowskiPoolingTranspose, MinkowskiInterpolation)
+                      MinkowskiPoolingTranspose, MinkowskiInterpolation, MinkowskiChannelwiseConvolution)
 from .tensor import kernel_offsets  # noqa: F401  (engine extra: the offset list of a kernel, in weight order)
 from .functional import gather_rows  # noqa: F401  (engine extra: x[idx] with a scatter-add backward)
 from .functional import SkipLink  # noqa: F401  (engine extra: a residual block's skip gradient, see functional.py)

@@ -570,6 +570,38 @@ def sparse_pool(x, nbr_fwd, nbr_inv, vin, vout, K, mode):
     return SparsePoolFn.apply(x, nbr_fwd, nbr_inv, vin, vout, K, mode)
 
 
+class ChannelwiseConvFn(torch.autograd.Function):
+    """y[o, c] = bias[c] + sum_k w[k, c] * x[nbr_fwd[k][o], c] over the present inputs (csrc/chconv.hip; float32, no matmul).
+    Backward-data is the forward kernel through the inverse table with the same w (no mirrored offsets), backward-weight a
+    two-stage reduction in a fixed order, the bias gradient a column sum: no atomics, the same bytes on every run.  A frozen
+    kernel skips the weight pass, an input without grad the data pass."""
+
+    @staticmethod
+    def forward(ctx, x, w, bias, nbr_fwd, nbr_inv, vin, vout, K):
+        be = get_backend()
+        if not hasattr(be, "chconv_forward"):
+            raise NotImplementedError("channel-wise convolution needs the HIP backend (ms3d_chconv_forward)")
+        x = x.contiguous()
+        ctx.save_for_backward(x, w)
+        ctx.geom = (nbr_fwd, nbr_inv, vin, vout, K, None if bias is None else tuple(bias.shape))
+        return be.chconv_forward(x, w, bias, nbr_fwd, vout, K)
+
+    @staticmethod
+    def backward(ctx, dy):
+        x, w = ctx.saved_tensors
+        nbr_fwd, nbr_inv, vin, vout, K, bias_shape = ctx.geom
+        be = get_backend()
+        dy = dy.contiguous()
+        dx = be.chconv_forward(dy, w, None, nbr_inv, vin, K) if ctx.needs_input_grad[0] else None
+        dw = be.chconv_backward_weight(x, dy, nbr_fwd, vout, K).view_as(w) if ctx.needs_input_grad[1] else None
+        db = be.column_sum(dy).view(bias_shape) if bias_shape is not None and ctx.needs_input_grad[2] else None
+        return dx, dw, db, None, None, None, None, None
+
+
+def channelwise_conv(x, w, bias, nbr_fwd, nbr_inv, vin, vout, K):
+    return ChannelwiseConvFn.apply(x, w, bias, nbr_fwd, nbr_inv, vin, vout, K)
+
+
 class UnionCombineFn(torch.autograd.Function):
     """out [n_out, C] = combine of the operands' rows on the union of their coordinate sets (op 0 sum of any number, 1
     subtract, 2 multiply of two; csrc/setops.hip).  maps: per operand (in_row int32 [n_out]: union row -> operand row in the

@@ -226,6 +226,48 @@ class MinkowskiGenerativeConvolutionTranspose(_ConvBase):
         return SparseTensor(y, coordinate_manager=out_cm, tensor_stride=out_ts, _stats=stats)
 
 
+class MinkowskiChannelwiseConvolution(nn.Module):
+    """Depthwise convolution: out[o, c] = bias[c] + sum_k kernel[k, c] * in[nbr[k][o], c] over the inputs present, offsets in
+    kernel_offsets() order (x fastest).  `kernel` has shape (K, in_channels), K = kernel_size ** 3 -- (1, in_channels) for
+    kernel size 1, always 2-D -- and `bias`, when asked for, (1, in_channels); both are initialised uniform(-s, s) with
+    s = 1 / sqrt(in_channels * K), the rule of the dense-weight convolutions.  The geometries are the convolutions': stride 1
+    with an odd kernel on the same coordinate set, stride 2 onto the stride-2 set, any dilation.  A pending BatchNorm / ReLU in
+    front is materialised first.  The arithmetic is float32 always (there is no matrix product for
+    torch.set_float32_matmul_precision to act on).
+
+    Not a _ConvBase: prepare_conv_weights lays out (K, cin, cout) weight images and deferred backward-weight groups for every
+    _ConvBase, and a (K, C) kernel has no place in either."""
+
+    def __init__(self, in_channels, kernel_size=-1, stride=1, dilation=1, bias=False, dimension=3):
+        super().__init__()
+        if dimension != 3:
+            raise NotImplementedError(f"dimension={dimension}: only 3-D sparse tensors are supported")
+        check_geometry(kernel_size, stride, dilation)
+        self.in_channels = self.out_channels = in_channels
+        self.kernel_size, self.stride, self.dilation = kernel_size, stride, dilation
+        K = kernel_size ** 3
+        self.kernel_volume = K
+        self.kernel = nn.Parameter(torch.empty((K, in_channels), dtype=torch.float32))
+        self.bias = nn.Parameter(torch.empty((1, in_channels), dtype=torch.float32)) if bias else None
+        s = 1.0 / math.sqrt(in_channels * K)
+        with torch.no_grad():
+            self.kernel.uniform_(-s, s)
+            if bias:
+                self.bias.uniform_(-s, s)
+
+    def forward(self, x: SparseTensor):
+        cm, ts = x.coordinate_manager, x.tensor_stride
+        geom = (self.kernel_size, self.stride, self.dilation)
+        nbr_fwd, _, vin, vout, K, out_ts, _ = cm.kernel_map(ts, *geom)
+        nbr_inv = cm.kernel_map_inverse(ts, *geom)
+        y = Fn.channelwise_conv(x._raw(), self.kernel, self.bias, nbr_fwd, nbr_inv, vin, vout, K)
+        return x._like(y, tensor_stride=out_ts)
+
+    def extra_repr(self):
+        return (f"in={self.in_channels}, kernel_size={self.kernel_size}, stride={self.stride}, dilation={self.dilation}, "
+                f"bias={self.bias is not None}")
+
+
 class MinkowskiPruning(nn.Module):
     """forward(x, mask): the rows of x whose entry of the bool mask [V] is set -- mask in the order of x.features /
     x.coordinates -- on a coordinate manager of their own, rooted at x's tensor stride.  .features is x.features[mask] and

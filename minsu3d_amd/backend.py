@@ -1055,6 +1055,39 @@ class _HipEngine:
                    "ms3d_pool_backward")
         return din
 
+    # ---- channel-wise convolution over a kernel map (csrc/chconv.hip)
+    def chconv_forward(self, x, w, bias, nbr, vout, K):
+        """out [vout, C] = bias + sum_k w[k] * x[nbr[k]] over the present inputs; w [K, C], bias [C] / [1, C] or None.
+        Backward-data is this call with dout, the inverse table and no bias."""
+        x = self._dev(x).contiguous()
+        w = self._dev(w).contiguous()
+        assert x.dtype == torch.float32 and x.dim() == 2 and w.dtype == torch.float32
+        c = x.size(1)
+        assert w.numel() == K * c and nbr.dtype == torch.int32 and nbr.numel() == K * vout
+        if bias is not None:
+            bias = self._dev(bias).contiguous()
+            assert bias.dtype == torch.float32 and bias.numel() == c
+        out = torch.empty((vout, c), dtype=torch.float32, device=x.device)
+        _lib.check(self.lib.ms3d_chconv_forward(_lib.ptr(x), _lib.ptr(w), _lib.ptr(bias), _lib.ptr(nbr), int(vout), int(K), int(c),
+                                                _lib.ptr(out), _lib.stream_handle()), "ms3d_chconv_forward")
+        return out
+
+    def chconv_backward_weight(self, x, dout, nbr, vout, K):
+        """dW [K, C] = sum_o x[nbr[k][o]] * dout[o]: one partial per fixed run of output rows, summed in part order"""
+        x = self._dev(x).contiguous()
+        dout = self._dev(dout).contiguous()
+        assert x.dtype == torch.float32 and x.dim() == 2 and dout.dtype == torch.float32 and dout.dim() == 2
+        c = x.size(1)
+        assert tuple(dout.shape) == (vout, c) and nbr.dtype == torch.int32 and nbr.numel() == K * vout
+        if vout <= 0:
+            return torch.zeros((K, c), dtype=torch.float32, device=x.device)
+        dW = torch.empty((K, c), dtype=torch.float32, device=x.device)
+        ws = self.ws.get("chconv_wgrad", 4 * self.lib.ms3d_chconv_wgrad_ws_floats(int(vout), int(K), int(c)), x.device)
+        _lib.check(self.lib.ms3d_chconv_backward_weight(_lib.ptr(x), _lib.ptr(dout), _lib.ptr(nbr), int(vout), int(K), int(c),
+                                                        _lib.ptr(ws), _lib.ptr(dW), _lib.stream_handle()),
+                   "ms3d_chconv_backward_weight")
+        return dW
+
     # ---- points <-> voxels (csrc/field.hip; the interpolation map: csrc/coords.hip)
     def interp_map(self, coords, points, tensor_stride):
         """the eight corners of every point in the coordinate set `coords` (int32 [V, 4], tensor stride `tensor_stride`) ->
