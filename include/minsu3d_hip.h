@@ -311,6 +311,40 @@ int ms3d_chconv_wgrad_rows_per_part(void);
 int ms3d_chconv_wgrad_parts(int Vout);
 size_t ms3d_chconv_wgrad_ws_floats(int Vout, int K, int C);
 
+/* ---- instance normalisation: per batch index (segment) and channel (csrc/inorm.hip; float32 rows and parameters, any C >= 1;
+ * every sum, the statistics mean / invstd (DOUBLE [B, C]) and the arithmetic of the row passes are float64, rounded once at the
+ * store: with few rows in a segment dx is a difference of nearly equal terms that float32 statistics cannot resolve; a lane takes four
+ * channels of a row -- one 16-byte access when C % 4 == 0 and every pointer is 16-byte aligned, four guarded 4-byte accesses
+ * otherwise; both routes run the same arithmetic in the same order and give the same bits).  The rows of segment s are
+ * order[seg_start[s] .. seg_start[s + 1]) (int64 rows, int32 offsets [B + 1]: CoordinateManager.batch_rows, one segment per
+ * batch index present), n_s of them; seg_of_row int32 [V] names the segment of every held row (CoordinateManager.
+ * batch_segments).  Rows are read and written where they lie: no permuted copy of x is made.
+ * forward:  mean[s][c] = (1/n_s) sum_r x[r][c];  var[s][c] = (1/n_s) sum_r (x[r][c] - mean[s][c])^2 (biased);
+ *           invstd[s][c] = 1 / sqrt(var[s][c] + eps);  y[r][c] = (x[r][c] - mean[s][c]) * invstd[s][c] * weight[c] + bias[c].
+ * backward: xhat = (x - mean) * invstd recomputed from the saved x, mean, invstd;  S1[s][c] = sum_r dy[r][c];
+ *           S2[s][c] = sum_r dy[r][c] * xhat[r][c];  dx[r][c] = weight[c] * invstd[s][c] * (dy[r][c] - S1[s][c] / n_s -
+ *           xhat[r][c] * S2[s][c] / n_s);  dweight[c] = sum_s S2[s][c], dbias[c] = sum_s S1[s][c] in ascending s.
+ * weight / bias may be NULL (1 / 0); dx, dweight, dbias may each be NULL (skipped; all three NULL: nothing is launched).
+ * Order of summation (the scheme of ms3d_broadcast_reduce): a segment is cut into ms3d_inorm_slices() slices of ceil(n_s /
+ * slices) consecutive positions of `order`; a workgroup sums one slice, each thread its rows in ascending order, the threads
+ * of a column in ascending order; a second kernel merges the slice partials in ascending slice order, skipping empty
+ * slices.  The slice count is a constant of the library, not of the device: no float atomics, no dependence on the CU count,
+ * the same bytes on every run.  The statistics are NOT E[x^2] - E[x]^2 of the raw values: a slice sums (x - K) and (x - K)^2
+ * with K = its first row and hands on (n, mean, M2), the merge is Chan's (delta = mean_b - mean_a; mean += delta n_b / n;
+ * M2 += M2_b + delta^2 n_a n_b / n).  A segment of one row gives y = bias and dx = 0 exactly.
+ * workspace: ms3d_inorm_workspace_bytes(B, C) = 8 * 2 * B * (slices + 1) * C bytes (doubles) for either direction (pure host
+ * arithmetic; 0 for B <= 0 or C < 1); less: MS3D_E_WORKSPACE.  C < 1 or B > 65535: MS3D_E_UNSUPPORTED, as is a NULL pointer
+ * that would be read or written.  V <= 0 or B <= 0: 0, nothing is launched (dweight / dbias are then not written). */
+int ms3d_inorm_slices(void);
+size_t ms3d_inorm_workspace_bytes(int B, int C);
+int ms3d_inorm_forward(const float *x, long V, int C, const long long *order, const int *seg_start, int B,
+                       const int *seg_of_row, float eps, const float *weight, const float *bias, double *mean /*[B, C]*/,
+                       double *invstd /*[B, C]*/, float *y, void *workspace, size_t workspace_bytes, ms3d_stream_t stream);
+int ms3d_inorm_backward(const float *dy, const float *x, long V, int C, const long long *order, const int *seg_start, int B,
+                        const int *seg_of_row, const double *mean, const double *invstd, const float *weight, float *dx,
+                        float *dweight /*[C]*/, float *dbias /*[C]*/, void *workspace, size_t workspace_bytes,
+                        ms3d_stream_t stream);
+
 /* ---- points <-> voxels: TensorField quantisation and trilinear interpolation (csrc/field.hip; the map: csrc/coords.hip).
  * float32, any C; 16-byte row accesses when C % 4 == 0 and the rows are 16-byte aligned.  Every direction is a gather with one
  * writer per output element: no float atomics, the same bytes on every run.  Contracts shared by the five entry points,

@@ -36,6 +36,15 @@ The depthwise layer of separable blocks, ConvNeXt-style sparse backbones and lar
     MinkowskiChannelwiseConvolution  (kernel (K, C), bias (1, C); the convolutions' geometries; float32 HIP gather kernels,
     csrc/chconv.hip; outside prepare_conv_weights: it is not a dense-weight convolution)
 
+Normalisation per sample and the activations of the decoders, generators and registration networks that use it:
+
+    MinkowskiInstanceNorm (eps 1e-8), MinkowskiStableInstanceNorm (eps 1e-6): `weight`, `bias` of shape (1, C), no running
+    statistics; per batch index and channel, biased variance; segmented HIP reductions in a fixed order, shifted sums merged
+    by Chan's formula (csrc/inorm.hip); rows read where they are held  (+ CoordinateManager.batch_segments: engine extra)
+    MinkowskiELU, MinkowskiLeakyReLU, MinkowskiPReLU, MinkowskiSELU, MinkowskiCELU, MinkowskiGELU, MinkowskiSiLU,
+    MinkowskiTanh, MinkowskiSoftplus, MinkowskiHardswish, MinkowskiHardtanh, MinkowskiReLU6, MinkowskiSoftmax,
+    MinkowskiLogSoftmax: the torch operator as `self.module`, applied to the rows
+
 Not supported (each raises NotImplementedError naming it): strides other than 1 and 2, a generative layer at stride 2 on an odd
 tensor stride, MinkowskiConvolutionTranspose onto a coordinate set that is not cached, convolutions (expand_coordinates) or
 pooling that create coordinates, `+=` and ME.cat across different coordinate sets, a union of more than 16 tensors,
@@ -55,7 +64,11 @@ from .modules import (MinkowskiConvolution, MinkowskiConvolutionTranspose, Minko
                       MinkowskiGenerativeConvolutionTranspose, MinkowskiPruning,
                       MinkowskiUnion, MinkowskiBroadcastAddition, MinkowskiBroadcastMultiplication,
                       MinkowskiBroadcastConcatenation, MinkowskiBroadcast, MinkowskiSigmoid,
-                      MinkowskiPoolingTranspose, MinkowskiInterpolation, MinkowskiChannelwiseConvolution)
+                      MinkowskiPoolingTranspose, MinkowskiInterpolation, MinkowskiChannelwiseConvolution,
+                      MinkowskiInstanceNorm, MinkowskiStableInstanceNorm,
+                      MinkowskiELU, MinkowskiLeakyReLU, MinkowskiPReLU, MinkowskiSELU, MinkowskiCELU, MinkowskiGELU,
+                      MinkowskiSiLU, MinkowskiTanh, MinkowskiSoftplus, MinkowskiHardswish, MinkowskiHardtanh,
+                      MinkowskiReLU6, MinkowskiSoftmax, MinkowskiLogSoftmax)
 from .tensor import kernel_offsets  # noqa: F401  (engine extra: the offset list of a kernel, in weight order)
 from .functional import gather_rows  # noqa: F401  (engine extra: x[idx] with a scatter-add backward)
 from .functional import SkipLink  # noqa: F401  (engine extra: a residual block's skip gradient, see functional.py)

@@ -602,6 +602,44 @@ def channelwise_conv(x, w, bias, nbr_fwd, nbr_inv, vin, vout, K):
     return ChannelwiseConvFn.apply(x, w, bias, nbr_fwd, nbr_inv, vin, vout, K)
 
 
+class InstanceNormFn(torch.autograd.Function):
+    """y[r, c] = (x[r, c] - mean[s, c]) * invstd[s, c] * weight[c] + bias[c] with the statistics of the row's segment s (its
+    batch index) and the biased variance (csrc/inorm.hip).  group = (order, seg_start, seg_of_row): CoordinateManager.
+    batch_rows' grouping and batch_segments; the rows are read where they are held, nothing is permuted.  Every sum runs in one
+    fixed order without atomics: the same bytes on every run; sums and statistics (mean, invstd: float64 [B, C]) are double, the
+    rows float32.  A frozen affine skips dweight / dbias, an input without grad
+    skips dx."""
+
+    @staticmethod
+    def forward(ctx, x, weight, bias, group, eps):
+        be = get_backend()
+        if not hasattr(be, "inorm_forward"):
+            raise NotImplementedError("instance normalisation needs the HIP backend (ms3d_inorm_forward)")
+        order, seg_start, seg_of_row = group
+        x = x.contiguous()
+        y, mean, invstd = be.inorm_forward(x, order, seg_start, seg_of_row, eps, weight, bias)
+        ctx.save_for_backward(x, mean, invstd, weight)
+        ctx.group = group
+        ctx.shapes = (None if weight is None else tuple(weight.shape), None if bias is None else tuple(bias.shape))
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        x, mean, invstd, weight = ctx.saved_tensors
+        order, seg_start, seg_of_row = ctx.group
+        w_shape, b_shape = ctx.shapes
+        need_x = ctx.needs_input_grad[0]
+        need_w = w_shape is not None and ctx.needs_input_grad[1]
+        need_b = b_shape is not None and ctx.needs_input_grad[2]
+        dx, dw, db = get_backend().inorm_backward(dy.contiguous(), x, order, seg_start, seg_of_row, mean, invstd, weight,
+                                                  need_x, need_w, need_b)
+        return dx, dw.view(w_shape) if need_w else None, db.view(b_shape) if need_b else None, None, None
+
+
+def instance_norm(x, weight, bias, group, eps):
+    return InstanceNormFn.apply(x, weight, bias, group, eps)
+
+
 class UnionCombineFn(torch.autograd.Function):
     """out [n_out, C] = combine of the operands' rows on the union of their coordinate sets (op 0 sum of any number, 1
     subtract, 2 multiply of two; csrc/setops.hip).  maps: per operand (in_row int32 [n_out]: union row -> operand row in the

@@ -530,6 +530,125 @@ class MinkowskiSigmoid(nn.Module):
         return x._like(torch.sigmoid(x._raw()))
 
 
+class _NonlinearityBase(nn.Module):
+    """MODULE(*args, **kwargs) of torch.nn kept as `self.module` (MinkowskiEngine's layout, so a parameter of the operator keeps
+    its key: MinkowskiPReLU's is `module.weight`) and applied to the rows; a pending BatchNorm / ReLU in front is materialised
+    first, the result lives on the input's coordinate set.  Plain torch operators: rows are independent, no kernel of the
+    engine's own is involved.  A TensorField passes through the same way."""
+    MODULE = None
+
+    def __init__(self, *args, **kwargs):
+        super().__init__()
+        self.module = self.MODULE(*args, **kwargs)
+
+    def forward(self, x):
+        return x._like(self.module(x._raw() if isinstance(x, SparseTensor) else x.F))
+
+    def __repr__(self):
+        return type(self).__name__ + "(" + self.module.extra_repr() + ")"
+
+
+class MinkowskiELU(_NonlinearityBase):
+    MODULE = nn.ELU
+
+
+class MinkowskiLeakyReLU(_NonlinearityBase):
+    MODULE = nn.LeakyReLU
+
+
+class MinkowskiPReLU(_NonlinearityBase):
+    MODULE = nn.PReLU
+
+
+class MinkowskiSELU(_NonlinearityBase):
+    MODULE = nn.SELU
+
+
+class MinkowskiCELU(_NonlinearityBase):
+    MODULE = nn.CELU
+
+
+class MinkowskiGELU(_NonlinearityBase):
+    MODULE = nn.GELU
+
+
+class MinkowskiSiLU(_NonlinearityBase):
+    MODULE = nn.SiLU
+
+
+class MinkowskiTanh(_NonlinearityBase):
+    MODULE = nn.Tanh
+
+
+class MinkowskiSoftplus(_NonlinearityBase):
+    MODULE = nn.Softplus
+
+
+class MinkowskiHardswish(_NonlinearityBase):
+    MODULE = nn.Hardswish
+
+
+class MinkowskiHardtanh(_NonlinearityBase):
+    MODULE = nn.Hardtanh
+
+
+class MinkowskiReLU6(_NonlinearityBase):
+    MODULE = nn.ReLU6
+
+
+class MinkowskiSoftmax(_NonlinearityBase):
+    MODULE = nn.Softmax
+
+
+class MinkowskiLogSoftmax(_NonlinearityBase):
+    MODULE = nn.LogSoftmax
+
+
+class MinkowskiInstanceNorm(nn.Module):
+    """normalisation per sample: every channel of the rows of ONE batch index is shifted to mean 0 and scaled to variance 1
+    (biased variance, as torch's instance_norm), then times `weight` plus `bias` -- both (1, num_features), ones and zeros,
+    state-dict keys `weight` and `bias`.  No running statistics: train() and eval() do the same.  The result lives on the
+    input's coordinate set and tensor stride; a pending BatchNorm / ReLU in front is materialised first.
+
+    `eps` as a keyword is an engine extra.  The default 1e-8 is how MinkowskiEngine's layer is recalled to behave (it adds
+    1e-8 to the variance); MinkowskiEngine is not installed where this package is developed (see the module docstring), so
+    this is this engine's definition, checked against torch.nn.functional.instance_norm in float64.
+
+    One HIP pass for the statistics (shifted sums per slice, merged by Chan's formula: csrc/inorm.hip), one for the rows; the
+    backward likewise.  Rows are grouped through CoordinateManager.batch_rows / batch_segments and read where they are held;
+    every sum runs in a fixed order: the same bytes on every run."""
+
+    def __init__(self, num_features, eps=1e-8):
+        super().__init__()
+        self.num_features = int(num_features)
+        self.eps = float(eps)
+        self.weight = nn.Parameter(torch.ones((1, self.num_features), dtype=torch.float32))
+        self.bias = nn.Parameter(torch.zeros((1, self.num_features), dtype=torch.float32))
+
+    def forward(self, x: SparseTensor):
+        c = x._F.size(1)
+        if c != self.num_features:
+            raise ValueError(f"{type(self).__name__}: the input has {c} channels, the layer num_features={self.num_features}")
+        cm, ts = x.coordinate_manager, x.tensor_stride
+        if not hasattr(get_backend(), "inorm_forward"):
+            raise NotImplementedError(f"{type(self).__name__} needs the HIP backend (ms3d_inorm_forward)")
+        order, _, offsets, _ = cm.batch_rows(ts)
+        y = Fn.instance_norm(x._raw(), self.weight, self.bias, (order, offsets, cm.batch_segments(ts)), self.eps)
+        return x._like(y)
+
+    def extra_repr(self):
+        return f"{self.num_features}, eps={self.eps}"
+
+
+class MinkowskiStableInstanceNorm(MinkowskiInstanceNorm):
+    """MinkowskiInstanceNorm with eps = 1e-6 by default: how MinkowskiEngine's second instance normalisation layer (built from
+    global pooling and broadcast layers there) is recalled to behave.  Here both classes run the same kernels -- the statistics
+    never form E[x^2] - E[x]^2 -- and differ in the default `eps` alone."""
+
+    def __init__(self, num_features, eps=1e-6):
+        super().__init__(num_features, eps)
+
+
 class MinkowskiUnion(nn.Module):
     """forward(*inputs): the sum of up to 16 tensors of one tensor stride and channel count on the UNION of their coordinate
     sets -- the first input's rows in their order, then the rows of the second that the first lacks, and so on; an input that

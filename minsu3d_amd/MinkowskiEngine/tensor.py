@@ -292,6 +292,22 @@ class CoordinateManager:
             br = self._batch_rows[ts] = (order, inv, offsets, counts.to(torch.float32).view(-1, 1))
         return br
 
+    def batch_segments(self, ts):
+        """int32 [V]: for every row of the coordinate set, as it is HELD, the index of its segment in batch_rows(ts) (the rank
+        of its batch index among the batch indices present) -- what a per-sample layer needs to find a row's statistics
+        without a permuted copy of the rows.  Derived from batch_rows, built once per tensor stride.  An engine extra."""
+        cache = self.__dict__.setdefault("_batch_segments", {})
+        seg = cache.get(ts)
+        if seg is None:
+            order, _, offsets, _ = self.batch_rows(ts)
+            lengths = (offsets[1:] - offsets[:-1]).long()
+            of_position = torch.repeat_interleave(torch.arange(lengths.numel(), dtype=torch.int32, device=order.device),
+                                                  lengths, output_size=order.numel())
+            seg = torch.empty(order.numel(), dtype=torch.int32, device=order.device)
+            seg[order] = of_position
+            cache[ts] = seg
+        return seg
+
     def k3(self, ts):
         if ts not in self._k3:
             self._k3[ts] = get_backend().kmap_k3(self.coords[ts], ts)

@@ -1088,6 +1088,63 @@ class _HipEngine:
                    "ms3d_chconv_backward_weight")
         return dW
 
+    # ---- instance normalisation over the batch grouping of a coordinate set (csrc/inorm.hip)
+    def _inorm_check(self, x, order, seg_start, seg_of_row):
+        assert x.dtype == torch.float32 and x.dim() == 2
+        assert order.dtype == torch.int64 and order.is_contiguous() and order.numel() == x.size(0)
+        assert seg_start.dtype == torch.int32 and seg_start.is_contiguous() and seg_start.numel() >= 1
+        assert seg_of_row.dtype == torch.int32 and seg_of_row.is_contiguous() and seg_of_row.numel() == x.size(0)
+        return x.size(0), x.size(1), seg_start.numel() - 1
+
+    def inorm_forward(self, x, order, seg_start, seg_of_row, eps, weight, bias):
+        """-> (y [V, C], mean float64 [B, C], invstd float64 [B, C]): x normalised per segment (order / seg_start: CoordinateManager.batch_rows;
+        seg_of_row: batch_segments) and channel with the biased variance, times weight plus bias ([C] / [1, C] or None: 1 / 0).
+        Rows are read where they lie."""
+        x = self._dev(x).contiguous()
+        v, c, B = self._inorm_check(x, order, seg_start, seg_of_row)
+        if weight is not None:
+            weight = self._dev(weight).contiguous()
+            assert weight.dtype == torch.float32 and weight.numel() == c
+        if bias is not None:
+            bias = self._dev(bias).contiguous()
+            assert bias.dtype == torch.float32 and bias.numel() == c
+        dev = x.device
+        y = torch.empty((v, c), dtype=torch.float32, device=dev)
+        mean = torch.empty((B, c), dtype=torch.float64, device=dev)
+        invstd = torch.empty((B, c), dtype=torch.float64, device=dev)
+        ws = self.ws.get("inorm", self.lib.ms3d_inorm_workspace_bytes(int(B), int(c)), dev)
+        _lib.check(self.lib.ms3d_inorm_forward(_lib.ptr(x), C.c_long(v), int(c), _lib.ptr(order), _lib.ptr(seg_start), int(B),
+                                               _lib.ptr(seg_of_row), C.c_float(eps), _lib.ptr(weight), _lib.ptr(bias),
+                                               _lib.ptr(mean), _lib.ptr(invstd), _lib.ptr(y), _lib.ptr(ws),
+                                               C.c_size_t(ws.numel()), _lib.stream_handle()), "ms3d_inorm_forward")
+        return y, mean, invstd
+
+    def inorm_backward(self, dy, x, order, seg_start, seg_of_row, mean, invstd, weight, want_dx=True, want_dweight=True,
+                       want_dbias=True):
+        """-> (dx [V, C], dweight [C], dbias [C]), each None when not wanted; the segment sums in a fixed order, dweight and
+        dbias over ascending segments"""
+        x = self._dev(x).contiguous()
+        dy = self._dev(dy).contiguous()
+        v, c, B = self._inorm_check(x, order, seg_start, seg_of_row)
+        assert dy.dtype == torch.float32 and tuple(dy.shape) == (v, c)
+        assert mean.dtype == torch.float64 and invstd.dtype == torch.float64 and mean.is_contiguous() and invstd.is_contiguous()
+        assert tuple(mean.shape) == (B, c) and tuple(invstd.shape) == (B, c)
+        if weight is not None:
+            weight = self._dev(weight).contiguous()
+            assert weight.dtype == torch.float32 and weight.numel() == c
+        dev = x.device
+        empty = v <= 0 or B <= 0                # (the entry point launches nothing: an empty sum is zero)
+        dx = torch.empty((v, c), dtype=torch.float32, device=dev) if want_dx else None
+        dweight = (torch.zeros if empty else torch.empty)(c, dtype=torch.float32, device=dev) if want_dweight else None
+        dbias = (torch.zeros if empty else torch.empty)(c, dtype=torch.float32, device=dev) if want_dbias else None
+        ws = self.ws.get("inorm", self.lib.ms3d_inorm_workspace_bytes(int(B), int(c)), dev)
+        _lib.check(self.lib.ms3d_inorm_backward(_lib.ptr(dy), _lib.ptr(x), C.c_long(v), int(c), _lib.ptr(order),
+                                                _lib.ptr(seg_start), int(B), _lib.ptr(seg_of_row), _lib.ptr(mean),
+                                                _lib.ptr(invstd), _lib.ptr(weight), _lib.ptr(dx), _lib.ptr(dweight),
+                                                _lib.ptr(dbias), _lib.ptr(ws), C.c_size_t(ws.numel()), _lib.stream_handle()),
+                   "ms3d_inorm_backward")
+        return dx, dweight, dbias
+
     # ---- points <-> voxels (csrc/field.hip; the interpolation map: csrc/coords.hip)
     def interp_map(self, coords, points, tensor_stride):
         """the eight corners of every point in the coordinate set `coords` (int32 [V, 4], tensor stride `tensor_stride`) ->
