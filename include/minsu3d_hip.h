@@ -678,6 +678,43 @@ int ms3d_bn_bwd_partial(const float *dy, const float *x, long V, int C, const fl
                         int partial_rows, int *nparts_out /*[host]*/, ms3d_stream_t stream);
 
 /* ======================================================================================
+ * Dense tensors in and out (csrc/dense.hip): sparse rows F [V, C] <-> a dense grid float [B, C, X, Y, Z].  A CELL is one
+ * (b, x', y', z') of the grid, numbered ((b * X + x') * Y + y') * Z + z'; element (b, c, cell) of the grid lies at
+ * (b * C + c) * X * Y * Z + (cell - b * X * Y * Z).  Every entry point returns MS3D_E_UNSUPPORTED WITHOUT touching a pointer
+ * or launching when a size is negative, the grid has more than 2^31 - 1 cells or B * C * X * Y * Z >= 2^63.  Nothing adds
+ * floats; every result is the same bytes on every run.
+ * ====================================================================================== */
+/* the tile of the two feature kernels: cells (list entries) and channels per workgroup */
+int ms3d_dense_tile_cells(void);
+int ms3d_dense_tile_channels(void);
+/* Cell map of a coordinate set: coords int32 [V, 4] (b, x, y, z); origin [host, 3]; the cell index of a row per axis is
+ * (x - origin_x) / divisor (divisor >= 1: the tensor stride when strides are contracted, else 1).  cell_row [B*X*Y*Z]: the row
+ * at each cell, -1 where none -- where several rows name one cell, the LOWEST row; row_cell [V]: the cell of each row, -1 for a
+ * row outside the grid or with a difference the divisor does not divide.  counts [host, 3] = (rows outside the grid, rows not
+ * divisible by the divisor, rows that lost their cell to another row); counts_dev: 4 ints of device scratch.  V == 0 fills
+ * the table with -1.  One host sync (none for V == 0). */
+int ms3d_dense_cell_map(const int *coords, int V, const int *origin /*[host,3]*/, int divisor, int B, int X, int Y, int Z,
+                        int *cell_row, int *row_cell, int *counts_dev, int *counts /*[host,3]*/, ms3d_stream_t stream);
+/* Rows -> grid: out[b, c, cell] = F[row * ld + c] with row = cell_row[cell] (through row_index[row] when row_index is not
+ * NULL: the table names rows of one order, the features are held in another), 0 where the cell has no row (or the row is
+ * >= n_rows).  Every element of out is written exactly once; no memset is needed in front.  ld >= C: floats between rows. */
+int ms3d_dense_scatter(const float *F, long n_rows, long ld, const int *cell_row, const int *row_index, int B, int C, int X,
+                       int Y, int Z, float *out /*[B,C,X,Y,Z]*/, ms3d_stream_t stream);
+/* Grid -> rows: out[i, c] = grid[b, c, cells[i]] for i < n (out [n, C], contiguous); a cell outside [0, B*X*Y*Z) gives a zero
+ * row; a cell listed twice is read twice. */
+int ms3d_dense_gather(const float *grid, int B, int C, int X, int Y, int Z, const int *cells, long n, float *out,
+                      ms3d_stream_t stream);
+/* Occupancy: keep [B*X*Y*Z] = 1 where any channel of the cell is != 0 (NaN counts, -0.0 does not), every cell when grid is
+ * NULL; rank [B*X*Y*Z] = the exclusive scan of keep; *n_kept [host] = the number kept (one host sync).
+ * ms3d_dense_cells_emit then writes the kept cells in ascending cell order: out_coords int32 [n_kept, 4] (b, x, y, z) and
+ * out_cells int32 [n_kept]. */
+size_t ms3d_dense_occupancy_workspace_bytes(void);
+int ms3d_dense_occupancy(const float *grid, int B, int C, int X, int Y, int Z, unsigned char *keep, int *rank,
+                         int *n_kept /*[host]*/, void *workspace, size_t workspace_bytes, ms3d_stream_t stream);
+int ms3d_dense_cells_emit(const unsigned char *keep, const int *rank, int B, int X, int Y, int Z, int *out_coords,
+                          int *out_cells, ms3d_stream_t stream);
+
+/* ======================================================================================
  * Instance post-processing (validation / test time): replaces the dense [P, N] mask algebra of
  * model/pointgroup.py:197-265 (cross IoU by mask matrix product on the host + numpy greedy NMS).
  * ====================================================================================== */

@@ -45,7 +45,23 @@ Normalisation per sample and the activations of the decoders, generators and reg
     MinkowskiTanh, MinkowskiSoftplus, MinkowskiHardswish, MinkowskiHardtanh, MinkowskiReLU6, MinkowskiSoftmax,
     MinkowskiLogSoftmax: the torch operator as `self.module`, applied to the rows
 
-Not supported (each raises NotImplementedError naming it): strides other than 1 and 2, a generative layer at stride 2 on an odd
+Dense tensors in and out, and the per-sample views of a batch:
+
+    SparseTensor.dense(shape=None, min_coordinate=None, contract_stride=True) -> (dense [B, C, X, Y, Z], min_coordinate
+    int32 [1, 3], tensor_stride int32 [3]); to_sparse(x, format=None, coordinates=None, device=None), to_sparse_all(x);
+    MinkowskiToSparseTensor, MinkowskiToDenseTensor, MinkowskiToFeature; SparseTensor.decomposition_permutations,
+    .decomposed_coordinates, .decomposed_features, .decomposed_coordinates_and_features, .coordinates_at(b), .features_at(b)
+    (+ CoordinateManager.dense_map / extent / decomposition: engine extras)
+
+    A transposing HIP kernel pair over a cached cell map (csrc/dense.hip): rows -> grid writes every element once (no fill in
+    front), grid -> rows is its backward and the feature read of to_sparse; bit-exact copies, the same bytes on every run.
+    Chosen here without a copy of MinkowskiEngine to compare against: min_coordinate=None takes the per-axis minimum of the
+    coordinates as the origin (and returns it), an int means that value on every axis; to_sparse keeps a cell when ANY
+    channel is != 0 (NaN counts, -0.0 does not) and orders the rows like torch.nonzero; a row outside the grid, a coordinate
+    off the stride lattice and a repeated coordinate raise ValueError (nothing is clipped or summed silently).  "BXXXC" input is permuted and copied contiguous once.
+
+Not supported (each raises NotImplementedError naming it): a dense grid of more than 2^31 - 1 cells, to_sparse of a tensor
+that is not 5-D ([B, C, X, Y, Z]: dimension 3) or in a format other than "BCXXX" / "BXXXC", dense() on a per-axis tensor stride, strides other than 1 and 2, a generative layer at stride 2 on an odd
 tensor stride, MinkowskiConvolutionTranspose onto a coordinate set that is not cached, convolutions (expand_coordinates) or
 pooling that create coordinates, `+=` and ME.cat across different coordinate sets, a union of more than 16 tensors,
 the `quantization_mode` argument of SparseTensor itself (quantise with a field), interpolation gradients with respect to the
@@ -57,6 +73,7 @@ Module/parameter names match ME so reference state_dicts keep their keys (`kerne
 from . import utils  # noqa: F401
 from .tensor import SparseTensor, CoordinateManager, cat, prefetch_coordinates  # noqa: F401
 from .tensor import TensorField, SparseTensorQuantizationMode  # noqa: F401
+from .tensor import to_sparse, to_sparse_all  # noqa: F401
 from .modules import (MinkowskiConvolution, MinkowskiConvolutionTranspose, MinkowskiBatchNorm,  # noqa: F401
                       MinkowskiReLU, prepare_conv_weights, release_conv_weights,
                       MinkowskiMaxPooling, MinkowskiAvgPooling, MinkowskiSumPooling, MinkowskiGlobalMaxPooling,
@@ -66,6 +83,7 @@ from .modules import (MinkowskiConvolution, MinkowskiConvolutionTranspose, Minko
                       MinkowskiBroadcastConcatenation, MinkowskiBroadcast, MinkowskiSigmoid,
                       MinkowskiPoolingTranspose, MinkowskiInterpolation, MinkowskiChannelwiseConvolution,
                       MinkowskiInstanceNorm, MinkowskiStableInstanceNorm,
+                      MinkowskiToSparseTensor, MinkowskiToDenseTensor, MinkowskiToFeature,
                       MinkowskiELU, MinkowskiLeakyReLU, MinkowskiPReLU, MinkowskiSELU, MinkowskiCELU, MinkowskiGELU,
                       MinkowskiSiLU, MinkowskiTanh, MinkowskiSoftplus, MinkowskiHardswish, MinkowskiHardtanh,
                       MinkowskiReLU6, MinkowskiSoftmax, MinkowskiLogSoftmax)

@@ -778,3 +778,54 @@ class InterpolateFn(torch.autograd.Function):
 
 def interpolate(x, rows, weights, group):
     return InterpolateFn.apply(x, rows, weights, group)
+
+
+class DenseScatterFn(torch.autograd.Function):
+    """rows -> grid (SparseTensor.dense): out [B, C, X, Y, Z] with out[b, :, cell] = x[cell_row[cell]], zeros where the cell has
+    no row (csrc/dense.hip).  cell_row / row_cell: the two directions of one cell map over the rows as the engine HOLDS them.
+    The backward is the other kernel over the same map: dx[r] = dout[b, :, row_cell[r]].  No float is added in either
+    direction: the same bytes on every run."""
+
+    @staticmethod
+    def forward(ctx, x, cell_row, row_cell, shape):
+        be = _field_backend("SparseTensor.dense", "dense_scatter", "dense_gather")
+        ctx.row_cell = row_cell
+        return be.dense_scatter(x, cell_row, shape)
+
+    @staticmethod
+    def backward(ctx, dout):
+        return get_backend().dense_gather(dout.contiguous(), ctx.row_cell), None, None, None
+
+
+def dense_scatter(x, cell_row, row_cell, shape):
+    return DenseScatterFn.apply(x, cell_row, row_cell, shape)
+
+
+class DenseGatherFn(torch.autograd.Function):
+    """grid -> rows (to_sparse): out [n, C] with out[i] = x[b, :, cells[i]] for x [B, C, X, Y, Z].  coords: the coordinates
+    int32 [n, 4] of the cells (b, x, y, z with origin 0), in the order of `cells` -- the backward builds the cell map from them
+    once and scatters: dx[b, :, cell] = dout[row of the cell], zeros at the cells not listed.  Where the list names a cell
+    twice (only to_sparse(coordinates=...) can), the rows of one cell are first summed in ascending row order onto its lowest
+    row (scatter_add_rows: a fixed order, no float atomics)."""
+
+    @staticmethod
+    def forward(ctx, x, cells, coords):
+        be = _field_backend("to_sparse", "dense_gather", "dense_scatter", "dense_cell_map")
+        ctx.geom = (cells, coords, tuple(x.shape))
+        return be.dense_gather(x, cells)
+
+    @staticmethod
+    def backward(ctx, dout):
+        cells, coords, shape = ctx.geom
+        be = get_backend()
+        B, _, X, Y, Z = shape
+        cell_row, _, (_, _, lost) = be.dense_cell_map(coords, (0, 0, 0), 1, (B, X, Y, Z))
+        dout = dout.contiguous()
+        if lost:
+            winner = cell_row[cells.long()].long()
+            dout = be.scatter_add_rows(dout, winner, dout.size(0))
+        return be.dense_scatter(dout, cell_row, shape), None, None
+
+
+def dense_gather(x, cells, coords):
+    return DenseGatherFn.apply(x, cells, coords)

@@ -16,7 +16,7 @@ import torch.nn as nn
 
 from ..backend import get_backend
 from . import functional as Fn
-from .tensor import SparseTensor, check_geometry, union_op
+from .tensor import SparseTensor, check_geometry, union_op, to_sparse, to_sparse_all
 
 
 class _ConvBase(nn.Module):
@@ -290,6 +290,47 @@ class MinkowskiPruning(nn.Module):
             idx = cm.inv[idx]
         y = Fn.select_rows(x._raw(), idx)
         return SparseTensor(y, coordinate_manager=type(cm).rooted(out_coords, ts), tensor_stride=ts)
+
+
+class MinkowskiToSparseTensor(nn.Module):
+    """forward(x): dense [B, C, X, Y, Z] -> SparseTensor at tensor stride 1 on a new manager: the cells with a non-zero channel
+    (remove_zeros=True: to_sparse) or every cell (remove_zeros=False: to_sparse_all); coordinates (int [n, 4]): exactly those
+    cells, in that order.  Gradients flow to x."""
+
+    def __init__(self, remove_zeros=True, coordinates=None):
+        super().__init__()
+        self.remove_zeros = remove_zeros
+        self.coordinates = coordinates
+
+    def forward(self, x):
+        if self.coordinates is not None:
+            return to_sparse(x, coordinates=self.coordinates)
+        return to_sparse(x) if self.remove_zeros else to_sparse_all(x)
+
+    def extra_repr(self):
+        return f"remove_zeros={self.remove_zeros}"
+
+
+class MinkowskiToDenseTensor(nn.Module):
+    """forward(x): SparseTensor -> its dense tensor [B, C, X, Y, Z] alone: x.dense(shape=shape)[0], so the origin is the
+    per-axis minimum of x's coordinates (SparseTensor.dense); shape: torch.Size / tuple (B, C, X, Y, Z) or None."""
+
+    def __init__(self, shape=None):
+        super().__init__()
+        self.shape = None if shape is None else tuple(int(v) for v in shape)
+
+    def forward(self, x: SparseTensor):
+        return x.dense(shape=self.shape)[0]
+
+    def extra_repr(self):
+        return f"shape={self.shape}"
+
+
+class MinkowskiToFeature(nn.Module):
+    """forward(x): x.F -- the feature rows in the caller's order, for the torch layers behind a sparse network"""
+
+    def forward(self, x: SparseTensor):
+        return x.F
 
 
 class MinkowskiBatchNorm(nn.Module):

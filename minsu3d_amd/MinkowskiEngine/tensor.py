@@ -308,6 +308,61 @@ class CoordinateManager:
             cache[ts] = seg
         return seg
 
+    def extent(self, ts):
+        """(per-axis minimum [3], per-axis maximum [3], largest batch index) of the coordinate set as Python ints, None for an
+        empty set; one small host read, once per tensor stride.  An engine extra."""
+        cache = self.__dict__.setdefault("_extent", {})
+        if ts not in cache:
+            c = self.coords[ts]
+            if c.size(0) == 0:
+                cache[ts] = None
+            else:
+                lo, hi = c.amin(0), c.amax(0)
+                v = torch.cat([lo[1:], hi[1:], hi[:1]]).tolist()
+                cache[ts] = (tuple(v[0:3]), tuple(v[3:6]), v[6])
+        return cache[ts]
+
+    def dense_map(self, ts, origin, divisor, grid):
+        """the map between the rows of the coordinate set of tensor stride ts, as they are HELD, and the cells of a dense grid
+        (B, X, Y, Z): a row's cell index per axis is (x - origin) / divisor, its cell ((b * X + x') * Y + y') * Z + z' -> (cell_row
+        int32 [B*X*Y*Z]: the row at each cell or -1; row_cell int32 [V]: the cell of each row or -1; (rows outside the grid, rows
+        the divisor does not divide, rows that lost their cell to another row)) -- backend.dense_cell_map.  Built once per (ts,
+        origin, divisor, grid), as kernel maps are (one host sync); the table is as large as the grid, so only the four newest
+        maps are kept.  An engine extra."""
+        cache = self.__dict__.setdefault("_dense_maps", {})
+        key = (ts, tuple(int(v) for v in origin), int(divisor), tuple(int(v) for v in grid))
+        hit = cache.get(key)
+        if hit is None:
+            be = get_backend()
+            if not hasattr(be, "dense_cell_map"):
+                raise NotImplementedError("SparseTensor.dense needs the HIP backend (ms3d_dense_cell_map)")
+            hit = cache[key] = be.dense_cell_map(self.coords[ts], key[1], key[2], key[3])
+            while len(cache) > 4:
+                cache.pop(next(iter(cache)))
+        return hit
+
+    def decomposition(self, ts):
+        """list of int64 row lists, one per batch index 0 .. B - 1 (B = largest batch index + 1; an index without rows gets an
+        empty list): the rows of .coordinates / .features -- the order the CALLER sees -- of every sample, each in ascending
+        row order.  From batch_rows where the rows are held in the caller's order, from one stable sort of the caller's batch
+        column on a Morton-sorted manager; one host read, once per tensor stride.  An engine extra."""
+        cache = self.__dict__.setdefault("_decomposition", {})
+        perms = cache.get(ts)
+        if perms is None:
+            b = self.visible_coords(ts)[:, 0].long()
+            if ts == 1 and self.perm is not None:
+                sb, order = torch.sort(b, stable=True)
+                present, counts = torch.unique_consecutive(sb, return_counts=True)
+                present, counts = present.tolist(), counts.tolist()
+            else:
+                order, _, offsets, _ = self.batch_rows(ts)
+                off = offsets.tolist()
+                counts = [off[i + 1] - off[i] for i in range(len(off) - 1)]
+                present = b[order[offsets[:-1].long()]].tolist() if counts else []
+            parts = dict(zip(present, torch.split(order, counts))) if counts else {}
+            perms = cache[ts] = [parts.get(i, order[:0]) for i in range((present[-1] + 1) if present else 0)]
+        return perms
+
     def k3(self, ts):
         if ts not in self._k3:
             self._k3[ts] = get_backend().kmap_k3(self.coords[ts], ts)
@@ -544,6 +599,105 @@ class SparseTensor:
         padded = torch.cat([feats, feats.new_zeros((1, feats.size(1)))])      # absent -> the zero row behind the last one
         return Fn.gather_rows(padded, torch.where(rows < 0, torch.full_like(rows, feats.size(0)), rows))
 
+    # ---- dense tensors
+    def dense(self, shape=None, min_coordinate=None, contract_stride=True):
+        """-> (dense float32 [B, C, X, Y, Z], min_coordinate int32 [1, 3], tensor_stride int32 [3]; the last two on the CPU).
+        dense[b, :, x', y', z'] is the feature row at the cell, exactly 0 where the tensor has no voxel.  MinkowskiEngine is
+        not installed where this engine is developed; this is the specification:
+
+        Origin.  min_coordinate=None: the per-axis minimum of the tensor's coordinates (zeros for an empty tensor); it is
+        returned.  min_coordinate=0 (any int): that value on every axis.  Otherwise 3 ints: a list, or a tensor [3] / [1, 3].
+        Cell index.  contract_stride=True: (c - origin) / tensor_stride per axis; an origin or a coordinate difference that is
+        not a multiple of the tensor stride raises ValueError.  contract_stride=False: c - origin.
+        Shape.  shape=None: B = largest batch index + 1, spatial sizes = largest cell index + 1 per axis.  Given: torch.Size or
+        tuple (B, C, X, Y, Z), C checked against the features (ValueError).
+        Errors.  ValueError naming how many rows lie outside the grid (a negative cell index, one >= the size, or a batch index
+        >= B), and ValueError for a set that holds a coordinate twice.  More than 2^31 - 1 cells: NotImplementedError.
+
+        The rows are read where the manager holds them (a Morton-sorted set is not un-permuted, a pending BatchNorm / ReLU is
+        materialised first); the cell map is cached on the manager (CoordinateManager.dense_map).  Gradients flow to the
+        features; the coordinates get none.  Every element of the result is written once by one kernel (csrc/dense.hip)."""
+        cm, ts = self.coordinate_manager, self.tensor_stride
+        c = self._F.size(1)
+        if not isinstance(ts, int):
+            raise NotImplementedError(f"dense() on tensor_stride={ts!r}: one integer tensor stride (no per-axis tuples)")
+        divisor = ts if contract_stride else 1
+        ext = cm.extent(ts)
+        if min_coordinate is None:
+            origin = ext[0] if ext is not None else (0, 0, 0)
+        elif isinstance(min_coordinate, int):
+            origin = (min_coordinate,) * 3
+        else:
+            origin = tuple(int(v) for v in torch.as_tensor(min_coordinate).reshape(-1).tolist())
+            if len(origin) != 3:
+                raise ValueError(f"dense(): min_coordinate must hold 3 integers, got {len(origin)}")
+        if any(o % divisor for o in origin):
+            raise ValueError(f"dense(): min_coordinate {list(origin)} is not a multiple of the tensor stride {ts} "
+                             "(pass contract_stride=False to keep the coordinates as they are)")
+        if shape is None:
+            if ext is None:
+                grid = (0, 0, 0, 0)
+            else:
+                grid = (ext[2] + 1,) + tuple(max((hi - o) // divisor + 1, 0) for hi, o in zip(ext[1], origin))
+        else:
+            shape = tuple(int(v) for v in shape)
+            if len(shape) != 5:
+                raise ValueError(f"dense(): shape must be (B, C, X, Y, Z), got {list(shape)}")
+            if shape[1] != c:
+                raise ValueError(f"dense(): shape {list(shape)} asks for {shape[1]} channels, the features have {c}")
+            if min(shape) < 0:
+                raise ValueError(f"dense(): negative size in shape {list(shape)}")
+            grid = (shape[0],) + shape[2:]
+        if grid[0] * grid[1] * grid[2] * grid[3] > 2 ** 31 - 1:
+            raise NotImplementedError(f"dense(): a grid of {list(grid)} (B, X, Y, Z) has more than 2^31 - 1 cells")
+        cell_row, row_cell, (outside, offgrid, lost) = cm.dense_map(ts, origin, divisor, grid)
+        if offgrid:
+            raise ValueError(f"dense(): {offgrid} rows have a coordinate whose difference to min_coordinate {list(origin)} is "
+                             f"not a multiple of the tensor stride {ts}")
+        if outside:
+            raise ValueError(f"dense(): {outside} rows lie outside the grid {list(grid)} (B, X, Y, Z) from min_coordinate "
+                             f"{list(origin)} (a negative cell index, one past the size, or a batch index >= B)")
+        if lost:
+            raise ValueError(f"dense(): the coordinate set holds a coordinate more than once ({lost} rows repeat another row's)")
+        out = Fn.dense_scatter(self._raw(), cell_row, row_cell, (grid[0], c) + grid[1:])
+        return out, torch.tensor([origin], dtype=torch.int32), torch.tensor([ts] * 3, dtype=torch.int32)
+
+    # ---- per-sample views (plain torch over the rows the caller sees; rows of a sample keep their order)
+    @property
+    def decomposition_permutations(self):
+        """list of int64 row lists into .features / .coordinates, one per batch index 0 .. B - 1, empty lists included"""
+        return list(self.coordinate_manager.decomposition(self.tensor_stride))
+
+    @property
+    def decomposed_coordinates(self):
+        """list of int32 [n_b, 3]: the coordinates of every sample without the batch column"""
+        coords = self.coordinates
+        return [coords[p, 1:] for p in self.decomposition_permutations]
+
+    @property
+    def decomposed_features(self):
+        """list of float [n_b, C]: the feature rows of every sample (differentiable)"""
+        feats = self.features
+        return [feats[p] for p in self.decomposition_permutations]
+
+    @property
+    def decomposed_coordinates_and_features(self):
+        return self.decomposed_coordinates, self.decomposed_features
+
+    def _sample_rows(self, batch_index):
+        perms = self.coordinate_manager.decomposition(self.tensor_stride)
+        if not isinstance(batch_index, int) or not 0 <= batch_index < len(perms):
+            raise ValueError(f"batch index {batch_index!r}: the tensor holds the batch indices 0 .. {len(perms) - 1}")
+        return perms[batch_index]
+
+    def coordinates_at(self, batch_index):
+        """int32 [n_b, 3]: the coordinates of one sample without the batch column"""
+        return self.coordinates[self._sample_rows(batch_index), 1:]
+
+    def features_at(self, batch_index):
+        """float [n_b, C]: the feature rows of one sample (differentiable)"""
+        return self.features[self._sample_rows(batch_index)]
+
     # ---- points in, points out (TensorField)
     def slice(self, field):
         """TensorField on `field`'s points: every point gets the row of its voxel (TensorField.slice)"""
@@ -766,6 +920,64 @@ class TensorField:
     def cat_slice(self, x):
         """.slice(x) with the field's own features concatenated in front"""
         return self._like(torch.cat([self._F, self.slice(x)._F], 1))
+
+
+def _dense_input(x, format, device):
+    if not torch.is_tensor(x) or x.dim() != 5:
+        nd = x.dim() if torch.is_tensor(x) else None
+        raise NotImplementedError(f"to_sparse of a {nd}-D tensor (dimension={None if nd is None else nd - 2}): only 3-D sparse "
+                                  "tensors are supported, the input is [B, C, X, Y, Z]")
+    if format is None:
+        format = "BCXXX"
+    if format not in ("BCXXX", "BXXXC"):
+        raise NotImplementedError(f"format={format!r}: 'BCXXX' (the default) or 'BXXXC'")
+    if device is not None:
+        x = x.to(device)
+    if x.dtype != torch.float32:
+        x = x.float()
+    if format == "BXXXC":
+        x = x.permute(0, 4, 1, 2, 3)      # channels-last: one contiguous copy below, then the same kernels
+    return x.contiguous()
+
+
+def _to_sparse(x, format, coordinates, device, keep_all):
+    x = _dense_input(x, format, device)
+    be = get_backend()
+    if not (hasattr(be, "dense_occupancy") and hasattr(be, "dense_cell_map")):
+        raise NotImplementedError("to_sparse needs the HIP backend (ms3d_dense_occupancy)")
+    B, _, X, Y, Z = x.shape
+    if B * X * Y * Z > 2 ** 31 - 1:
+        raise NotImplementedError(f"to_sparse: a grid of {[B, X, Y, Z]} (B, X, Y, Z) has more than 2^31 - 1 cells")
+    if coordinates is None:
+        _, coords, cells = be.dense_occupancy(x.detach(), keep_all)
+    else:
+        if coordinates.dim() != 2 or coordinates.size(1) != 4 or coordinates.is_floating_point():
+            raise ValueError(f"to_sparse: coordinates must be int [n, 4] (b, x, y, z), got {list(coordinates.shape)} "
+                             f"{coordinates.dtype}")
+        coords = coordinates.to(device=x.device, dtype=torch.int32).contiguous()
+        _, cells, (outside, _, _) = be.dense_cell_map(coords, (0, 0, 0), 1, (B, X, Y, Z))
+        if outside:
+            raise ValueError(f"to_sparse: {outside} coordinates lie outside the dense tensor {[B, X, Y, Z]} (B, X, Y, Z)")
+    cm = CoordinateManager(coords, spatial_sort=coords.size(0) >= _SORT_MIN_ROWS)
+    if cm.perm is not None:                # read the rows straight into the order the manager holds them in
+        cells = cells[cm.perm].contiguous()
+    return SparseTensor(Fn.dense_gather(x, cells, cm.coords[1]), coordinate_manager=cm)
+
+
+def to_sparse(x, format=None, coordinates=None, device=None):
+    """SparseTensor (tensor stride 1, a new manager) of a dense x [B, C, X, Y, Z] (format "BCXXX", the default) or
+    [B, X, Y, Z, C] ("BXXXC": permuted and copied contiguous once, then the same kernels): the cells where ANY channel is
+    non-zero (NaN counts as non-zero, -0.0 does not), coordinates (b, x, y, z) with origin 0, rows in ascending (b, x, y, z)
+    order -- the order of torch.nonzero on the mask, and the order the caller sees; a set of at least _SORT_MIN_ROWS rows is
+    Morton-sorted internally like any SparseTensor.  coordinates (int [n, 4]): exactly those cells, in the caller's order (one
+    named twice gives two equal rows); coordinates outside x raise ValueError.  Gradients flow to x (zeros at the cells not
+    kept).  An input that is not 5-D raises NotImplementedError."""
+    return _to_sparse(x, format, coordinates, device, False)
+
+
+def to_sparse_all(x, format=None):
+    """to_sparse that keeps EVERY cell of x: B * X * Y * Z rows in ascending (b, x, y, z) order"""
+    return _to_sparse(x, format, None, None, True)
 
 
 def union_op(op, *tensors):

@@ -1145,6 +1145,95 @@ class _HipEngine:
                    "ms3d_inorm_backward")
         return dx, dweight, dbias
 
+    # ---- dense tensors in and out (csrc/dense.hip)
+    DENSE_MAX_CELLS = 2 ** 31 - 1
+
+    @staticmethod
+    def _dense_grid(grid):
+        grid = tuple(int(v) for v in grid)
+        assert len(grid) == 4 and min(grid) >= 0, grid
+        n = grid[0] * grid[1] * grid[2] * grid[3]
+        if n > _HipEngine.DENSE_MAX_CELLS:
+            # (refused here as every entry point refuses it, before anything of that size is allocated)
+            _lib.check(_lib.E_UNSUPPORTED, f"a dense grid of {grid}: more than 2^31 - 1 cells")
+        return grid, n
+
+    def dense_cell_map(self, coords, origin, divisor, grid):
+        """the map between the rows of coords int32 [V, 4] and the cells of grid = (B, X, Y, Z): cell index per axis
+        (x - origin) / divisor -> (cell_row int32 [B*X*Y*Z]: row at each cell or -1, the lowest row where several name one cell;
+        row_cell int32 [V]: cell of each row or -1; (rows outside the grid, rows the divisor does not divide, rows that lost
+        their cell to another row)).  One host sync."""
+        coords = self._dev(coords)
+        assert coords.dtype == torch.int32 and coords.dim() == 2 and coords.size(1) == 4
+        (B, X, Y, Z), ncells = self._dense_grid(grid)
+        origin = [int(v) for v in origin]
+        assert len(origin) == 3 and int(divisor) >= 1
+        V, dev = coords.size(0), coords.device
+        cell_row = torch.empty(ncells, dtype=torch.int32, device=dev)
+        row_cell = torch.empty(V, dtype=torch.int32, device=dev)
+        scratch = torch.empty(4, dtype=torch.int32, device=dev)
+        counts = (C.c_int * 3)(0, 0, 0)
+        _lib.check(self.lib.ms3d_dense_cell_map(_lib.ptr(coords), V, (C.c_int * 3)(*origin), int(divisor), B, X, Y, Z,
+                                                _lib.ptr(cell_row), _lib.ptr(row_cell), _lib.ptr(scratch), counts,
+                                                _lib.stream_handle()), "ms3d_dense_cell_map")
+        return cell_row, row_cell, (counts[0], counts[1], counts[2])
+
+    def dense_scatter(self, feats, cell_row, shape, row_index=None):
+        """rows -> grid: out float32 [B, C, X, Y, Z] with out[b, :, cell] = feats[cell_row[cell]] (through row_index when given:
+        int32, table row -> row of feats) and zeros where cell_row is -1; every element written once, no fill in front.  feats
+        may be a row-strided view (stride(1) == 1)."""
+        B, c, X, Y, Z = (int(v) for v in shape)
+        _, ncells = self._dense_grid((B, X, Y, Z))
+        if not feats.is_cuda or feats.dim() != 2 or feats.stride(1) != 1 or feats.stride(0) < feats.size(1):
+            feats = self._dev(feats)
+        assert feats.dtype == torch.float32 and feats.dim() == 2 and feats.size(1) == c
+        cell_row = self._dev(cell_row)
+        assert cell_row.dtype == torch.int32 and cell_row.numel() == ncells
+        if row_index is not None:
+            row_index = self._dev(row_index)
+            assert row_index.dtype == torch.int32 and row_index.dim() == 1
+        ld = feats.stride(0) if feats.size(0) > 1 else max(c, 1)
+        out = torch.empty((B, c, X, Y, Z), dtype=torch.float32, device=feats.device)
+        _lib.check(self.lib.ms3d_dense_scatter(C.c_void_p(feats.data_ptr()), C.c_long(feats.size(0)), C.c_long(ld),
+                                               _lib.ptr(cell_row), _lib.ptr(row_index), B, c, X, Y, Z, _lib.ptr(out),
+                                               _lib.stream_handle()), "ms3d_dense_scatter")
+        return out
+
+    def dense_gather(self, grid, cells):
+        """grid -> rows: out float32 [n, C] with out[i] = grid[b, :, cells[i]] for grid [B, C, X, Y, Z] and cells int32 [n]
+        (a cell outside the grid gives a zero row; a cell listed twice is read twice)"""
+        grid, cells = self._dev(grid), self._dev(cells)
+        assert grid.dtype == torch.float32 and grid.dim() == 5
+        assert cells.dtype == torch.int32 and cells.dim() == 1
+        B, c, X, Y, Z = grid.shape
+        self._dense_grid((B, X, Y, Z))
+        out = torch.empty((cells.numel(), c), dtype=torch.float32, device=grid.device)
+        _lib.check(self.lib.ms3d_dense_gather(_lib.ptr(grid), B, c, X, Y, Z, _lib.ptr(cells), C.c_long(cells.numel()),
+                                              _lib.ptr(out), _lib.stream_handle()), "ms3d_dense_gather")
+        return out
+
+    def dense_occupancy(self, grid, keep_all=False):
+        """grid float32 [B, C, X, Y, Z] -> (keep uint8 [B*X*Y*Z]: any channel != 0 (NaN counts, -0.0 does not), or every cell
+        with keep_all; coords int32 [n, 4]: the kept cells as (b, x, y, z) in ascending cell order -- the order of
+        torch.nonzero on the mask; cells int32 [n]).  One host sync."""
+        grid = self._dev(grid)
+        assert grid.dtype == torch.float32 and grid.dim() == 5
+        B, c, X, Y, Z = grid.shape
+        _, ncells = self._dense_grid((B, X, Y, Z))
+        dev = grid.device
+        keep = torch.empty(ncells, dtype=torch.uint8, device=dev)
+        rank = torch.empty(ncells, dtype=torch.int32, device=dev)
+        ws = self.ws.get("dense_occ", self.lib.ms3d_dense_occupancy_workspace_bytes(), dev)
+        n = C.c_int(0)
+        _lib.check(self.lib.ms3d_dense_occupancy(None if keep_all else _lib.ptr(grid), B, c, X, Y, Z, _lib.ptr(keep),
+                                                 _lib.ptr(rank), C.byref(n), _lib.ptr(ws), C.c_size_t(ws.numel()),
+                                                 _lib.stream_handle()), "ms3d_dense_occupancy")
+        coords = torch.empty((n.value, 4), dtype=torch.int32, device=dev)
+        cells = torch.empty(n.value, dtype=torch.int32, device=dev)
+        _lib.check(self.lib.ms3d_dense_cells_emit(_lib.ptr(keep), _lib.ptr(rank), B, X, Y, Z, _lib.ptr(coords), _lib.ptr(cells),
+                                                  _lib.stream_handle()), "ms3d_dense_cells_emit")
+        return keep, coords, cells
+
     # ---- points <-> voxels (csrc/field.hip; the interpolation map: csrc/coords.hip)
     def interp_map(self, coords, points, tensor_stride):
         """the eight corners of every point in the coordinate set `coords` (int32 [V, 4], tensor stride `tensor_stride`) ->
