@@ -227,6 +227,23 @@ int ms3d_coords_expand(const int *in_coords, int Vin, const int *offsets, int K,
 int ms3d_coords_prune(const int *coords, int V, const unsigned char *keep, int *out_coords, int *src_row, int *dst_row,
                       int *n_kept /*[host]*/, void *workspace, size_t workspace_bytes, ms3d_stream_t stream);
 
+/* ms3d_coords_check: is a coordinate set that a CALLER supplied (the target of a layer's `coordinates=`) usable as an output
+ * set, and if not, why.  *flags -> [host] (one sync), the OR of
+ *   MS3D_COORDS_OUT_OF_RANGE  a row lies outside the packable range [-16384, 16384) or its batch index outside [0, 524288)
+ *   MS3D_COORDS_OFF_LATTICE   a coordinate (x, y or z) is not a multiple of `lattice` (the tensor stride of the set; >= 1)
+ *   MS3D_COORDS_REPEATED      a coordinate occurs twice (ms3d_kmap_invert needs distinct output rows); a row that does not fit
+ *                             the key aliases another coordinate and is not asked, so read this bit with the first one down
+ * The table of ms3d_sparse_quantize is built (clear, insert: 64-bit CAS on the key, atomicMin of the row) and one kernel, one
+ * thread per row, tests floor(v / lattice) * lattice == v and "this row is the first of its slot"; the bits are ORed into one
+ * device int, by the threads that do not see their bit up yet.  Returns 0 WHATEVER the flags say -- the caller names the reason;
+ * MS3D_E_UNSUPPORTED is for bad arguments only (flags NULL, lattice < 1, V < 0, NULL coords / workspace with V > 0).  V == 0:
+ * *flags = 0, nothing is launched.  workspace: ms3d_coord_workspace_bytes(V). */
+#define MS3D_COORDS_OUT_OF_RANGE 1
+#define MS3D_COORDS_OFF_LATTICE 2
+#define MS3D_COORDS_REPEATED 4
+int ms3d_coords_check(const int *coords, int V, int lattice, int *flags /*[host]*/, void *workspace, size_t workspace_bytes,
+                      ms3d_stream_t stream);
+
 /* ---- arithmetic across coordinate sets: union of sets, feature combine, broadcast of one row per batch index.
  * ms3d_coords_union: the distinct coordinates of N sets (1 <= N <= 16) of one tensor stride, handed over back to back as coords
  * [set_start[N], 4] with HOST offsets set_start [N + 1] (set_start[0] = 0, ascending; set i = rows set_start[i] ..

@@ -60,18 +60,34 @@ Dense tensors in and out, and the per-sample views of a batch:
     channel is != 0 (NaN counts, -0.0 does not) and orders the rows like torch.nonzero; a row outside the grid, a coordinate
     off the stride lattice and a repeated coordinate raise ValueError (nothing is clipped or summed silently).  "BXXXC" input is permuted and copied contiguous once.
 
+Coordinate map keys, and layers onto coordinates the caller names:
+
+    CoordinateMapKey (a manager plus a tensor stride: hashable, get_tensor_stride(), get_coordinate_size()),
+    SparseTensor.coordinate_map_key, CoordinateManager.get_coordinates(key),
+    SparseTensor(features, coordinate_map_key=key[, coordinate_manager=...]): a new tensor on an existing set, features in the
+    order of that set's .coordinates (SparseTensor(F, coordinate_manager=cm, tensor_stride=ts) stays the engine's form: rows
+    as the manager HOLDS them);
+    `coordinates=` on MinkowskiConvolution (keyword only), MinkowskiConvolutionTranspose, MinkowskiChannelwiseConvolution,
+    MinkowskiMaxPooling / AvgPooling / SumPooling and MinkowskiPoolingTranspose: an integer tensor [M, 4] (validated once by
+    ms3d_coords_check, csrc/coords.hip: out of range, off the stride lattice and repeated rows raise ValueError), a
+    CoordinateMapKey or a SparseTensor; the output lives on that set, a row no input reaches is zero or the bias;
+    expand_coordinates=True on MinkowskiConvolution (stride 1), MinkowskiConvolutionTranspose and MinkowskiPoolingTranspose:
+    the output set is every coordinate the kernel reaches  (+ CoordinateManager.target_map / expand: engine extras)
+
 Not supported (each raises NotImplementedError naming it): a dense grid of more than 2^31 - 1 cells, to_sparse of a tensor
 that is not 5-D ([B, C, X, Y, Z]: dimension 3) or in a format other than "BCXXX" / "BXXXC", dense() on a per-axis tensor stride, strides other than 1 and 2, a generative layer at stride 2 on an odd
-tensor stride, MinkowskiConvolutionTranspose onto a coordinate set that is not cached, convolutions (expand_coordinates) or
-pooling that create coordinates, `+=` and ME.cat across different coordinate sets, a union of more than 16 tensors,
+tensor stride, MinkowskiConvolutionTranspose onto a coordinate set that is not cached when neither `coordinates=` nor
+expand_coordinates says where to, expand_coordinates on a stride-2 MinkowskiConvolution, forward pooling that creates
+coordinates, `+=` and ME.cat across different coordinate sets, a union of more than 16 tensors,
 the `quantization_mode` argument of SparseTensor itself (quantise with a field), interpolation gradients with respect to the
-coordinates, pooling transpose at strides other than 1 and 2 or onto a set that is not cached, dimension != 3, per-axis kernel
+coordinates, pooling transpose at strides other than 1 and 2 or (without `coordinates=` / expand_coordinates) onto a set that is not
+cached, dimension != 3, per-axis kernel
 tuples.
 
 Module/parameter names match ME so reference state_dicts keep their keys (`kernel`, `bn.weight`, ...).
 """
 from . import utils  # noqa: F401
-from .tensor import SparseTensor, CoordinateManager, cat, prefetch_coordinates  # noqa: F401
+from .tensor import SparseTensor, CoordinateManager, CoordinateMapKey, cat, prefetch_coordinates  # noqa: F401
 from .tensor import TensorField, SparseTensorQuantizationMode  # noqa: F401
 from .tensor import to_sparse, to_sparse_all  # noqa: F401
 from .modules import (MinkowskiConvolution, MinkowskiConvolutionTranspose, MinkowskiBatchNorm,  # noqa: F401

@@ -16,17 +16,20 @@ import torch.nn as nn
 
 from ..backend import get_backend
 from . import functional as Fn
-from .tensor import SparseTensor, check_geometry, union_op, to_sparse, to_sparse_all
+from .tensor import SparseTensor, CoordinateMapKey, check_geometry, union_op, to_sparse, to_sparse_all, target_key
 
 
 class _ConvBase(nn.Module):
     _two_sets = False     # True: input and output coordinate sets differ at every stride (no mirrored backward-data weights)
 
-    def __init__(self, in_channels, out_channels, kernel_size=-1, stride=1, dilation=1, bias=False, dimension=3):
+    def __init__(self, in_channels, out_channels, kernel_size=-1, stride=1, dilation=1, bias=False, dimension=3,
+                 expand_coordinates=False):
         super().__init__()
         if dimension != 3:
             raise NotImplementedError(f"dimension={dimension}: only 3-D sparse tensors are supported")
         check_geometry(kernel_size, stride, dilation)
+        self.expand_coordinates = bool(expand_coordinates)
+        self._check_expand(kernel_size, stride, dilation)
         self.in_channels, self.out_channels = in_channels, out_channels
         self.kernel_size, self.stride, self.dilation = kernel_size, stride, dilation
         K = kernel_size ** 3
@@ -50,6 +53,37 @@ class _ConvBase(nn.Module):
         old = (self.kernel_size, self.stride, self.dilation) in ((3, 1, 1), (2, 2, 1)) or K == 1
         return Fn.ConvSpec(nbr_fwd, nbr_bwd, vin, vout, K, cin, cout, mirror, None if old else mirror), out_ts
 
+    def _check_expand(self, kernel_size, stride, dilation):
+        """refusals of expand_coordinates=True at construction (the subclasses that restrict it)"""
+
+    def _image_mirror(self):
+        """does prepare_conv_weights lay this module's backward-data image out with mirrored offsets: the layers that map a
+        coordinate set onto ITSELF (odd kernel, stride 1, one set) -- never a module constructed with expand_coordinates,
+        whose output set is another one on every call"""
+        return (self.kernel_size % 2 == 1 and self.kernel_size > 1 and self.stride == 1 and not self._two_sets
+                and not self.expand_coordinates)
+
+    def _kernel_two_sets(self):
+        """the kernel of a call whose table maps the input set onto ANOTHER set (mirror = False: a target given by
+        `coordinates=`): where prepare_conv_weights laid this module's image out mirrored, an UNSTAMPED alias of the parameter
+        -- the call lays its own images out and its weight gradient goes straight to the parameter, not through the window's
+        mirrored image or its deferred-reduction group; otherwise the kernel of any call"""
+        return self.kernel.view_as(self.kernel) if self._image_mirror() else self._kernel()
+
+    def _conv_onto(self, x, out_cm, out_ts, table):
+        """y = conv(x) over `table` = (nbr_fwd, nbr_bwd, vin, vout, K) between two different coordinate sets -> SparseTensor on
+        (out_cm, out_ts).  sub = False keeps a K = 27 table off the submanifold backward-weight route, as the generative layer
+        does; a pending BatchNorm / ReLU flows into the gather.  An empty target gives an empty tensor (no launch)."""
+        nbr_fwd, nbr_bwd, vin, vout, K = table
+        cin, cout = self.in_channels, self.out_channels
+        kernel = self._kernel_two_sets()
+        if vout == 0:
+            y = x._raw()[:0] @ kernel.reshape(-1, cin, cout)[0]
+            return SparseTensor(y if self.bias is None else y + self.bias, coordinate_manager=out_cm, tensor_stride=out_ts)
+        spec = Fn.ConvSpec(nbr_fwd, nbr_bwd, vin, vout, K, cin, cout, False, False)
+        y, stats = Fn.conv(x._F, kernel, spec, x._pending, want_stats=self.training, bias=self.bias)
+        return SparseTensor(y, coordinate_manager=out_cm, tensor_stride=out_ts, _stats=stats)
+
     def _kernel(self):
         """the kernel this forward uses: the parameter, or -- inside a prepare_conv_weights window in training -- its
         alias behind the group's GroupFlushFn node (same storage; the gradient reaches the parameter through that node)"""
@@ -60,7 +94,8 @@ class _ConvBase(nn.Module):
 
     def extra_repr(self):
         return (f"in={self.in_channels}, out={self.out_channels}, kernel_size={self.kernel_size}, stride={self.stride}, "
-                f"dilation={self.dilation}, bias={self.bias is not None}")
+                f"dilation={self.dilation}, bias={self.bias is not None}"
+                + (", expand_coordinates=True" if self.expand_coordinates else ""))
 
 
 def _flush_group(name):
@@ -111,8 +146,8 @@ def prepare_conv_weights(root, precision=None):
             if buf is None or buf.device != m.kernel.device:
                 buf = m.__dict__["_wf_buf"] = torch.empty(be.wf_floats(K, cin, cout), dtype=torch.float32, device=m.kernel.device)
             # same orientation rule as the forward() of the module: 3x3x3 maps mirror their offsets in backward-data
-            layers.append((m.kernel, buf, K, cin, cout,
-                           m.kernel_size % 2 == 1 and m.kernel_size > 1 and m.stride == 1 and not m._two_sets, m, grp))
+            # (per module: _ConvBase._image_mirror)
+            layers.append((m.kernel, buf, K, cin, cout, m._image_mirror(), m, grp))
     prec = Fn.conv_precision(be) if precision is None else precision
     be.prep_weights_multi([l[:6] for l in layers], **Fn._pk(prec))
     token = be.weight_token
@@ -146,12 +181,44 @@ class MinkowskiConvolution(_ConvBase):
     """Any kernel size and dilation at stride 1 (odd sizes: submanifold, output coords = input coords) or stride 2 (output on
     the stride-2 coordinate set, whatever the kernel size).  k3 s1, k2 s2 and k1 s1 -- the reference's layers -- run on the
     tables, pair lists and fused blocks tuned for them; every other geometry walks its table with the general kernels,
-    untuned.  Strides other than 1 and 2, even kernels at stride 1 and per-axis tuples raise NotImplementedError."""
+    untuned.  Strides other than 1 and 2, even kernels at stride 1 and per-axis tuples raise NotImplementedError.
 
-    def forward(self, x: SparseTensor, residual: SparseTensor = None, skip=None):
+    forward(x, coordinates=target) writes onto a coordinate set the caller names -- an integer tensor [M, 4], a
+    CoordinateMapKey or a SparseTensor (tensor.target_key) at tensor stride ts * stride: out[o] = bias + sum_k x[o + off_k]
+    W[k], off = kernel_offsets(kernel_size, dilation, ts); a row no input reaches is the bias.  A target that names the set
+    the layer lands on anyway takes the ordinary path.  expand_coordinates=True (stride 1 only): the output set is every
+    coordinate the kernel reaches, CoordinateManager.expand, on a manager rooted at the tensor stride."""
+
+    def _check_expand(self, kernel_size, stride, dilation):
+        if self.expand_coordinates and stride != 1:
+            raise NotImplementedError(f"MinkowskiConvolution(kernel_size={kernel_size}, stride={stride}, "
+                                      f"expand_coordinates=True): expand_coordinates is supported at stride 1 only")
+
+    def _forward_onto(self, x, residual, skip, coordinates):
+        if coordinates is not None and self.expand_coordinates:
+            raise ValueError("MinkowskiConvolution: expand_coordinates=True derives the output set, coordinates= names it: "
+                             "not both")
+        if residual is not None or skip is not None:
+            raise ValueError("MinkowskiConvolution: residual / skip (engine extras of the submanifold layers) cannot be "
+                             "combined with " + ("coordinates=" if coordinates is not None else "expand_coordinates=True"))
+        cm, ts = x.coordinate_manager, x.tensor_stride
+        if coordinates is None:
+            gen = cm.expand(ts, self.kernel_size, self.dilation)
+            return self._conv_onto(x, gen[0], ts, gen[1:])
+        out_ts = ts * self.stride
+        key = target_key(coordinates, out_ts, x.device)
+        if key.coordinate_manager is cm:
+            return self.forward(x)          # the set this layer lands on anyway: its own at stride 1, the cached one at 2
+        table = cm.target_map(ts, key, self.kernel_size, self.stride, self.dilation)
+        return self._conv_onto(x, key.coordinate_manager, out_ts, table)
+
+    def forward(self, x: SparseTensor, residual: SparseTensor = None, skip=None, *, coordinates=None):
         """`residual` (same coordinate map as the output) is added in the kernel epilogue -- used by ResidualBlock
         instead of a separate `+=` pass; `skip` = ("head" | "tail", functional.SkipLink) routes the skip connection's
-        gradient through the block's first convolution instead of an elementwise add.  Neither is part of ME's API."""
+        gradient through the block's first convolution instead of an elementwise add.  Neither is part of ME's API.
+        `coordinates` (keyword only): the set to write onto, see the class."""
+        if coordinates is not None or self.expand_coordinates:
+            return self._forward_onto(x, residual, skip, coordinates)
         cm, ts = x.coordinate_manager, x.tensor_stride
         cin, cout = self.in_channels, self.out_channels
         ks, stride = self.kernel_size, self.stride
@@ -192,10 +259,29 @@ class MinkowskiConvolution(_ConvBase):
 class MinkowskiConvolutionTranspose(_ConvBase):
     """stride-2 transposed convolution of any kernel size: the output lives on the cached coordinate set of stride ts/2
     (the encoder's) and the table is the inverse of the matching strided map.  A transposed convolution that would have to
-    CREATE coordinates (stride 1, or an input that was never downsampled from a finer set) is not supported."""
+    CREATE coordinates (stride 1, or an input that was never downsampled from a finer set) is not supported -- unless the
+    caller names the output set or asks for all of it:
 
-    def forward(self, x: SparseTensor):
+    forward(x, coordinates) / forward(x, coordinates=target): onto an integer tensor [M, 4], a CoordinateMapKey or a
+    SparseTensor (tensor.target_key) at tensor stride ts // stride, at stride 1 or 2: out[o] = bias + sum_k x[o - off_k] W[k],
+    off = kernel_offsets(kernel_size, dilation, ts // stride) -- the rule of generate(); the cached finer set of the same
+    manager at stride 2 takes the ordinary path.  expand_coordinates=True: the code path of
+    MinkowskiGenerativeConvolutionTranspose (the same CoordinateManager.generate entry, hence the same output manager)."""
+
+    def forward(self, x: SparseTensor, coordinates=None):
         cm, ts = x.coordinate_manager, x.tensor_stride
+        if coordinates is not None or self.expand_coordinates:
+            if coordinates is not None and self.expand_coordinates:
+                raise ValueError("MinkowskiConvolutionTranspose: expand_coordinates=True derives the output set, coordinates= "
+                                 "names it: not both")
+            if coordinates is None:
+                return MinkowskiGenerativeConvolutionTranspose.forward(self, x)
+            out_ts = _transposed_stride(self, ts)
+            key = target_key(coordinates, out_ts, x.device)
+            if not (key.coordinate_manager is cm and self.stride == 2):
+                return self._conv_onto(x, key.coordinate_manager, out_ts,
+                                       cm.target_map(ts, key, self.kernel_size, self.stride, self.dilation, transposed=True))
+            # (the cached finer set of this manager: the ordinary path below)
         if self.stride != 2 or ts % 2 != 0 or (ts // 2) not in cm.coords:
             raise NotImplementedError(f"MinkowskiConvolutionTranspose(kernel_size={self.kernel_size}, stride={self.stride}) on "
                                       f"tensor stride {ts}: only stride 2 onto a cached finer coordinate set; generating "
@@ -206,6 +292,15 @@ class MinkowskiConvolutionTranspose(_ConvBase):
                            fwd.sub)
         y, stats = Fn.conv(x._F, self._kernel(), spec, x._pending, want_stats=self.training, bias=self.bias)
         return x._like(y, tensor_stride=fine, stats=stats)
+
+
+def _transposed_stride(layer, ts):
+    """output tensor stride of a transposed layer onto given coordinates; an input stride the layer's stride does not divide
+    is refused in the wording of CoordinateManager.generate"""
+    if ts % layer.stride != 0:
+        raise NotImplementedError(f"kernel_size={layer.kernel_size}, stride={layer.stride}, dilation={layer.dilation} on tensor "
+                                  f"stride {ts}: a generative stride-2 layer needs an even tensor stride")
+    return ts // layer.stride
 
 
 class MinkowskiGenerativeConvolutionTranspose(_ConvBase):
@@ -255,9 +350,21 @@ class MinkowskiChannelwiseConvolution(nn.Module):
             if bias:
                 self.bias.uniform_(-s, s)
 
-    def forward(self, x: SparseTensor):
+    def forward(self, x: SparseTensor, coordinates=None):
+        """coordinates: the set to write onto (an integer tensor [M, 4], a CoordinateMapKey or a SparseTensor at tensor stride
+        ts * stride, tensor.target_key); a row no input reaches is the bias"""
         cm, ts = x.coordinate_manager, x.tensor_stride
         geom = (self.kernel_size, self.stride, self.dilation)
+        if coordinates is not None:
+            key = target_key(coordinates, ts * self.stride, x.device)
+            if key.coordinate_manager is not cm:
+                nbr_fwd, nbr_inv, vin, vout, K = cm.target_map(ts, key, *geom)
+                if vout == 0:
+                    y = x._raw()[:0] * self.kernel[:1]
+                    y = y if self.bias is None else y + self.bias
+                else:
+                    y = Fn.channelwise_conv(x._raw(), self.kernel, self.bias, nbr_fwd, nbr_inv, vin, vout, K)
+                return SparseTensor(y, coordinate_manager=key.coordinate_manager, tensor_stride=key.tensor_stride)
         nbr_fwd, _, vin, vout, K, out_ts, _ = cm.kernel_map(ts, *geom)
         nbr_inv = cm.kernel_map_inverse(ts, *geom)
         y = Fn.channelwise_conv(x._raw(), self.kernel, self.bias, nbr_fwd, nbr_inv, vin, vout, K)
@@ -407,6 +514,14 @@ class MinkowskiReLU(nn.Module):
         return x._like(torch.relu(x._raw()))
 
 
+def _pool_onto(x, key, table, mode):
+    """pooling (mode 0 max, 1 average, 2 sum) of x over `table` = (nbr_fwd, nbr_inv, vin, vout, K) onto the set `key` names"""
+    nbr_fwd, nbr_inv, vin, vout, K = table
+    rows = x._raw()
+    y = rows[:0] if vout == 0 else Fn.sparse_pool(rows, nbr_fwd, nbr_inv, vin, vout, K, mode)
+    return SparseTensor(y, coordinate_manager=key.coordinate_manager, tensor_stride=key.tensor_stride)
+
+
 class _PoolBase(nn.Module):
     """pooling over the kernel map of (kernel_size, stride, dilation): same geometries as the convolutions (stride 1 with an
     odd kernel: output coords = input coords; stride 2: the stride-2 coordinate set).  A pending BatchNorm / ReLU in front
@@ -420,8 +535,15 @@ class _PoolBase(nn.Module):
         check_geometry(kernel_size, stride, dilation)
         self.kernel_size, self.stride, self.dilation = kernel_size, stride, dilation
 
-    def forward(self, x: SparseTensor):
+    def forward(self, x: SparseTensor, coordinates=None):
+        """coordinates: the set to write onto (an integer tensor [M, 4], a CoordinateMapKey or a SparseTensor at tensor stride
+        ts * stride, tensor.target_key); a row no input reaches is zero"""
         cm, ts = x.coordinate_manager, x.tensor_stride
+        if coordinates is not None:
+            key = target_key(coordinates, ts * self.stride, x.device)
+            if key.coordinate_manager is not cm:
+                table = cm.target_map(ts, key, self.kernel_size, self.stride, self.dilation)
+                return _pool_onto(x, key, table, self.MODE)
         nbr_fwd, _, vin, vout, K, out_ts, _ = cm.kernel_map(ts, self.kernel_size, self.stride, self.dilation)
         nbr_inv = cm.kernel_map_inverse(ts, self.kernel_size, self.stride, self.dilation)
         y = Fn.sparse_pool(x._raw(), nbr_fwd, nbr_inv, vin, vout, K, self.MODE)
@@ -453,16 +575,32 @@ class MinkowskiPoolingTranspose(nn.Module):
     uncached target raises NotImplementedError), stride 1 (odd kernels) stays on the set.  Sum pooling (csrc/pool.hip) over
     the transposed table forward, through the forward table backward.  Strides other than 1 and 2 are not supported."""
 
-    def __init__(self, kernel_size, stride, dilation=1, dimension=3):
+    def __init__(self, kernel_size, stride, dilation=1, dimension=3, expand_coordinates=False):
         super().__init__()
         if dimension != 3:
             raise NotImplementedError(f"dimension={dimension}: only 3-D sparse tensors are supported")
         check_geometry(kernel_size, stride, dilation)
         self.kernel_size, self.stride, self.dilation = kernel_size, stride, dilation
+        self.expand_coordinates = bool(expand_coordinates)
 
-    def forward(self, x: SparseTensor):
+    def forward(self, x: SparseTensor, coordinates=None):
+        """coordinates: the set to write onto (an integer tensor [M, 4], a CoordinateMapKey or a SparseTensor at tensor stride
+        ts // stride, tensor.target_key): out[o] = sum_k x[o - off_k], off = kernel_offsets(kernel_size, dilation, ts //
+        stride).  expand_coordinates=True: the same sum onto every coordinate the kernel reaches (CoordinateManager.generate:
+        the set and the tables of the generative transposed convolution of this geometry)."""
         cm, ts = x.coordinate_manager, x.tensor_stride
         geom = (self.kernel_size, self.stride, self.dilation)
+        if coordinates is not None or self.expand_coordinates:
+            if coordinates is not None and self.expand_coordinates:
+                raise ValueError("MinkowskiPoolingTranspose: expand_coordinates=True derives the output set, coordinates= names "
+                                 "it: not both")
+            if coordinates is None:
+                out_cm, nbr_fwd, nbr_bwd, vin, vout, K, out_ts = cm.generate(ts, *geom)
+                return _pool_onto(x, CoordinateMapKey(out_cm, out_ts), (nbr_fwd, nbr_bwd, vin, vout, K), 2)
+            key = target_key(coordinates, _transposed_stride(self, ts), x.device)
+            if key.coordinate_manager is not cm:
+                return _pool_onto(x, key, cm.target_map(ts, key, *geom, transposed=True), 2)
+            # (a set of this manager: its own at stride 1, the cached finer one at stride 2 -- the ordinary paths below)
         if self.stride == 1:
             # the transpose of a submanifold table is its mirror image, and a sum does not care about the offset order
             nbr, _, vin, vout, K, _, _ = cm.kernel_map(ts, *geom)
@@ -479,7 +617,8 @@ class MinkowskiPoolingTranspose(nn.Module):
         return x._like(y, tensor_stride=fine)
 
     def extra_repr(self):
-        return f"kernel_size={self.kernel_size}, stride={self.stride}, dilation={self.dilation}"
+        return (f"kernel_size={self.kernel_size}, stride={self.stride}, dilation={self.dilation}"
+                + (", expand_coordinates=True" if self.expand_coordinates else ""))
 
 
 class MinkowskiInterpolation(nn.Module):

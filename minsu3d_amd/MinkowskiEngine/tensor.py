@@ -43,6 +43,93 @@ def check_geometry(kernel_size, stride, dilation):
         raise NotImplementedError(f"{geom}: at most 254 kernel offsets (kernel_size <= 6)")
 
 
+class CoordinateMapKey:
+    """The name of ONE coordinate set: a coordinate manager plus a tensor stride -- the pair `+`, `cat`, `slice` and `union`
+    compare already.  Hashable; two keys are equal when the manager is the same object and the stride is equal.  What
+    `SparseTensor.coordinate_map_key` returns, what `SparseTensor(features, coordinate_map_key=...)` and the `coordinates=`
+    argument of the layers take."""
+    __slots__ = ("coordinate_manager", "tensor_stride")
+
+    def __init__(self, coordinate_manager, tensor_stride):
+        self.coordinate_manager, self.tensor_stride = coordinate_manager, tensor_stride
+
+    def __eq__(self, other):
+        return (isinstance(other, CoordinateMapKey) and other.coordinate_manager is self.coordinate_manager
+                and other.tensor_stride == self.tensor_stride)
+
+    def __ne__(self, other):
+        return not self == other
+
+    def __hash__(self):
+        return hash((id(self.coordinate_manager), self.tensor_stride))
+
+    def get_tensor_stride(self):
+        return [self.tensor_stride] * 3
+
+    def get_coordinate_size(self):
+        return 4
+
+    def __repr__(self):
+        return (f"CoordinateMapKey(tensor_stride={self.get_tensor_stride()}, coordinate_size=4, "
+                f"manager=0x{id(self.coordinate_manager):x})")
+
+
+_COORDS_FLAG_REASONS = ((1, "a row lies outside the packable range: a coordinate outside [-16384, 16384) or a batch index outside "
+                            "[0, 524288)"),
+                        (2, "a coordinate is not a multiple of the output tensor stride {ts}"),
+                        (4, "a coordinate occurs twice (the rows of an output set are distinct)"))
+_TARGET_SETS = {}     # (id of a coordinate tensor, output tensor stride, device) -> (rooted manager, the tensor, its version)
+
+
+def _target_rows(coordinates):
+    """the [M, 4] integer tensor a layer's `coordinates=` may be (checked before anything touches a backend)"""
+    if coordinates.dim() != 2 or coordinates.size(1) != 4 or coordinates.is_floating_point() or coordinates.is_complex() \
+            or coordinates.dtype == torch.bool:
+        raise ValueError(f"coordinates=: an integer tensor [M, 4] (b, x, y, z), a CoordinateMapKey or a SparseTensor, got a "
+                         f"tensor {list(coordinates.shape)} {coordinates.dtype}")
+
+
+def target_key(coordinates, out_ts, device):
+    """The coordinate set a layer was told to write onto (`coordinates=`) -> its CoordinateMapKey.
+    A CoordinateMapKey (or a SparseTensor: its key) names a set some manager holds; its stride must be the layer's output
+    stride `out_ts` (ValueError otherwise), nothing else is checked.  An integer tensor [M, 4] of (b, x, y, z), any integer
+    dtype, any device, is moved to `device` as int32 and becomes the only set of a manager rooted at out_ts that holds the rows
+    in the given order; it is validated ONCE by ms3d_coords_check (backend.coords_check), every raised bit a ValueError naming
+    it -- nothing is clipped, merged or dropped.  The manager is kept per tensor OBJECT and version (the four newest, with the
+    tensor): two layers handed the same tensor land on the same manager, an in-place edit makes a new one."""
+    if isinstance(coordinates, SparseTensor):
+        coordinates = coordinates.coordinate_map_key
+    if isinstance(coordinates, CoordinateMapKey):
+        if coordinates.tensor_stride != out_ts:
+            raise ValueError(f"coordinates=: the target set has tensor stride {coordinates.tensor_stride}, the layer's output "
+                             f"tensor stride is {out_ts}")
+        if coordinates.tensor_stride not in coordinates.coordinate_manager.coords:
+            raise ValueError(f"coordinates=: the key's manager holds no coordinate set of tensor stride {out_ts}")
+        return coordinates
+    if not torch.is_tensor(coordinates):
+        raise TypeError(f"coordinates=: an integer tensor [M, 4], a CoordinateMapKey or a SparseTensor, got "
+                        f"{type(coordinates).__name__}")
+    _target_rows(coordinates)
+    ident = (id(coordinates), out_ts, str(device))
+    hit = _TARGET_SETS.get(ident)
+    if hit is None or hit[1] is not coordinates or hit[2] != coordinates._version:
+        be = get_backend()
+        if not hasattr(be, "coords_check"):
+            raise NotImplementedError("a layer onto given coordinates needs the HIP backend (ms3d_coords_check)")
+        rows = coordinates.detach().to(device=device, dtype=torch.int32).contiguous()
+        if rows.numel() > 0 and rows.data_ptr() == coordinates.data_ptr():
+            rows = rows.clone()          # the set must not follow a later in-place edit of the caller's tensor
+        flags = be.coords_check(rows, out_ts)
+        for bit, reason in _COORDS_FLAG_REASONS:
+            if flags & bit:
+                raise ValueError("coordinates=: " + reason.format(ts=out_ts))
+        _TARGET_SETS.pop(ident, None)
+        hit = _TARGET_SETS[ident] = (CoordinateManager.rooted(rows, out_ts), coordinates, coordinates._version)
+        while len(_TARGET_SETS) > 4:
+            _TARGET_SETS.pop(next(iter(_TARGET_SETS)))
+    return CoordinateMapKey(hit[0], out_ts)
+
+
 class CoordinateManager:
     """coordinates per tensor stride and kernel maps per (stride, kind), built once and shared by every
     convolution of a level and by the backward pass (ME's coordinate manager does the same caching)."""
@@ -113,6 +200,67 @@ class CoordinateManager:
             nbr_bwd = be.kmap_invert(nbr_fwd, K, vout, vin)
             gen = cache[key] = (CoordinateManager.rooted(out, out_ts), nbr_fwd, nbr_bwd, vin, vout, K, out_ts)
         return gen
+
+    def get_coordinates(self, key):
+        """the rows of the coordinate set `key` names (a CoordinateMapKey of this manager, or a tensor stride) in the order the
+        CALLER sees them: visible_coords"""
+        if isinstance(key, CoordinateMapKey):
+            if key.coordinate_manager is not self:
+                raise ValueError("get_coordinates: the key names a set of another coordinate manager")
+            key = key.tensor_stride
+        if key not in self.coords:
+            raise ValueError(f"get_coordinates: this manager holds no coordinate set of tensor stride {key}")
+        return self.visible_coords(key)
+
+    def target_map(self, ts, key, kernel_size, stride=1, dilation=1, transposed=False):
+        """the kernel map of a layer from this manager's set of tensor stride ts ONTO the set `key` names (any manager) ->
+        (nbr_fwd [K, Vout], nbr_bwd [K, Vin], Vin, Vout, K).  Both sets are taken as their managers HOLD them (a Morton-sorted
+        stride-1 set through coords[1], not coords_external), like every table.  Forward layers (convolution, pooling,
+        channel-wise): nbr_fwd[k][o] = input row at target[o] + kernel_offsets(kernel_size, dilation, ts)[k].  Transposed layers
+        (transposed convolution, pooling transpose): nbr_fwd[k][o] = input row at target[o] - kernel_offsets(kernel_size,
+        dilation, key's stride)[k] -- y[o] = sum_k x[o - off_k] W[k], the rule of generate().  nbr_bwd is the inverse table
+        (the target's rows are distinct).  A target row no input reaches is a column of -1.  Built once per (ts, key, geometry,
+        direction) and kept on this manager with the key (the sixteen newest)."""
+        kernel_size, stride, dilation = int(kernel_size), int(stride), int(dilation)
+        cache = self.__dict__.setdefault("_target_maps", {})
+        ident = (ts, key, kernel_size, stride, dilation, bool(transposed))
+        hit = cache.get(ident)
+        if hit is None:
+            check_geometry(kernel_size, stride, dilation)
+            be = get_backend()
+            if not (hasattr(be, "kmap_general") and hasattr(be, "kmap_invert")):
+                raise NotImplementedError("a layer onto given coordinates needs the HIP backend (ms3d_kmap_general)")
+            out_ts = key.tensor_stride
+            offsets = kernel_offsets(kernel_size, dilation, out_ts if transposed else ts)
+            if transposed:
+                offsets = -offsets
+            cin, out = self.coords[ts], key.coordinate_manager.coords[out_ts]
+            vin, vout, K = cin.size(0), out.size(0), offsets.shape[0]
+            nbr_fwd = be.kmap_general(cin, out, torch.from_numpy(offsets))
+            hit = cache[ident] = (nbr_fwd, be.kmap_invert(nbr_fwd, K, vout, vin), vin, vout, K)
+            while len(cache) > 16:
+                cache.pop(next(iter(cache)))
+        return hit
+
+    def expand(self, ts, kernel_size, dilation=1):
+        """what a stride-1 convolution with expand_coordinates=True needs -> (manager rooted at ts on every coordinate the
+        kernel reaches, nbr_fwd [K, Vout], nbr_bwd [K, Vin], Vin, Vout, K): the set is every c - kernel_offsets(kernel_size,
+        dilation, ts)[k] over the rows c the CALLER sees, in first-occurrence order (backend.coords_expand, as generate()), the
+        tables are target_map's.  Built once per (ts, kernel size, dilation)."""
+        kernel_size, dilation = int(kernel_size), int(dilation)
+        check_geometry(kernel_size, 1, dilation)
+        cache = self.__dict__.setdefault("_expanded", {})
+        ident = (ts, kernel_size, dilation)
+        hit = cache.get(ident)
+        if hit is None:
+            be = get_backend()
+            if not (hasattr(be, "coords_expand") and hasattr(be, "kmap_general")):
+                raise NotImplementedError(f"kernel_size={kernel_size}, dilation={dilation}: expand_coordinates needs the HIP "
+                                          "backend (ms3d_coords_expand)")
+            out = be.coords_expand(self.visible_coords(ts), torch.from_numpy(-kernel_offsets(kernel_size, dilation, ts)))
+            out_cm = CoordinateManager.rooted(out, ts)
+            hit = cache[ident] = (out_cm,) + self.target_map(ts, CoordinateMapKey(out_cm, ts), kernel_size, 1, dilation)
+        return hit
 
     def visible_coords(self, ts):
         """the coordinates of tensor stride ts in the order the CALLER sees them (x.coordinates)"""
@@ -505,8 +653,38 @@ _SORT_MIN_ROWS = int(os.environ.get("MS3D_SORT_MIN_ROWS", "100000"))
 
 
 class SparseTensor:
-    def __init__(self, features, coordinates=None, device=None, coordinate_manager=None, tensor_stride=1,
-                 _pending=None, _stats=None):
+    def __init__(self, features, coordinates=None, device=None, coordinate_manager=None, tensor_stride=None,
+                 coordinate_map_key=None, _pending=None, _stats=None):
+        """Three forms.  SparseTensor(features, coordinates): a new manager; the rows stay in the caller's order.
+        SparseTensor(features, coordinate_map_key=key[, coordinate_manager=key's manager]): a new tensor on an EXISTING set;
+        `features` are in the CALLER's order, the order of `.coordinates` of that set, and go through one gather
+        (functional.PermuteRowsFn, gradients flow back) into the order a Morton-sorted manager holds them in.
+        SparseTensor(features, coordinate_manager=cm, tensor_stride=ts) is the ENGINE's constructor, used by every layer:
+        the rows are taken AS HELD by the manager, which on a Morton-sorted stride-1 set is not the order of `.coordinates`
+        / `.features` -- pass a key to hand over rows in that order."""
+        if coordinate_map_key is not None:
+            key = coordinate_map_key
+            if not isinstance(key, CoordinateMapKey):
+                raise ValueError(f"coordinate_map_key: a CoordinateMapKey, got {type(key).__name__}")
+            if coordinates is not None:
+                raise ValueError("coordinate_map_key names an existing coordinate set: pass either it or coordinates=, not both")
+            if coordinate_manager is not None and coordinate_manager is not key.coordinate_manager:
+                raise ValueError("coordinate_manager is not the manager of coordinate_map_key")
+            if tensor_stride is not None and tensor_stride != key.tensor_stride:
+                raise ValueError(f"tensor_stride={tensor_stride!r} differs from the tensor stride of coordinate_map_key, "
+                                 f"{key.tensor_stride}")
+            coordinate_manager, tensor_stride = key.coordinate_manager, key.tensor_stride
+            if tensor_stride not in coordinate_manager.coords:
+                raise ValueError(f"coordinate_map_key: its manager holds no coordinate set of tensor stride {tensor_stride}")
+            rows = coordinate_manager.size(tensor_stride)
+            if features.dim() != 2 or features.size(0) != rows:
+                raise ValueError(f"features {list(features.shape)}: the coordinate set of coordinate_map_key has {rows} rows")
+            if device is not None:
+                features = features.to(device)
+            if tensor_stride == 1 and coordinate_manager.perm is not None:
+                features = Fn.PermuteRowsFn.apply(features, coordinate_manager.perm, coordinate_manager.inv)
+        elif tensor_stride is None:
+            tensor_stride = 1
         if coordinate_manager is None:
             if device is not None:
                 features, coordinates = features.to(device), coordinates.to(device)
@@ -553,6 +731,11 @@ class SparseTensor:
         return cm.coords[self.tensor_stride]
 
     C = coordinates
+
+    @property
+    def coordinate_map_key(self):
+        """the CoordinateMapKey of this tensor's coordinate set: (its manager, its tensor stride)"""
+        return CoordinateMapKey(self.coordinate_manager, self.tensor_stride)
 
     @property
     def device(self):

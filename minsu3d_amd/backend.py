@@ -921,6 +921,21 @@ class _HipEngine:
             return out[:V], src[:V], dst
         return out[:n.value].clone(), src[:n.value].clone(), dst
 
+    def coords_check(self, coords, lattice):
+        """is the int32 [V, 4] coordinate set usable as a layer's output set on the lattice of tensor stride `lattice` -> the
+        flag bits of ms3d_coords_check: 1 a row outside the packable range / batch index outside [0, 524288), 2 a coordinate
+        that is not a multiple of `lattice`, 4 a coordinate that occurs twice; 0 = usable.  One host sync."""
+        coords = self._dev(coords)
+        assert coords.dtype == torch.int32 and coords.dim() == 2 and coords.size(1) == 4 and coords.is_contiguous()
+        V, dev = coords.size(0), coords.device
+        if V == 0:
+            return 0
+        ws = self._cws(V, dev)
+        flags = C.c_int(0)
+        _lib.check(self.lib.ms3d_coords_check(_lib.ptr(coords), V, int(lattice), C.byref(flags), _lib.ptr(ws),
+                                              C.c_size_t(ws.numel()), _lib.stream_handle()), "ms3d_coords_check")
+        return flags.value
+
     # ---- arithmetic across coordinate sets (csrc/coords.hip: union; csrc/setops.hip: the feature kernels)
     UNION_MAX_SETS = 16
 

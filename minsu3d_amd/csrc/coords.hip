@@ -121,6 +121,27 @@ __device__ __forceinline__ int table_lookup(const unsigned long long *__restrict
     }
 }
 
+// validation of a caller-supplied coordinate set (ms3d_coords_check), behind table_clear / table_insert (which raise bit 0 for
+// a row that does not fit the key): one thread per row; bit 1 = a coordinate is not a multiple of `lattice` (the floor_div
+// arithmetic of the strided sets: floor(v / q) * q == v), bit 2 = the row is not the first holder of its key's slot (the
+// coordinate occurs twice).  A row that does not fit the key aliases another coordinate, so it is not asked about repeats.
+// One device int collects the bits; a thread ORs only the bits it does not see up yet (a handful of atomics per call).
+__global__ __launch_bounds__(256) void coords_check_kernel(const int *__restrict__ coords, int n, int lattice,
+                                                           const int *__restrict__ slot_of_row, const int *__restrict__ vals,
+                                                           int *flags)
+{
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const int4 c = reinterpret_cast<const int4 *>(coords)[i];
+    int bits = 0;
+    if (floor_div(c.y, lattice) * lattice != c.y || floor_div(c.z, lattice) * lattice != c.z ||
+        floor_div(c.w, lattice) * lattice != c.w)
+        bits |= MS3D_COORDS_OFF_LATTICE;
+    const bool fits = in_range(c.y) && in_range(c.z) && in_range(c.w) && c.x >= 0 && c.x <= 0x7FFFF;
+    if (fits && vals[slot_of_row[i]] != i) bits |= MS3D_COORDS_REPEATED;
+    if (bits && (*flags & bits) != bits) atomicOr(flags, bits);
+}
+
 // one thread per (offset, row): writes nbr[k][i]; consecutive threads -> consecutive rows (coalesced stores)
 __global__ void kmap_k3_kernel(const int *__restrict__ coords, int V, int ts, const unsigned long long *__restrict__ keys,
                                const int *__restrict__ vals, unsigned mask, int *__restrict__ nbr)
@@ -883,6 +904,28 @@ int ms3d_coords_prune(const int *coords, int V, const unsigned char *keep, int *
     prune_emit_kernel<<<grid, 256, 0, stream>>>(V, coords, keep, w.rank, out_coords, src_row, dst_row);
     MS3D_LAUNCH_CHECK();
     MS3D_CHECK(hipStreamSynchronize(stream));
+    return 0;
+}
+
+int ms3d_coords_check(const int *coords, int V, int lattice, int *flags, void *workspace, size_t workspace_bytes,
+                      ms3d_stream_t stream_)
+{
+    hipStream_t stream = (hipStream_t)stream_;
+    if (!flags) return MS3D_E_UNSUPPORTED;
+    *flags = 0;
+    if (lattice < 1 || V < 0) return MS3D_E_UNSUPPORTED;
+    if (V == 0) return 0;
+    if (!coords || !workspace) return MS3D_E_UNSUPPORTED;
+    CoordWs w;
+    if (carve(w, V, workspace) > workspace_bytes) return MS3D_E_WORKSPACE;
+    int rc = build_table(w, coords, V, 1, stream);      // (clears w.total[1] and raises MS3D_COORDS_OUT_OF_RANGE in it)
+    if (rc) return rc;
+    coords_check_kernel<<<ms3d_divup(V, 256), 256, 0, stream>>>(coords, V, lattice, w.slot_of_row, w.vals, w.total + 1);
+    MS3D_LAUNCH_CHECK();
+    int h = 0;
+    MS3D_CHECK(hipMemcpyAsync(&h, w.total + 1, sizeof(int), hipMemcpyDeviceToHost, stream));
+    MS3D_CHECK(hipStreamSynchronize(stream));
+    *flags = h;
     return 0;
 }
 
