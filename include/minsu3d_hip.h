@@ -206,6 +206,25 @@ int ms3d_kmap_general(const int *in_coords, int Vin, const int *out_coords, int 
  * scatter is collision free: plain stores).  Backward-data of a strided convolution, pooling backward and transposed
  * convolutions onto a cached coordinate set walk it. */
 int ms3d_kmap_invert(const int *nbr, int K, int Vout, int Vin, int *nbr_inv, ms3d_stream_t stream);
+/* Region map: the kernel map of a coordinate set onto ITSELF over an arbitrary offset list (a cross, a hand-written list:
+ * lists that are not their own mirror image k <-> K-1-k), the forward table nbr_fwd[K][V] -- ms3d_kmap_general(coords, coords,
+ * offsets) for ANY input, repeated rows included -- AND its inverse nbr_inv[K][V] -- ms3d_kmap_invert of it -- from one pass
+ * over one hash table.  nbr_inv is specified for DISTINCT rows only (with repeated rows its bytes are still the same on every
+ * run: only the first row of a coordinate writes into it).  offsets: DEVICE int[K][3] in voxel units, distinct rows.
+ * partner: HOST int[K], partner[k] = the index of -offsets[k] in the list: k itself for the zero offset, -1 when the list
+ * lacks the opposite offset; it is read before anything is launched and handed to the kernel by value.  For distinct rows
+ * nbr_fwd[k][i] = j implies nbr_fwd[p][j] = i, nbr_inv[p][i] = j and nbr_inv[k][j] = i with p = partner[k], so only one
+ * offset of each partnered pair is looked up and the thread stores all four entries; an unpartnered offset costs one lookup
+ * plus one collision-free scatter into nbr_inv, the zero offset none.  Only the row that the table names for its own key (the
+ * first occurrence) writes mirrored entries; any other row does its own lookups and writes only its own column: every entry
+ * has exactly one writer, no atomics on the tables, no host synchronisation, the same bytes on every run.  A shifted
+ * coordinate outside the packable range [-16384, 16384) gives -1, in both tables.
+ * Decided on the host before anything is launched: K < 1 or K > 254, or a partner that is not an involution (out of range, or
+ * partner[partner[k]] != k): MS3D_E_UNSUPPORTED; a short workspace: MS3D_E_WORKSPACE; V == 0 with valid arguments: returns
+ * 0, launches nothing.  workspace: ms3d_coord_workspace_bytes(V). */
+int ms3d_kmap_region(const int *coords, int V, const int *offsets /*DEVICE [K][3]*/, const int *partner /*HOST [K]*/, int K,
+                     int *nbr_fwd /*[K][V]*/, int *nbr_inv /*[K][V]*/, void *workspace, size_t workspace_bytes,
+                     ms3d_stream_t stream);
 
 /* ---- coordinate sets that are not derived by flooring: generation and pruning.
  * ms3d_coords_expand: the set of distinct (batch of row i, xyz of row i + offsets[k]) over all input rows i and offsets k, in

@@ -74,7 +74,28 @@ Coordinate map keys, and layers onto coordinates the caller names:
     expand_coordinates=True on MinkowskiConvolution (stride 1), MinkowskiConvolutionTranspose and MinkowskiPoolingTranspose:
     the output set is every coordinate the kernel reaches  (+ CoordinateManager.target_map / expand: engine extras)
 
-Not supported (each raises NotImplementedError naming it): a dense grid of more than 2^31 - 1 cells, to_sparse of a tensor
+Kernel regions -- crosses and hand-written offset lists:
+
+    RegionType (HYPER_CUBE, HYPER_CROSS, CUSTOM), KernelGenerator(kernel_size, stride, dilation, is_transpose, region_type,
+    region_offsets, expand_coordinates, axis_types, dimension) and `kernel_generator=` on MinkowskiConvolution,
+    MinkowskiConvolutionTranspose, MinkowskiGenerativeConvolutionTranspose, MinkowskiChannelwiseConvolution,
+    MinkowskiMaxPooling / AvgPooling / SumPooling and MinkowskiPoolingTranspose  (+ KernelGenerator.offsets(tensor_stride),
+    `region=` on CoordinateManager.kernel_map / kernel_map_inverse / target_map / generate / expand: engine extras)
+
+    The offset rules, chosen here -- MinkowskiEngine's as recalled, not pinned, like the conventions above:
+    HYPER_CUBE is kernel_offsets(kernel_size, dilation, ts), K = kernel_size ** 3, and the layer is the plain layer (same
+    tables, same tuned routes).  HYPER_CROSS (odd kernel sizes, h = (kernel_size - 1) // 2, K = 6 h + 1): the centre first,
+    then axis x at -h .. -1, +1 .. +h, then y, then z, each times dilation * ts; size 1 is the cube of size 1.  CUSTOM:
+    region_offsets, an integer tensor or array [K, 3] with 1 <= K <= 254 and distinct rows, in the order given, times ts only
+    (dilation must be 1, kernel_size is ignored).  `kernel` is (K, in, out) -- (K, C) channel-wise --, init bound 1 / sqrt(in
+    * K).  A cross or custom layer always works between "two sets", even at stride 1 on its own set: forward table and
+    inverse table from one pass of ms3d_kmap_region (csrc/coords.hip: one lookup per partnered pair of offsets, four stores),
+    no mirrored weight image, never the K = 27 / K = 8 tuned routes; `residual=` / `skip=` are refused on it (ValueError).
+    A layer argument that contradicts the generator, an even cross, repeated custom rows and CUSTOM with dilation != 1 raise
+    ValueError.
+
+Not supported (each raises NotImplementedError naming it): `axis_types` of a KernelGenerator, a region of more than 254
+offsets, a dense grid of more than 2^31 - 1 cells, to_sparse of a tensor
 that is not 5-D ([B, C, X, Y, Z]: dimension 3) or in a format other than "BCXXX" / "BXXXC", dense() on a per-axis tensor stride, strides other than 1 and 2, a generative layer at stride 2 on an odd
 tensor stride, MinkowskiConvolutionTranspose onto a coordinate set that is not cached when neither `coordinates=` nor
 expand_coordinates says where to, expand_coordinates on a stride-2 MinkowskiConvolution, forward pooling that creates
@@ -82,7 +103,7 @@ coordinates, `+=` and ME.cat across different coordinate sets, a union of more t
 the `quantization_mode` argument of SparseTensor itself (quantise with a field), interpolation gradients with respect to the
 coordinates, pooling transpose at strides other than 1 and 2 or (without `coordinates=` / expand_coordinates) onto a set that is not
 cached, dimension != 3, per-axis kernel
-tuples.
+tuples; and, as ValueError, an even HYPER_CROSS kernel size and a CUSTOM region with dilation != 1.
 
 Module/parameter names match ME so reference state_dicts keep their keys (`kernel`, `bn.weight`, ...).
 """
@@ -90,6 +111,7 @@ from . import utils  # noqa: F401
 from .tensor import SparseTensor, CoordinateManager, CoordinateMapKey, cat, prefetch_coordinates  # noqa: F401
 from .tensor import TensorField, SparseTensorQuantizationMode  # noqa: F401
 from .tensor import to_sparse, to_sparse_all  # noqa: F401
+from .tensor import RegionType, KernelGenerator  # noqa: F401
 from .modules import (MinkowskiConvolution, MinkowskiConvolutionTranspose, MinkowskiBatchNorm,  # noqa: F401
                       MinkowskiReLU, prepare_conv_weights, release_conv_weights,
                       MinkowskiMaxPooling, MinkowskiAvgPooling, MinkowskiSumPooling, MinkowskiGlobalMaxPooling,

@@ -4,8 +4,9 @@ v0.5.4): `kernel` of shape (K, in, out) -- (in, out) fo
 nn.BatchNorm1d`.
 
 Convolutions take any integer kernel size and dilation with stride 1 (odd sizes) or 2; pooling layers walk the same
-kernel maps.  What MinkowskiEngine does for the geometries beyond the reference's three -- the offset order of even
-kernels, average pooling dividing by the number of inputs PRESENT, the bias shape -- is written down from memory of
+kernel maps.  `kernel_generator=` (tensor.KernelGenerator) hands the same geometry over as one object, and with it the
+crosses and hand-written offset lists (_layer_geometry).  What MinkowskiEngine does for the geometries beyond the
+reference's three -- the offset order of even kernels, the offset order of a cross, average pooling dividing by the number of inputs PRESENT, the bias shape -- is written down from memory of
 its v0.5 sources: MinkowskiEngine is not installed where this package is developed (as SURVEY Appendix A says of the
 conventions it recalls), so these are this engine's definitions, checked against dense torch operators."""
 import math
@@ -17,24 +18,54 @@ import torch.nn as nn
 from ..backend import get_backend
 from . import functional as Fn
 from .tensor import SparseTensor, CoordinateMapKey, check_geometry, union_op, to_sparse, to_sparse_all, target_key
+from .tensor import KernelGenerator
+
+
+def _layer_geometry(layer, kernel_size, stride, dilation, kernel_generator, expand_coordinates=False):
+    """the geometry of a layer built with `kernel_generator=` -> (kernel_size, stride, dilation, region, expand_coordinates,
+    kernel volume).  Without a generator: the layer's own arguments through check_geometry, region None.  With one, kernel
+    size, stride, dilation and region come from it; a layer argument that was given (is not its default -1 / 1 / 1) and
+    says otherwise is a ValueError (the kernel size of a CUSTOM region is ignored); expand_coordinates is "layer argument
+    or generator attribute".  A HYPER_CUBE generator comes back with region None: the layer IS the plain layer."""
+    if kernel_generator is None:
+        check_geometry(kernel_size, stride, dilation)
+        return kernel_size, stride, dilation, None, bool(expand_coordinates), kernel_size ** 3
+    g = kernel_generator
+    if not isinstance(g, KernelGenerator):
+        raise TypeError(f"{layer}: kernel_generator must be a KernelGenerator, got {type(g).__name__}")
+    given = (("stride", stride, 1, g.stride), ("dilation", dilation, 1, g.dilation))
+    if not (g.region_key is not None and g.region_key[0] == "CUSTOM"):
+        given = (("kernel_size", kernel_size, -1, g.kernel_size),) + given
+    for name, value, default, theirs in given:
+        if value != default and value != theirs:
+            raise ValueError(f"{layer}: {name}={value} contradicts the kernel_generator's {name}={theirs}")
+    return (g.kernel_size, g.stride, g.dilation, g.region_key, bool(expand_coordinates) or g.expand_coordinates,
+            g.kernel_volume)
+
+
+def _region_name(region):
+    """how extra_repr names a region"""
+    return "" if region is None else f", region={region[0]}[{region[1] if region[0] == 'HYPER_CROSS' else len(region[1])}]"
 
 
 class _ConvBase(nn.Module):
     _two_sets = False     # True: input and output coordinate sets differ at every stride (no mirrored backward-data weights)
 
     def __init__(self, in_channels, out_channels, kernel_size=-1, stride=1, dilation=1, bias=False, dimension=3,
-                 expand_coordinates=False):
+                 expand_coordinates=False, kernel_generator=None):
         super().__init__()
         if dimension != 3:
             raise NotImplementedError(f"dimension={dimension}: only 3-D sparse tensors are supported")
-        check_geometry(kernel_size, stride, dilation)
-        self.expand_coordinates = bool(expand_coordinates)
+        # region: None for a cube (a HYPER_CUBE generator included), else the key of a cross or a custom offset list -- such a
+        # layer works between "two sets" at every stride: CoordinateManager.kernel_map(region=), mirror = sub = False
+        kernel_size, stride, dilation, self.region, self.expand_coordinates, K = _layer_geometry(
+            type(self).__name__, kernel_size, stride, dilation, kernel_generator, expand_coordinates)
         self._check_expand(kernel_size, stride, dilation)
         self.in_channels, self.out_channels = in_channels, out_channels
         self.kernel_size, self.stride, self.dilation = kernel_size, stride, dilation
-        K = kernel_size ** 3
         self.kernel_volume = K
-        shape = (in_channels, out_channels) if (kernel_size == 1 and stride == 1) else (K, in_channels, out_channels)
+        shape = (in_channels, out_channels) if (kernel_size == 1 and stride == 1 and self.region is None) \
+            else (K, in_channels, out_channels)
         self.kernel = nn.Parameter(torch.empty(shape, dtype=torch.float32))
         s = 1.0 / math.sqrt(in_channels * K)
         # ME's name and shape, so that state_dict keys carry over; same uniform bound as the kernel
@@ -47,7 +78,11 @@ class _ConvBase(nn.Module):
     def _spec(self, cm, ts):
         """-> (ConvSpec of the forward convolution from tensor stride ts, output tensor stride)"""
         cin, cout = self.in_channels, self.out_channels
-        nbr_fwd, nbr_bwd, vin, vout, K, out_ts, mirror = cm.kernel_map(ts, self.kernel_size, self.stride, self.dilation)
+        nbr_fwd, nbr_bwd, vin, vout, K, out_ts, mirror = cm.kernel_map(ts, self.kernel_size, self.stride, self.dilation,
+                                                                       region=self.region)
+        if self.region is not None:
+            # (sub = False: a custom list of 27 or 8 offsets is neither the 3x3x3 submanifold map nor the k2 map)
+            return Fn.ConvSpec(nbr_fwd, nbr_bwd, vin, vout, K, cin, cout, False, False), out_ts
         # the three maps of the reference's models keep the library's own rule for what a table is (sub = None); the
         # general ones say whether they map a coordinate set onto itself
         old = (self.kernel_size, self.stride, self.dilation) in ((3, 1, 1), (2, 2, 1)) or K == 1
@@ -60,8 +95,8 @@ class _ConvBase(nn.Module):
         """does prepare_conv_weights lay this module's backward-data image out with mirrored offsets: the layers that map a
         coordinate set onto ITSELF (odd kernel, stride 1, one set) -- never a module constructed with expand_coordinates,
         whose output set is another one on every call"""
-        return (self.kernel_size % 2 == 1 and self.kernel_size > 1 and self.stride == 1 and not self._two_sets
-                and not self.expand_coordinates)
+        return (self.region is None and self.kernel_size % 2 == 1 and self.kernel_size > 1 and self.stride == 1
+                and not self._two_sets and not self.expand_coordinates)
 
     def _kernel_two_sets(self):
         """the kernel of a call whose table maps the input set onto ANOTHER set (mirror = False: a target given by
@@ -94,7 +129,7 @@ class _ConvBase(nn.Module):
 
     def extra_repr(self):
         return (f"in={self.in_channels}, out={self.out_channels}, kernel_size={self.kernel_size}, stride={self.stride}, "
-                f"dilation={self.dilation}, bias={self.bias is not None}"
+                f"dilation={self.dilation}, bias={self.bias is not None}" + _region_name(self.region)
                 + (", expand_coordinates=True" if self.expand_coordinates else ""))
 
 
@@ -187,7 +222,11 @@ class MinkowskiConvolution(_ConvBase):
     CoordinateMapKey or a SparseTensor (tensor.target_key) at tensor stride ts * stride: out[o] = bias + sum_k x[o + off_k]
     W[k], off = kernel_offsets(kernel_size, dilation, ts); a row no input reaches is the bias.  A target that names the set
     the layer lands on anyway takes the ordinary path.  expand_coordinates=True (stride 1 only): the output set is every
-    coordinate the kernel reaches, CoordinateManager.expand, on a manager rooted at the tensor stride."""
+    coordinate the kernel reaches, CoordinateManager.expand, on a manager rooted at the tensor stride.
+
+    kernel_generator= (a KernelGenerator): a HYPER_CUBE generator is this layer as its plain arguments build it.  A cross or a
+    custom offset list is a layer between "two sets" on every path, its own set at stride 1 included: forward and inverse
+    tables of CoordinateManager.kernel_map(region=), mirror = sub = False, no residual / skip."""
 
     def _check_expand(self, kernel_size, stride, dilation):
         if self.expand_coordinates and stride != 1:
@@ -200,16 +239,22 @@ class MinkowskiConvolution(_ConvBase):
                              "not both")
         if residual is not None or skip is not None:
             raise ValueError("MinkowskiConvolution: residual / skip (engine extras of the submanifold layers) cannot be "
-                             "combined with " + ("coordinates=" if coordinates is not None else "expand_coordinates=True"))
+                             "combined with " + ("coordinates=" if coordinates is not None else "expand_coordinates=True"
+                                                 if self.expand_coordinates else "a kernel_generator region"))
         cm, ts = x.coordinate_manager, x.tensor_stride
+        if coordinates is None and not self.expand_coordinates:
+            # a cross or a custom list on the layer's own sets: the region's forward and inverse tables, no mirrored image
+            spec, out_ts = self._spec(cm, ts)
+            y, stats = Fn.conv(x._F, self._kernel(), spec, x._pending, want_stats=self.training, bias=self.bias)
+            return x._like(y, tensor_stride=out_ts, stats=stats)
         if coordinates is None:
-            gen = cm.expand(ts, self.kernel_size, self.dilation)
+            gen = cm.expand(ts, self.kernel_size, self.dilation, region=self.region)
             return self._conv_onto(x, gen[0], ts, gen[1:])
         out_ts = ts * self.stride
         key = target_key(coordinates, out_ts, x.device)
         if key.coordinate_manager is cm:
             return self.forward(x)          # the set this layer lands on anyway: its own at stride 1, the cached one at 2
-        table = cm.target_map(ts, key, self.kernel_size, self.stride, self.dilation)
+        table = cm.target_map(ts, key, self.kernel_size, self.stride, self.dilation, region=self.region)
         return self._conv_onto(x, key.coordinate_manager, out_ts, table)
 
     def forward(self, x: SparseTensor, residual: SparseTensor = None, skip=None, *, coordinates=None):
@@ -217,7 +262,7 @@ class MinkowskiConvolution(_ConvBase):
         instead of a separate `+=` pass; `skip` = ("head" | "tail", functional.SkipLink) routes the skip connection's
         gradient through the block's first convolution instead of an elementwise add.  Neither is part of ME's API.
         `coordinates` (keyword only): the set to write onto, see the class."""
-        if coordinates is not None or self.expand_coordinates:
+        if coordinates is not None or self.expand_coordinates or self.region is not None:
             return self._forward_onto(x, residual, skip, coordinates)
         cm, ts = x.coordinate_manager, x.tensor_stride
         cin, cout = self.in_channels, self.out_channels
@@ -280,7 +325,8 @@ class MinkowskiConvolutionTranspose(_ConvBase):
             key = target_key(coordinates, out_ts, x.device)
             if not (key.coordinate_manager is cm and self.stride == 2):
                 return self._conv_onto(x, key.coordinate_manager, out_ts,
-                                       cm.target_map(ts, key, self.kernel_size, self.stride, self.dilation, transposed=True))
+                                       cm.target_map(ts, key, self.kernel_size, self.stride, self.dilation, transposed=True,
+                                                     region=self.region))
             # (the cached finer set of this manager: the ordinary path below)
         if self.stride != 2 or ts % 2 != 0 or (ts // 2) not in cm.coords:
             raise NotImplementedError(f"MinkowskiConvolutionTranspose(kernel_size={self.kernel_size}, stride={self.stride}) on "
@@ -314,7 +360,8 @@ class MinkowskiGenerativeConvolutionTranspose(_ConvBase):
 
     def forward(self, x: SparseTensor):
         cm, ts = x.coordinate_manager, x.tensor_stride
-        out_cm, nbr_fwd, nbr_bwd, vin, vout, K, out_ts = cm.generate(ts, self.kernel_size, self.stride, self.dilation)
+        out_cm, nbr_fwd, nbr_bwd, vin, vout, K, out_ts = cm.generate(ts, self.kernel_size, self.stride, self.dilation,
+                                                                     region=self.region)
         # (sub = False: a K = 27 table between two different sets stays off the submanifold backward-weight route)
         spec = Fn.ConvSpec(nbr_fwd, nbr_bwd, vin, vout, K, self.in_channels, self.out_channels, False, False)
         y, stats = Fn.conv(x._F, self._kernel(), spec, x._pending, want_stats=self.training, bias=self.bias)
@@ -333,14 +380,14 @@ class MinkowskiChannelwiseConvolution(nn.Module):
     Not a _ConvBase: prepare_conv_weights lays out (K, cin, cout) weight images and deferred backward-weight groups for every
     _ConvBase, and a (K, C) kernel has no place in either."""
 
-    def __init__(self, in_channels, kernel_size=-1, stride=1, dilation=1, bias=False, dimension=3):
+    def __init__(self, in_channels, kernel_size=-1, stride=1, dilation=1, bias=False, dimension=3, kernel_generator=None):
         super().__init__()
         if dimension != 3:
             raise NotImplementedError(f"dimension={dimension}: only 3-D sparse tensors are supported")
-        check_geometry(kernel_size, stride, dilation)
+        kernel_size, stride, dilation, self.region, _, K = _layer_geometry(type(self).__name__, kernel_size, stride, dilation,
+                                                                          kernel_generator)
         self.in_channels = self.out_channels = in_channels
         self.kernel_size, self.stride, self.dilation = kernel_size, stride, dilation
-        K = kernel_size ** 3
         self.kernel_volume = K
         self.kernel = nn.Parameter(torch.empty((K, in_channels), dtype=torch.float32))
         self.bias = nn.Parameter(torch.empty((1, in_channels), dtype=torch.float32)) if bias else None
@@ -358,21 +405,21 @@ class MinkowskiChannelwiseConvolution(nn.Module):
         if coordinates is not None:
             key = target_key(coordinates, ts * self.stride, x.device)
             if key.coordinate_manager is not cm:
-                nbr_fwd, nbr_inv, vin, vout, K = cm.target_map(ts, key, *geom)
+                nbr_fwd, nbr_inv, vin, vout, K = cm.target_map(ts, key, *geom, region=self.region)
                 if vout == 0:
                     y = x._raw()[:0] * self.kernel[:1]
                     y = y if self.bias is None else y + self.bias
                 else:
                     y = Fn.channelwise_conv(x._raw(), self.kernel, self.bias, nbr_fwd, nbr_inv, vin, vout, K)
                 return SparseTensor(y, coordinate_manager=key.coordinate_manager, tensor_stride=key.tensor_stride)
-        nbr_fwd, _, vin, vout, K, out_ts, _ = cm.kernel_map(ts, *geom)
-        nbr_inv = cm.kernel_map_inverse(ts, *geom)
+        nbr_fwd, _, vin, vout, K, out_ts, _ = cm.kernel_map(ts, *geom, region=self.region)
+        nbr_inv = cm.kernel_map_inverse(ts, *geom, region=self.region)
         y = Fn.channelwise_conv(x._raw(), self.kernel, self.bias, nbr_fwd, nbr_inv, vin, vout, K)
         return x._like(y, tensor_stride=out_ts)
 
     def extra_repr(self):
         return (f"in={self.in_channels}, kernel_size={self.kernel_size}, stride={self.stride}, dilation={self.dilation}, "
-                f"bias={self.bias is not None}")
+                f"bias={self.bias is not None}" + _region_name(self.region))
 
 
 class MinkowskiPruning(nn.Module):
@@ -528,11 +575,12 @@ class _PoolBase(nn.Module):
     is materialised first."""
     MODE = None
 
-    def __init__(self, kernel_size, stride=1, dilation=1, dimension=3):
+    def __init__(self, kernel_size, stride=1, dilation=1, dimension=3, kernel_generator=None):
         super().__init__()
         if dimension != 3:
             raise NotImplementedError(f"dimension={dimension}: only 3-D sparse tensors are supported")
-        check_geometry(kernel_size, stride, dilation)
+        kernel_size, stride, dilation, self.region, _, self.kernel_volume = _layer_geometry(
+            type(self).__name__, kernel_size, stride, dilation, kernel_generator)
         self.kernel_size, self.stride, self.dilation = kernel_size, stride, dilation
 
     def forward(self, x: SparseTensor, coordinates=None):
@@ -542,15 +590,15 @@ class _PoolBase(nn.Module):
         if coordinates is not None:
             key = target_key(coordinates, ts * self.stride, x.device)
             if key.coordinate_manager is not cm:
-                table = cm.target_map(ts, key, self.kernel_size, self.stride, self.dilation)
+                table = cm.target_map(ts, key, self.kernel_size, self.stride, self.dilation, region=self.region)
                 return _pool_onto(x, key, table, self.MODE)
-        nbr_fwd, _, vin, vout, K, out_ts, _ = cm.kernel_map(ts, self.kernel_size, self.stride, self.dilation)
-        nbr_inv = cm.kernel_map_inverse(ts, self.kernel_size, self.stride, self.dilation)
+        nbr_fwd, _, vin, vout, K, out_ts, _ = cm.kernel_map(ts, self.kernel_size, self.stride, self.dilation, region=self.region)
+        nbr_inv = cm.kernel_map_inverse(ts, self.kernel_size, self.stride, self.dilation, region=self.region)
         y = Fn.sparse_pool(x._raw(), nbr_fwd, nbr_inv, vin, vout, K, self.MODE)
         return x._like(y, tensor_stride=out_ts)
 
     def extra_repr(self):
-        return f"kernel_size={self.kernel_size}, stride={self.stride}, dilation={self.dilation}"
+        return f"kernel_size={self.kernel_size}, stride={self.stride}, dilation={self.dilation}" + _region_name(self.region)
 
 
 class MinkowskiMaxPooling(_PoolBase):
@@ -575,13 +623,13 @@ class MinkowskiPoolingTranspose(nn.Module):
     uncached target raises NotImplementedError), stride 1 (odd kernels) stays on the set.  Sum pooling (csrc/pool.hip) over
     the transposed table forward, through the forward table backward.  Strides other than 1 and 2 are not supported."""
 
-    def __init__(self, kernel_size, stride, dilation=1, dimension=3, expand_coordinates=False):
+    def __init__(self, kernel_size, stride, dilation=1, dimension=3, expand_coordinates=False, kernel_generator=None):
         super().__init__()
         if dimension != 3:
             raise NotImplementedError(f"dimension={dimension}: only 3-D sparse tensors are supported")
-        check_geometry(kernel_size, stride, dilation)
+        kernel_size, stride, dilation, self.region, self.expand_coordinates, self.kernel_volume = _layer_geometry(
+            type(self).__name__, kernel_size, stride, dilation, kernel_generator, expand_coordinates)
         self.kernel_size, self.stride, self.dilation = kernel_size, stride, dilation
-        self.expand_coordinates = bool(expand_coordinates)
 
     def forward(self, x: SparseTensor, coordinates=None):
         """coordinates: the set to write onto (an integer tensor [M, 4], a CoordinateMapKey or a SparseTensor at tensor stride
@@ -595,29 +643,32 @@ class MinkowskiPoolingTranspose(nn.Module):
                 raise ValueError("MinkowskiPoolingTranspose: expand_coordinates=True derives the output set, coordinates= names "
                                  "it: not both")
             if coordinates is None:
-                out_cm, nbr_fwd, nbr_bwd, vin, vout, K, out_ts = cm.generate(ts, *geom)
+                out_cm, nbr_fwd, nbr_bwd, vin, vout, K, out_ts = cm.generate(ts, *geom, region=self.region)
                 return _pool_onto(x, CoordinateMapKey(out_cm, out_ts), (nbr_fwd, nbr_bwd, vin, vout, K), 2)
             key = target_key(coordinates, _transposed_stride(self, ts), x.device)
             if key.coordinate_manager is not cm:
-                return _pool_onto(x, key, cm.target_map(ts, key, *geom, transposed=True), 2)
+                return _pool_onto(x, key, cm.target_map(ts, key, *geom, transposed=True, region=self.region), 2)
             # (a set of this manager: its own at stride 1, the cached finer one at stride 2 -- the ordinary paths below)
         if self.stride == 1:
             # the transpose of a submanifold table is its mirror image, and a sum does not care about the offset order
-            nbr, _, vin, vout, K, _, _ = cm.kernel_map(ts, *geom)
-            y = Fn.sparse_pool(x._raw(), nbr, cm.kernel_map_inverse(ts, *geom), vin, vout, K, 2)
+            nbr, _, vin, vout, K, _, _ = cm.kernel_map(ts, *geom, region=self.region)
+            inv = cm.kernel_map_inverse(ts, *geom, region=self.region)
+            if self.region is not None:
+                nbr, inv = inv, nbr        # out[o] = sum_k in[o - off_k]: the inverse table forward (a region has no mirror rule)
+            y = Fn.sparse_pool(x._raw(), nbr, inv, vin, vout, K, 2)
             return x._like(y)
         if ts % 2 != 0 or (ts // 2) not in cm.coords:
             raise NotImplementedError(f"MinkowskiPoolingTranspose(kernel_size={self.kernel_size}, stride={self.stride}) on "
                                       f"tensor stride {ts}: only onto a cached finer coordinate set; generating new "
                                       "coordinates is not supported")
         fine = ts // 2
-        down, _, v_fine, v_coarse, K, _, _ = cm.kernel_map(fine, *geom)       # the strided map fine -> ts
-        up = cm.kernel_map_inverse(fine, *geom)                               # [K, v_fine]: the coarse row a fine row feeds
+        down, _, v_fine, v_coarse, K, _, _ = cm.kernel_map(fine, *geom, region=self.region)    # the strided map fine -> ts
+        up = cm.kernel_map_inverse(fine, *geom, region=self.region)           # [K, v_fine]: the coarse row a fine row feeds
         y = Fn.sparse_pool(x._raw(), up, down, v_coarse, v_fine, K, 2)
         return x._like(y, tensor_stride=fine)
 
     def extra_repr(self):
-        return (f"kernel_size={self.kernel_size}, stride={self.stride}, dilation={self.dilation}"
+        return (f"kernel_size={self.kernel_size}, stride={self.stride}, dilation={self.dilation}" + _region_name(self.region)
                 + (", expand_coordinates=True" if self.expand_coordinates else ""))
 
 

@@ -43,6 +43,134 @@ def check_geometry(kernel_size, stride, dilation):
         raise NotImplementedError(f"{geom}: at most 254 kernel offsets (kernel_size <= 6)")
 
 
+class RegionType(enum.Enum):
+    """the shape of a kernel: every cell of the cube, the axes through its centre, or a list the caller writes"""
+    HYPER_CUBE = 0
+    HYPER_CROSS = 1
+    CUSTOM = 2
+
+
+def region_offsets(region, tensor_stride=1):
+    """int32 [K, 3] (x, y, z) offsets in voxel units, in weight order, of a region key (KernelGenerator.region_key):
+    ("HYPER_CROSS", kernel_size, dilation): the centre first, then axis x at -h .. -1, +1 .. +h, then y, then z (h =
+    (kernel_size - 1) // 2, K = 6 h + 1), each times dilation * tensor_stride; ("CUSTOM", rows): the rows in the order given,
+    times tensor_stride."""
+    if region[0] == "CUSTOM":
+        return (np.asarray(region[1], dtype=np.int64).reshape(-1, 3) * int(tensor_stride)).astype(np.int32)
+    _, kernel_size, dilation = region
+    h = (kernel_size - 1) // 2
+    steps = [s for s in range(-h, h + 1) if s != 0]
+    rows = [(0, 0, 0)]
+    for axis in range(3):
+        rows += [tuple(s if a == axis else 0 for a in range(3)) for s in steps]
+    return (np.asarray(rows, dtype=np.int64).reshape(-1, 3) * (int(dilation) * int(tensor_stride))).astype(np.int32)
+
+
+def _region_key(region):
+    """a layer's `region` argument (None, a KernelGenerator or a region key) -> None for a cube, else the hashable key"""
+    if isinstance(region, KernelGenerator):
+        return region.region_key
+    return region
+
+
+class KernelGenerator:
+    """MinkowskiEngine's kernel generator: the geometry of a convolution or pooling layer as one object, handed to the layers
+    as `kernel_generator=`.  Attributes: kernel_size, stride, dilation (plain ints), region_type, region_offsets (int32 CPU
+    tensor [K, 3] for CUSTOM, else None), kernel_volume, expand_coordinates, is_transpose, dimension (3).  Hashable by value.
+    `offsets(tensor_stride)` -> np.int32 [K, 3] in voxel units, in weight order (an engine extra):
+
+      HYPER_CUBE   kernel_offsets(kernel_size, dilation, ts); K = kernel_size ** 3.  The plain layer: a layer handed such a
+                   generator is the layer its plain arguments build.
+      HYPER_CROSS  odd kernel sizes; see region_offsets.  Kernel size 1 is the cube of size 1.
+      CUSTOM       region_offsets: an integer tensor or array [K, 3], 1 <= K <= 254, distinct rows (ValueError), used in the
+                   order given and multiplied by the tensor stride only: dilation must be 1 (ValueError), kernel_size is
+                   ignored.
+
+    Refused at construction: axis_types, dimension other than -1 / 3, per-axis tuples, strides other than 1 and 2, more than
+    254 offsets (NotImplementedError); an even cross (ValueError).  These rules are chosen here, MinkowskiEngine's as
+    recalled, not pinned (see the package docstring)."""
+
+    def __init__(self, kernel_size=-1, stride=1, dilation=1, is_transpose=False, region_type=RegionType.HYPER_CUBE,
+                 region_offsets=None, expand_coordinates=False, axis_types=None, dimension=-1):
+        if axis_types is not None:
+            raise NotImplementedError(f"axis_types={axis_types!r}: per-axis region types are not supported")
+        if isinstance(dimension, bool) or dimension not in (-1, 3):
+            raise NotImplementedError(f"dimension={dimension}: only 3-D sparse tensors are supported")
+        if not isinstance(region_type, RegionType):
+            raise TypeError(f"region_type: a RegionType, got {region_type!r}")
+        geom = f"kernel_size={kernel_size}, stride={stride}, dilation={dilation}"
+        offs = None
+        if region_type is RegionType.HYPER_CUBE:
+            check_geometry(kernel_size, stride, dilation)
+            K = kernel_size ** 3
+        else:
+            sized = (stride, dilation) if region_type is RegionType.CUSTOM else (kernel_size, stride, dilation)
+            if not all(isinstance(v, int) for v in sized) or min(sized) < 1:
+                raise NotImplementedError(f"{geom}: one positive integer per argument (no per-axis tuples)")
+            if stride not in (1, 2):
+                raise NotImplementedError(f"{geom}: strides other than 1 and 2 are not supported")
+            if region_type is RegionType.HYPER_CROSS:
+                if kernel_size % 2 == 0:
+                    raise ValueError(f"{geom}: a HYPER_CROSS region needs an odd kernel size")
+                K = 3 * (kernel_size - 1) + 1
+            else:
+                if region_offsets is None:
+                    raise ValueError("region_type=CUSTOM needs region_offsets: an integer tensor or array [K, 3]")
+                if dilation != 1:
+                    raise ValueError(f"{geom}: a CUSTOM region carries its offsets as written; dilation must be 1")
+                offs = region_offsets.detach().cpu().numpy() if torch.is_tensor(region_offsets) else np.asarray(region_offsets)
+                if offs.ndim != 2 or offs.shape[1] != 3 or offs.shape[0] < 1 or offs.dtype.kind not in "iu":
+                    raise ValueError(f"region_offsets: an integer tensor or array [K, 3] with K >= 1, got "
+                                     f"{list(offs.shape)} {offs.dtype}")
+                K = offs.shape[0]
+                if not isinstance(kernel_size, int):
+                    kernel_size = -1
+            if K > 254:
+                raise NotImplementedError(f"{geom}: a region of {K} offsets: at most 254 kernel offsets")
+            if offs is not None:
+                offs = np.ascontiguousarray(offs.astype(np.int32))
+                if len({tuple(r) for r in offs.tolist()}) != K:
+                    raise ValueError("region_offsets: the rows must be distinct (an offset occurs twice)")
+        if region_offsets is not None and region_type is not RegionType.CUSTOM:
+            raise ValueError(f"region_offsets needs region_type=RegionType.CUSTOM, got {region_type}")
+        self.kernel_size, self.stride, self.dilation = kernel_size, stride, dilation
+        self.is_transpose, self.expand_coordinates = bool(is_transpose), bool(expand_coordinates)
+        self.region_type, self.dimension, self.axis_types = region_type, 3, None
+        self.region_offsets = None if offs is None else torch.from_numpy(offs.copy())
+        self.kernel_volume = K
+        if region_type is RegionType.HYPER_CUBE or (region_type is RegionType.HYPER_CROSS and kernel_size == 1):
+            self.region_key = None                      # a cube: the layers and the coordinate manager never see a region
+        elif region_type is RegionType.HYPER_CROSS:
+            self.region_key = ("HYPER_CROSS", kernel_size, dilation)
+        else:
+            self.region_key = ("CUSTOM", tuple(tuple(r) for r in offs.tolist()))
+
+    def offsets(self, tensor_stride=1):
+        """np.int32 [kernel_volume, 3]: the offsets in voxel units at that tensor stride, in weight order"""
+        if self.region_key is None:
+            return kernel_offsets(self.kernel_size, self.dilation, tensor_stride)
+        return region_offsets(self.region_key, tensor_stride)
+
+    def _value(self):
+        return (self.region_type, self.kernel_size, self.stride, self.dilation, self.is_transpose, self.expand_coordinates,
+                self.region_key)
+
+    def __eq__(self, other):
+        return isinstance(other, KernelGenerator) and other._value() == self._value()
+
+    def __ne__(self, other):
+        return not self == other
+
+    def __hash__(self):
+        return hash(self._value())
+
+    def __repr__(self):
+        return (f"KernelGenerator(kernel_size={self.kernel_size}, stride={self.stride}, dilation={self.dilation}, "
+                f"region_type={self.region_type}, kernel_volume={self.kernel_volume}"
+                + (", is_transpose=True" if self.is_transpose else "")
+                + (", expand_coordinates=True" if self.expand_coordinates else "") + ")")
+
+
 class CoordinateMapKey:
     """The name of ONE coordinate set: a coordinate manager plus a tensor stride -- the pair `+`, `cat`, `slice` and `union`
     compare already.  Hashable; two keys are equal when the manager is the same object and the stride is equal.  What
@@ -130,6 +258,21 @@ def target_key(coordinates, out_ts, device):
     return CoordinateMapKey(hit[0], out_ts)
 
 
+def _check_region_geometry(kernel_size, stride, dilation, region):
+    """check_geometry for a cube; a region (validated when its KernelGenerator was built) only has its stride checked"""
+    if region is None:
+        check_geometry(kernel_size, stride, dilation)
+    elif stride not in (1, 2):
+        raise NotImplementedError(f"region={region}, stride={stride}: strides other than 1 and 2 are not supported")
+
+
+def _offsets_of(kernel_size, dilation, tensor_stride, region):
+    """the offset list of a layer: kernel_offsets of a cube, region_offsets of a region key"""
+    if region is None:
+        return kernel_offsets(kernel_size, dilation, tensor_stride)
+    return region_offsets(region, tensor_stride)
+
+
 class CoordinateManager:
     """coordinates per tensor stride and kernel maps per (stride, kind), built once and shared by every
     convolution of a level and by the backward pass (ME's coordinate manager does the same caching)."""
@@ -169,26 +312,27 @@ class CoordinateManager:
         cm._k3, cm._k2, cm._ident, cm._kmaps, cm._kinv, cm._batch_rows = {}, {}, {}, {}, {}, {}
         return cm
 
-    def generate(self, ts, kernel_size, stride=1, dilation=1):
+    def generate(self, ts, kernel_size, stride=1, dilation=1, region=None):
         """what a generative transposed convolution from tensor stride ts needs -> (manager rooted at ts // stride on the
         generated set, nbr_fwd [K, Vout], nbr_bwd [K, Vin], Vin, Vout, K, output tensor stride); built once per (ts, kernel
         size, stride, dilation), so two layers of one geometry on one input share the output manager.  The set is every
         c + offsets[k] over the input rows c and kernel_offsets(kernel_size, dilation, ts // stride), in first-occurrence
-        order (backend.coords_expand); nbr_fwd[k][o] = input row at out[o] - offsets[k], nbr_bwd its inverse."""
-        kernel_size, stride, dilation = int(kernel_size), int(stride), int(dilation)
-        check_geometry(kernel_size, stride, dilation)
-        geom = f"kernel_size={kernel_size}, stride={stride}, dilation={dilation}"
+        order (backend.coords_expand); nbr_fwd[k][o] = input row at out[o] - offsets[k], nbr_bwd its inverse.  region (a
+        non-cube KernelGenerator or its key): its offsets at ts // stride instead, part of the cache key."""
+        kernel_size, stride, dilation, region = int(kernel_size), int(stride), int(dilation), _region_key(region)
+        _check_region_geometry(kernel_size, stride, dilation, region)
+        geom = f"kernel_size={kernel_size}, stride={stride}, dilation={dilation}" + (f", region={region}" if region else "")
         if ts % stride != 0:
             raise NotImplementedError(f"{geom} on tensor stride {ts}: a generative stride-2 layer needs an even tensor stride")
         cache = self.__dict__.setdefault("_generated", {})
-        key = (ts, kernel_size, stride, dilation)
+        key = (ts, kernel_size, stride, dilation) if region is None else (ts, stride, region)
         gen = cache.get(key)
         if gen is None:
             be = get_backend()
             if not (hasattr(be, "coords_expand") and hasattr(be, "kmap_general")):
                 raise NotImplementedError(f"{geom}: generating coordinates needs the HIP backend (ms3d_coords_expand)")
             out_ts = ts // stride
-            offsets = kernel_offsets(kernel_size, dilation, out_ts)
+            offsets = _offsets_of(kernel_size, dilation, out_ts, region)
             cin = self.coords[ts]
             vin, K = cin.size(0), offsets.shape[0]
             # first occurrence counts in the order of the rows the CALLER sees (x.coordinates): on a Morton-sorted manager
@@ -212,7 +356,7 @@ class CoordinateManager:
             raise ValueError(f"get_coordinates: this manager holds no coordinate set of tensor stride {key}")
         return self.visible_coords(key)
 
-    def target_map(self, ts, key, kernel_size, stride=1, dilation=1, transposed=False):
+    def target_map(self, ts, key, kernel_size, stride=1, dilation=1, transposed=False, region=None):
         """the kernel map of a layer from this manager's set of tensor stride ts ONTO the set `key` names (any manager) ->
         (nbr_fwd [K, Vout], nbr_bwd [K, Vin], Vin, Vout, K).  Both sets are taken as their managers HOLD them (a Morton-sorted
         stride-1 set through coords[1], not coords_external), like every table.  Forward layers (convolution, pooling,
@@ -220,18 +364,21 @@ class CoordinateManager:
         (transposed convolution, pooling transpose): nbr_fwd[k][o] = input row at target[o] - kernel_offsets(kernel_size,
         dilation, key's stride)[k] -- y[o] = sum_k x[o - off_k] W[k], the rule of generate().  nbr_bwd is the inverse table
         (the target's rows are distinct).  A target row no input reaches is a column of -1.  Built once per (ts, key, geometry,
-        direction) and kept on this manager with the key (the sixteen newest)."""
-        kernel_size, stride, dilation = int(kernel_size), int(stride), int(dilation)
+        direction) and kept on this manager with the key (the sixteen newest).  region (a non-cube KernelGenerator or its
+        key): its offsets at the same tensor stride and with the same sign, part of the cache key."""
+        kernel_size, stride, dilation, region = int(kernel_size), int(stride), int(dilation), _region_key(region)
         cache = self.__dict__.setdefault("_target_maps", {})
         ident = (ts, key, kernel_size, stride, dilation, bool(transposed))
+        if region is not None:
+            ident = (ts, key, stride, region, bool(transposed))
         hit = cache.get(ident)
         if hit is None:
-            check_geometry(kernel_size, stride, dilation)
+            _check_region_geometry(kernel_size, stride, dilation, region)
             be = get_backend()
             if not (hasattr(be, "kmap_general") and hasattr(be, "kmap_invert")):
                 raise NotImplementedError("a layer onto given coordinates needs the HIP backend (ms3d_kmap_general)")
             out_ts = key.tensor_stride
-            offsets = kernel_offsets(kernel_size, dilation, out_ts if transposed else ts)
+            offsets = _offsets_of(kernel_size, dilation, out_ts if transposed else ts, region)
             if transposed:
                 offsets = -offsets
             cin, out = self.coords[ts], key.coordinate_manager.coords[out_ts]
@@ -242,24 +389,26 @@ class CoordinateManager:
                 cache.pop(next(iter(cache)))
         return hit
 
-    def expand(self, ts, kernel_size, dilation=1):
+    def expand(self, ts, kernel_size, dilation=1, region=None):
         """what a stride-1 convolution with expand_coordinates=True needs -> (manager rooted at ts on every coordinate the
         kernel reaches, nbr_fwd [K, Vout], nbr_bwd [K, Vin], Vin, Vout, K): the set is every c - kernel_offsets(kernel_size,
         dilation, ts)[k] over the rows c the CALLER sees, in first-occurrence order (backend.coords_expand, as generate()), the
-        tables are target_map's.  Built once per (ts, kernel size, dilation)."""
-        kernel_size, dilation = int(kernel_size), int(dilation)
-        check_geometry(kernel_size, 1, dilation)
+        tables are target_map's.  Built once per (ts, kernel size, dilation); region (a non-cube KernelGenerator or its key):
+        its offsets instead, part of the cache key."""
+        kernel_size, dilation, region = int(kernel_size), int(dilation), _region_key(region)
+        _check_region_geometry(kernel_size, 1, dilation, region)
         cache = self.__dict__.setdefault("_expanded", {})
-        ident = (ts, kernel_size, dilation)
+        ident = (ts, kernel_size, dilation) if region is None else (ts, region)
         hit = cache.get(ident)
         if hit is None:
             be = get_backend()
             if not (hasattr(be, "coords_expand") and hasattr(be, "kmap_general")):
                 raise NotImplementedError(f"kernel_size={kernel_size}, dilation={dilation}: expand_coordinates needs the HIP "
                                           "backend (ms3d_coords_expand)")
-            out = be.coords_expand(self.visible_coords(ts), torch.from_numpy(-kernel_offsets(kernel_size, dilation, ts)))
+            out = be.coords_expand(self.visible_coords(ts), torch.from_numpy(-_offsets_of(kernel_size, dilation, ts, region)))
             out_cm = CoordinateManager.rooted(out, ts)
-            hit = cache[ident] = (out_cm,) + self.target_map(ts, CoordinateMapKey(out_cm, ts), kernel_size, 1, dilation)
+            hit = cache[ident] = (out_cm,) + self.target_map(ts, CoordinateMapKey(out_cm, ts), kernel_size, 1, dilation,
+                                                             region=region)
         return hit
 
     def visible_coords(self, ts):
@@ -373,14 +522,20 @@ class CoordinateManager:
             return torch.where(rows >= 0, self.perm[rows.clamp(min=0).long()], rows.long()).to(torch.int32)
         return rows
 
-    def kernel_map(self, ts, kernel_size, stride=1, dilation=1):
+    def kernel_map(self, ts, kernel_size, stride=1, dilation=1, region=None):
         """-> (nbr_fwd [K, Vout], nbr_bwd [K, Vin], Vin, Vout, K, output tensor stride, mirror) for a layer from the
         coordinate set of tensor stride ts; built once per key.  (3, 1, 1), (2, 2, 1) and (1, 1, *) are the tables of
         k3() / k2() / identity().  Stride 1 (odd kernel sizes only): the output set is the input set, the table is its own
         transpose up to k <-> K-1-k (nbr_bwd = nbr_fwd, mirror = True).  Stride 2: the output set is the stride-2 set of
         k2() whatever the kernel size, nbr_bwd is the inverse table, mirror = False.  Other strides: NotImplementedError.
-        Offsets: kernel_offsets()."""
-        kernel_size, stride, dilation = int(kernel_size), int(stride), int(dilation)
+        Offsets: kernel_offsets().
+        region (a non-cube KernelGenerator or its key; kernel_size and dilation are then the region's own): the offsets are
+        region_offsets(region, ts) and the layer works between "two sets" even at stride 1 on its own set -> (nbr_fwd [K, Vout],
+        nbr_bwd = the inverse table [K, Vin], Vin, Vout, K, output tensor stride, False).  Stride 1: both tables from one pass
+        of backend.kmap_region (ms3d_kmap_region); stride 2: onto the stride-2 set of k2(), kmap_general + kmap_invert."""
+        kernel_size, stride, dilation, region = int(kernel_size), int(stride), int(dilation), _region_key(region)
+        if region is not None:
+            return self._region_map(ts, stride, region)
         if kernel_size == 1 and stride == 1:
             ident, V = self.identity(ts), self.size(ts)
             return ident, ident, V, V, 1, ts, False
@@ -412,11 +567,35 @@ class CoordinateManager:
             self._kmaps[key] = km
         return km
 
-    def kernel_map_inverse(self, ts, kernel_size, stride=1, dilation=1):
+    def _region_map(self, ts, stride, region):
+        key = (ts, stride, region)
+        km = self._kmaps.get(key)
+        if km is None:
+            _check_region_geometry(0, stride, 0, region)
+            be = get_backend()
+            offsets = region_offsets(region, ts)
+            K, vin = offsets.shape[0], self.size(ts)
+            if stride == 1:
+                if not hasattr(be, "kmap_region"):
+                    raise NotImplementedError(f"region={region} at stride 1 needs the HIP backend (ms3d_kmap_region)")
+                nbr, inv = be.kmap_region(self.coords[ts], offsets)
+                km = (nbr, inv, vin, vin, K, ts, False)
+            else:
+                if not (hasattr(be, "kmap_general") and hasattr(be, "kmap_invert")):
+                    raise NotImplementedError(f"region={region} at stride 2 needs the HIP backend (ms3d_kmap_general)")
+                self.k2(ts)                    # makes the stride-2 coordinate set (every strided layer lands on it)
+                out = self.coords[2 * ts]
+                vout = out.size(0)
+                nbr = be.kmap_general(self.coords[ts], out, torch.from_numpy(offsets))
+                km = (nbr, be.kmap_invert(nbr, K, vout, vin), vin, vout, K, 2 * ts, False)
+            self._kmaps[key] = km
+        return km
+
+    def kernel_map_inverse(self, ts, kernel_size, stride=1, dilation=1, region=None):
         """[K, Vin] table that names, per offset, the OUTPUT row an input row feeds (what a backward gather of a pooling
         layer walks): nbr_bwd of a strided map; for a submanifold map -- whose nbr_bwd is the forward table, to be read
         with mirrored offsets -- the inverse is built (and kept) here"""
-        nbr_fwd, nbr_bwd, vin, vout, K, _, mirror = self.kernel_map(ts, kernel_size, stride, dilation)
+        nbr_fwd, nbr_bwd, vin, vout, K, _, mirror = self.kernel_map(ts, kernel_size, stride, dilation, region=region)
         if not mirror and nbr_bwd is not nbr_fwd:
             return nbr_bwd
         key = (ts, int(kernel_size), int(stride), int(dilation))

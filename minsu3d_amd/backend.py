@@ -874,6 +874,37 @@ class _HipEngine:
                    "ms3d_kmap_invert")
         return inv
 
+    def kmap_region(self, coords, offsets):
+        """(nbr_fwd [K, V], nbr_inv [K, V]) of a coordinate set onto itself over an arbitrary offset list (ms3d_kmap_region):
+        nbr_fwd = kmap_general(coords, coords, offsets), nbr_inv = kmap_invert of it, from one pass.  offsets: int32 [K, 3]
+        numpy array in voxel units, distinct rows, 1 <= K <= 254; the partner list (index of -offsets[k], -1 for none) is
+        derived here from the array that is uploaded."""
+        coords = self._dev(coords)
+        V, dev = coords.size(0), coords.device
+        off = np.ascontiguousarray(np.asarray(offsets, dtype=np.int32))
+        assert off.ndim == 2 and off.shape[1] == 3 and off.shape[0] >= 1
+        K = off.shape[0]
+        # (a list is the same every step: its device copy and its partner list are kept, the sixteen newest)
+        cache = self.__dict__.setdefault("_region_lists", {})
+        ident = (off.tobytes(), str(dev))
+        hit = cache.get(ident)
+        if hit is None:
+            rows = off.tolist()
+            index = {tuple(o): k for k, o in enumerate(rows)}
+            partner = (C.c_int * K)(*[index.get((-o[0], -o[1], -o[2]), -1) for o in rows])
+            hit = cache[ident] = (torch.from_numpy(off.copy()).to(dev), partner)
+            while len(cache) > 16:
+                cache.pop(next(iter(cache)))
+        d_off, partner = hit
+        both = torch.empty((2, K, max(V, 1)), dtype=torch.int32, device=dev)       # one allocation: one fill in the library
+        fwd, inv = both[0], both[1]
+        if V <= 0:
+            both.fill_(-1)
+        ws = self._cws(V, dev)
+        _lib.check(self.lib.ms3d_kmap_region(_lib.ptr(coords), V, _lib.ptr(d_off), partner, K, _lib.ptr(fwd), _lib.ptr(inv),
+                                             _lib.ptr(ws), C.c_size_t(ws.numel()), _lib.stream_handle()), "ms3d_kmap_region")
+        return fwd, inv
+
     # ---- coordinate sets that are generated or pruned
     def coords_expand(self, in_coords, offsets):
         """-> int32 [n, 4]: the distinct (b, xyz + offsets[k]) over all rows of in_coords and all offsets, in first-occurrence

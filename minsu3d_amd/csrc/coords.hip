@@ -12,6 +12,8 @@
 //       k2 s2 : down[k][p] = child of coarse row p at offset k;  up[k][f] = (k == koff[f]) ? parent[f] : -1
 //       general: nbr[k][o] = row at c_o + offsets[k] for any offset list (any kernel size, stride, dilation), and the
 //               inverse table nbr_inv[k][i] = o of a map that is not its own mirror image
+//       region: a set onto itself over any offset list (a cross, a hand-written list), table and inverse from one pass:
+//               one lookup per pair of opposite offsets, four stores (kmap_region_kernel)
 #include <algorithm>
 #include <mutex>
 #include <unordered_map>
@@ -245,6 +247,65 @@ __global__ void kmap_invert_kernel(const int *__restrict__ nbr, int Vout, int Vi
     if (o >= Vout) return;
     const int i = nbr[(size_t)k * Vout + o];
     if (i >= 0 && i < Vin) nbr_inv[(size_t)k * Vin + i] = o;
+}
+// Region map (ms3d_kmap_region): a coordinate set onto ITSELF over any offset list, forward table and inverse from one pass.
+// partner.p[k] = index of -offsets[k] in the list (k itself for the zero offset, REGION_NO_PARTNER when the list lacks it),
+// handed over by value.  One thread per (offset, row); both tables were pre-filled with -1 and only hits are stored.
+//   j = nbr_fwd[k][i] over distinct rows  <=>  nbr_fwd[p][j] = i, nbr_inv[k][j] = i, nbr_inv[p][i] = j   (p = partner of k)
+// so of a partnered pair only the lower index k is looked up and the thread stores all four entries; the blocks of the higher
+// index leave at once.  An offset without a partner (or its own partner) is one lookup plus the scatter into nbr_inv.
+// Rows that repeat: the table names the FIRST row of a coordinate, so only a row the table names for its own key writes
+// mirrored entries and entries of nbr_inv -- each such entry then has exactly one writer (the first row at the other end
+// of the offset) -- and any other row looks both offsets of the pair up itself and writes its own column of nbr_fwd alone,
+// which nobody mirrors into.  nbr_fwd is therefore kmap_general_kernel's table for any input.  A set with a row outside the
+// packable range (range_flag, raised by table_insert_kernel: such a row aliases another key) is walked without mirroring at
+// all: every (offset, row) does its own lookup.
+constexpr int REGION_NO_PARTNER = 255;
+struct RegionPartner {
+    unsigned char p[256];
+};
+__device__ __forceinline__ int region_lookup(const int4 c, const int *__restrict__ offsets, int k,
+                                             const unsigned long long *__restrict__ keys, const int *__restrict__ vals,
+                                             unsigned mask)
+{
+    const int x = c.y + offsets[3 * k], y = c.z + offsets[3 * k + 1], z = c.w + offsets[3 * k + 2];
+    if (!(in_range(x) && in_range(y) && in_range(z))) return -1;
+    return table_lookup(keys, vals, mask, pack_key(c.x, x, y, z));
+}
+__global__ __launch_bounds__(256) void kmap_region_kernel(const int *__restrict__ coords, int V, const int *__restrict__ offsets,
+                                                          int K, const RegionPartner partner,
+                                                          const unsigned long long *__restrict__ keys,
+                                                          const int *__restrict__ vals, unsigned mask,
+                                                          const int *__restrict__ slot_of_row,
+                                                          const int *__restrict__ range_flag, int *__restrict__ nbr_fwd,
+                                                          int *__restrict__ nbr_inv)
+{
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    const int k = blockIdx.y;
+    if (i >= V || k >= K) return;
+    const int p = partner.p[k];
+    const bool pair = *range_flag == 0 && p != REGION_NO_PARTNER && p != k;
+    if (pair && p < k) return;
+    const int4 c = reinterpret_cast<const int4 *>(coords)[i];
+    if (!(in_range(c.y) && in_range(c.z) && in_range(c.w) && c.x >= 0 && c.x <= 0x7FFFF)) return;
+    const int own = vals[slot_of_row[i]];          // the row the table names for this row's key: no probe
+    const bool first = own == i;
+    const bool zero = (offsets[3 * k] | offsets[3 * k + 1] | offsets[3 * k + 2]) == 0;
+    const int r = zero ? own : region_lookup(c, offsets, k, keys, vals, mask);
+    if (r >= 0) {
+        nbr_fwd[(size_t)k * V + i] = r;
+        if (first) nbr_inv[(size_t)k * V + r] = i;
+    }
+    if (!pair) return;
+    if (first) {
+        if (r >= 0) {
+            nbr_fwd[(size_t)p * V + r] = i;
+            nbr_inv[(size_t)p * V + i] = r;
+        }
+    } else {
+        const int r2 = region_lookup(c, offsets, p, keys, vals, mask);
+        if (r2 >= 0) nbr_fwd[(size_t)p * V + i] = r2;
+    }
 }
 __global__ void kmap_k2_kernel(const int *__restrict__ parent, const int *__restrict__ koff, int Vf, int Vc,
                                int *__restrict__ nbr_down, int *__restrict__ nbr_up)
@@ -811,6 +872,42 @@ int ms3d_kmap_general(const int *in_coords, int Vin, const int *out_coords, int 
     if (rc) return rc;
     dim3 grid(ms3d_divup(Vout, 256), K);
     kmap_general_kernel<<<grid, 256, 0, stream>>>(out_coords, Vout, offsets, K, w.keys, w.vals, (unsigned)w.H - 1u, nbr);
+    MS3D_LAUNCH_CHECK();
+    return 0;
+}
+
+int ms3d_kmap_region(const int *coords, int V, const int *offsets, const int *partner, int K, int *nbr_fwd, int *nbr_inv,
+                     void *workspace, size_t workspace_bytes, ms3d_stream_t stream_)
+{
+    hipStream_t stream = (hipStream_t)stream_;
+    if (K < 1 || K > 254 || !partner) return MS3D_E_UNSUPPORTED;
+    RegionPartner rp;
+    for (int k = 0; k < K; ++k) {
+        const int p = partner[k];
+        if (p != -1 && (p < 0 || p >= K || partner[p] != k)) return MS3D_E_UNSUPPORTED;     // not an involution
+        rp.p[k] = (unsigned char)(p < 0 ? REGION_NO_PARTNER : p);
+    }
+    for (int k = K; k < 256; ++k) rp.p[k] = (unsigned char)REGION_NO_PARTNER;
+    if (V < 0) return MS3D_E_UNSUPPORTED;
+    CoordWs w;
+    if (carve(w, V > 0 ? V : 1, workspace) > workspace_bytes) return MS3D_E_WORKSPACE;
+    if (V == 0) return 0;
+    if (!coords || !offsets || !nbr_fwd || !nbr_inv || !workspace) return MS3D_E_UNSUPPORTED;
+    int rc = build_table(w, coords, V, 1, stream);
+    if (rc) return rc;
+    const long n = (long)V * K;
+    if (nbr_inv == nbr_fwd + n) {           // one allocation [2][K][V] (what the Python backend hands over): one fill
+        fill_minus1_kernel<<<ms3d_divup(2 * n, 256), 256, 0, stream>>>(nbr_fwd, 2 * n);
+        MS3D_LAUNCH_CHECK();
+    } else {
+        fill_minus1_kernel<<<ms3d_divup(n, 256), 256, 0, stream>>>(nbr_fwd, n);
+        MS3D_LAUNCH_CHECK();
+        fill_minus1_kernel<<<ms3d_divup(n, 256), 256, 0, stream>>>(nbr_inv, n);
+        MS3D_LAUNCH_CHECK();
+    }
+    dim3 grid(ms3d_divup(V, 256), K);
+    kmap_region_kernel<<<grid, 256, 0, stream>>>(coords, V, offsets, K, rp, w.keys, w.vals, (unsigned)w.H - 1u, w.slot_of_row,
+                                                 w.total + 1, nbr_fwd, nbr_inv);
     MS3D_LAUNCH_CHECK();
     return 0;
 }
