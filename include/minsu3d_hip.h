@@ -184,6 +184,14 @@ size_t ms3d_coord_workspace_bytes(int n);
  * *n_unique -> [host].  unique_idx may be NULL. */
 int ms3d_sparse_quantize(const int *coords, int n, int *unique_idx, int *inverse, int *n_unique /*[host]*/,
                          void *workspace, size_t workspace_bytes, ms3d_stream_t stream);
+/* labels through that quantisation (csrc/labels.hip): out[u] = the label all rows i with inverse[i] == u share, else
+ * ignore_label -- ME's "the first point sets the label, a later point with another label turns it into ignore_label for good"
+ * in its order-independent form.  unique_idx [m] and inverse [n] are what ms3d_sparse_quantize returned for the n rows.  Two
+ * launches (initialise from the first-occurrence rows, then every dissenting row stores ignore_label: all writers of a slot
+ * store one value), plain stores, no atomics, no sort, the same bytes on every run.  n == 0 or m == 0: returns 0, launches
+ * nothing; n < 0, m < 0, m > n or a NULL array: MS3D_E_UNSUPPORTED.  An index outside its array is never followed. */
+int ms3d_quantize_labels(const int *labels /*[n]*/, const int *unique_idx /*[m]*/, const int *inverse /*[n]*/, int n, int m,
+                         int ignore_label, int *out /*[m]*/, ms3d_stream_t stream);
 /* submanifold 3x3x3 table nbr[27][V]; offset k = ix + 3*iy + 9*iz <-> (ix-1, iy-1, iz-1)*tensor_stride */
 int ms3d_kmap_k3(const int *coords, int V, int tensor_stride, int *nbr, void *workspace, size_t workspace_bytes,
                  ms3d_stream_t stream);

@@ -94,6 +94,23 @@ Kernel regions -- crosses and hand-written offset lists:
     A layer argument that contradicts the generator, an even cross, repeated custom rows and CUSTOM with dilation != 1 raise
     ValueError.
 
+Labels and batches in -- what a segmentation, completion or detection script calls before its first layer:
+
+    utils.sparse_quantize(..., labels=, ignore_label=-100, return_maps_only=False)  (keyword-only: the positional order is the
+    reference's call form, not MinkowskiEngine's), utils.batched_coordinates, utils.sparse_collate(coords, feats, labels),
+    utils.batch_sparse_collate, utils.SparseCollation(limit_numpoints)
+
+    Returns coords[, features][, labels][, index][, inverse]; one label per returned row, in the labels' own integer dtype.
+    On the GPU the vote is ms3d_quantize_labels (csrc/labels.hip) over the maps of ms3d_sparse_quantize: two launches
+    (initialise from the first-occurrence rows, then every dissenting row stores ignore_label), plain stores, no atomics, no
+    sort, the same bytes on every run; on CPU tensors, numpy input and in DataLoader workers the same rule as a torch
+    expression.  Chosen here without a copy of MinkowskiEngine to compare against: a voxel keeps a label only when ALL of
+    its points carry it, else it gets ignore_label; ignore_label defaults to -100 and votes like any other label (a voxel
+    whose points all carry it keeps it, a real label beside it does not win the voxel); labels that are not integers, not of
+    shape [N] or outside int32, an ignore_label outside int32 or the labels' dtype, and return_maps_only with labels raise
+    ValueError.  batched_coordinates floors float input and numbers the samples by their position in the list, empty
+    samples included; sparse_collate hands a list of labels that are not arrays back as it is.
+
 Not supported (each raises NotImplementedError naming it): `axis_types` of a KernelGenerator, a region of more than 254
 offsets, a dense grid of more than 2^31 - 1 cells, to_sparse of a tensor
 that is not 5-D ([B, C, X, Y, Z]: dimension 3) or in a format other than "BCXXX" / "BXXXC", dense() on a per-axis tensor stride, strides other than 1 and 2, a generative layer at stride 2 on an odd

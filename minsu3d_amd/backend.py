@@ -809,6 +809,18 @@ class _HipEngine:
                    "ms3d_sparse_quantize")
         return uniq[:nu.value], inv[:n]
 
+    def quantize_labels(self, labels, uniq, inv, ignore_label):
+        """label of every voxel of sparse_quantize's (uniq, inv): the one all its points share, else ignore_label
+        (csrc/labels.hip) -> int32 [m]"""
+        labels, uniq, inv = self._dev(labels), self._dev(uniq), self._dev(inv)
+        assert labels.dtype == uniq.dtype == inv.dtype == torch.int32 and labels.dim() == uniq.dim() == inv.dim() == 1
+        n, m = labels.size(0), uniq.size(0)
+        assert inv.size(0) == n
+        out = torch.empty(m, dtype=torch.int32, device=labels.device)
+        _lib.check(self.lib.ms3d_quantize_labels(_lib.ptr(labels), _lib.ptr(uniq), _lib.ptr(inv), n, m, int(ignore_label),
+                                                 _lib.ptr(out), _lib.stream_handle()), "ms3d_quantize_labels")
+        return out
+
     def spatial_order(self, coords):
         """row permutation that sorts voxels by (batch, Morton code); None = keep the given order"""
         coords = self._dev(coords)

@@ -1,7 +1,8 @@
 """`import MinkowskiEngine as ME` for the reference's call sites (SparseTensor,
 MinkowskiConvolution, MinkowskiConvolutionTranspose, MinkowskiBatchNorm, MinkowskiReLU, cat,
 utils.sparse_quantize, utils.sparse_collate) and the general convolution / pooling / linear layers beside them -- an
-alias of minsu3d_amd.MinkowskiEngine."""
+alias of minsu3d_amd.MinkowskiEngine.  `utils` is that package's module itself, so ME.utils.batched_coordinates,
+batch_sparse_collate and SparseCollation are reached through it without a re-export."""
 import sys
 
 import minsu3d_amd.MinkowskiEngine as _me
