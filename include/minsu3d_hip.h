@@ -234,6 +234,35 @@ int ms3d_kmap_region(const int *coords, int V, const int *offsets /*DEVICE [K][3
                      int *nbr_fwd /*[K][V]*/, int *nbr_inv /*[K][V]*/, void *workspace, size_t workspace_bytes,
                      ms3d_stream_t stream);
 
+/* Kernel maps as index pairs (csrc/kmap_pairs.hip): an offset-major table nbr[K][Vout] (int32, -1 = none, valid entries in
+ * [0, Vin)) exported as packed per-offset pair lists in the CALLER's row numbering.
+ *   out_order [Vout] or NULL  out_order[j] = the row of the table (the held row) of visible output row j; NULL = identity
+ *   in_rename [Vin] or NULL   in_rename[i] = the visible row of held input row i; NULL = identity
+ *   start [K + 1], DEVICE     int32: start[k] = first pair of offset k, start[K] = P = the number of valid entries
+ *   pairs [2][pair_ld]        int64 (so that features[pairs[0]] indexes as it is): row 0 the visible input row, row 1 the
+ *                             visible output row; offset k owns columns start[k] .. start[k + 1]; inside an offset the pairs
+ *                             ascend in the visible output row j (the kernel walks j and reads nbr[k][out_order[j]]).
+ *                             pair_ld >= P is the length of a row of the buffer; columns >= P are not written.
+ * An entry >= Vin is never followed into in_rename: it is treated as -1, as is the entry behind an out_order value outside
+ * [0, Vout).
+ * Two calls with one host read between them: ms3d_kmap_pairs_count (one workgroup per offset and run of
+ * ms3d_kmap_pairs_rows() visible output rows: wave ballots and popcounts -> one int per (k, run), k-major; one exclusive scan
+ * over them; start[]), the host reads start[K] and allocates pairs, then ms3d_kmap_pairs_fill with the SAME arguments and the
+ * SAME, untouched workspace (the same decomposition: ballot again, lane rank by mbcnt, wave bases through LDS, both rows
+ * stored at consecutive columns).  No atomics and no sort: every slot has one writer, the same bytes on every run.
+ * Decided on the host before anything is launched: K < 1, K > 65535 (the offset is a grid coordinate), Vout < 0, Vin < 0, a NULL
+ * nbr / start / pairs, pair_ld < 0 or K * Vout > 2^31 - 1 (P must fit start's int32): MS3D_E_UNSUPPORTED; a workspace shorter
+ * than ms3d_kmap_pairs_workspace_bytes(K, Vout) (pure host arithmetic, 4 bytes per (k, run) plus the scan's; 0 for a refused
+ * geometry or Vout == 0): MS3D_E_WORKSPACE.  Vout == 0 (or, for the fill, pair_ld == 0): returns 0 and launches nothing -- start
+ * is then the caller's to zero. */
+int ms3d_kmap_pairs_rows(void);
+size_t ms3d_kmap_pairs_workspace_bytes(int K, int Vout);
+int ms3d_kmap_pairs_count(const int *nbr, int K, int Vout, int Vin, const int *out_order, int *start /*DEVICE [K + 1]*/,
+                          void *workspace, size_t workspace_bytes, ms3d_stream_t stream);
+int ms3d_kmap_pairs_fill(const int *nbr, int K, int Vout, int Vin, const int *out_order, const int *in_rename,
+                         long long *pairs /*[2][pair_ld]*/, long long pair_ld, const void *workspace, size_t workspace_bytes,
+                         ms3d_stream_t stream);
+
 /* ---- coordinate sets that are not derived by flooring: generation and pruning.
  * ms3d_coords_expand: the set of distinct (batch of row i, xyz of row i + offsets[k]) over all input rows i and offsets k, in
  * first-occurrence order of the candidate sequence c = i * K + k (input row major, offset minor) -- the rule

@@ -94,6 +94,32 @@ Kernel regions -- crosses and hand-written offset lists:
     A layer argument that contradicts the generator, an even cross, repeated custom rows and CUSTOM with dilation != 1 raise
     ValueError.
 
+Kernel, stride and origin maps as index pairs -- what a layer the user writes (local attention over a kernel map, a pooling,
+a correspondence loss, a plot) indexes x.F with:
+
+    CoordinateManager.kernel_map(in_key, out_key, stride=1, kernel_size=3, dilation=1, region_type=RegionType.HYPER_CUBE,
+    region_offsets=None, is_transpose=False, is_pool=False, kernel_generator=None) -> {k: int64 [2, N_k]} (input row, output
+    row), CoordinateManager.stride(key, stride=2) -> CoordinateMapKey, CoordinateManager.stride_map(in_key, stride_key) ->
+    (in_rows, out_rows), CoordinateManager.origin_map(key) -> {0: int64 [2, V]}; a key is a CoordinateMapKey or a
+    SparseTensor  (+ CoordinateManager.kernel_map_pairs -> (pairs int64 [2, P], start int32 [K + 1]): the packed form the dict
+    is made of views of; kernel_map_tables: the engine's tables under a name of their own: engine extras)
+
+    The rows are the rows of `.coordinates` / `.features` as the CALLER sees them, also on a Morton-sorted manager.  Column
+    (i, o) of entry k: C_out[o] + off_k == C_in[i] with off = kernel_offsets / region_offsets at the input's tensor stride;
+    is_transpose=True: C_out[o] - off_k == C_in[i] with off at the output's tensor stride (the rule of the generative
+    layer); y.F = sum_k index_add(o, x.F[i] @ W[k]) is the layer.  The tables are the layers' own (kernel_map_tables,
+    kernel_map_inverse, target_map for a set of another manager); ms3d_kmap_pairs_count / ms3d_kmap_pairs_fill (csrc/
+    kmap_pairs.hip) pack them: ballot and popcount per (offset, run of rows), one scan, one host read of the pair count,
+    then both int64 rows stored at their ranks, the caller's numbering folded in; no atomics, no sort, the same bytes on
+    every run.  Cached per (keys, geometry, direction).  kernel_map(ts, kernel_size, ...) with a tensor stride first stays
+    the engine's form.  stride_map pairs every row of the finer set with its parent, floor(c / s) * s, from the k2 tables;
+    origin_map names, per row, the row of a MinkowskiGlobal*Pooling output its sample lands in (the rank of its batch index
+    among those present -- checked against the global pooling layers).
+    Chosen here without a copy of MinkowskiEngine to compare against, recalled, not pinned: int64 pairs; the dict holds only
+    the offsets that have a pair, in ascending k; inside an entry the output row ascends; is_pool changes nothing (pooling
+    and convolution share their tables); the keys' tensor strides must agree with `stride` (ValueError), as must the
+    arguments with a kernel_generator given beside them.
+
 Labels and batches in -- what a segmentation, completion or detection script calls before its first layer:
 
     utils.sparse_quantize(..., labels=, ignore_label=-100, return_maps_only=False)  (keyword-only: the positional order is the

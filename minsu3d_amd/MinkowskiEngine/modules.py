@@ -78,8 +78,8 @@ class _ConvBase(nn.Module):
     def _spec(self, cm, ts):
         """-> (ConvSpec of the forward convolution from tensor stride ts, output tensor stride)"""
         cin, cout = self.in_channels, self.out_channels
-        nbr_fwd, nbr_bwd, vin, vout, K, out_ts, mirror = cm.kernel_map(ts, self.kernel_size, self.stride, self.dilation,
-                                                                       region=self.region)
+        nbr_fwd, nbr_bwd, vin, vout, K, out_ts, mirror = cm.kernel_map_tables(ts, self.kernel_size, self.stride, self.dilation,
+                                                                              region=self.region)
         if self.region is not None:
             # (sub = False: a custom list of 27 or 8 offsets is neither the 3x3x3 submanifold map nor the k2 map)
             return Fn.ConvSpec(nbr_fwd, nbr_bwd, vin, vout, K, cin, cout, False, False), out_ts
@@ -412,7 +412,7 @@ class MinkowskiChannelwiseConvolution(nn.Module):
                 else:
                     y = Fn.channelwise_conv(x._raw(), self.kernel, self.bias, nbr_fwd, nbr_inv, vin, vout, K)
                 return SparseTensor(y, coordinate_manager=key.coordinate_manager, tensor_stride=key.tensor_stride)
-        nbr_fwd, _, vin, vout, K, out_ts, _ = cm.kernel_map(ts, *geom, region=self.region)
+        nbr_fwd, _, vin, vout, K, out_ts, _ = cm.kernel_map_tables(ts, *geom, region=self.region)
         nbr_inv = cm.kernel_map_inverse(ts, *geom, region=self.region)
         y = Fn.channelwise_conv(x._raw(), self.kernel, self.bias, nbr_fwd, nbr_inv, vin, vout, K)
         return x._like(y, tensor_stride=out_ts)
@@ -592,7 +592,7 @@ class _PoolBase(nn.Module):
             if key.coordinate_manager is not cm:
                 table = cm.target_map(ts, key, self.kernel_size, self.stride, self.dilation, region=self.region)
                 return _pool_onto(x, key, table, self.MODE)
-        nbr_fwd, _, vin, vout, K, out_ts, _ = cm.kernel_map(ts, self.kernel_size, self.stride, self.dilation, region=self.region)
+        nbr_fwd, _, vin, vout, K, out_ts, _ = cm.kernel_map_tables(ts, self.kernel_size, self.stride, self.dilation, region=self.region)
         nbr_inv = cm.kernel_map_inverse(ts, self.kernel_size, self.stride, self.dilation, region=self.region)
         y = Fn.sparse_pool(x._raw(), nbr_fwd, nbr_inv, vin, vout, K, self.MODE)
         return x._like(y, tensor_stride=out_ts)
@@ -651,7 +651,7 @@ class MinkowskiPoolingTranspose(nn.Module):
             # (a set of this manager: its own at stride 1, the cached finer one at stride 2 -- the ordinary paths below)
         if self.stride == 1:
             # the transpose of a submanifold table is its mirror image, and a sum does not care about the offset order
-            nbr, _, vin, vout, K, _, _ = cm.kernel_map(ts, *geom, region=self.region)
+            nbr, _, vin, vout, K, _, _ = cm.kernel_map_tables(ts, *geom, region=self.region)
             inv = cm.kernel_map_inverse(ts, *geom, region=self.region)
             if self.region is not None:
                 nbr, inv = inv, nbr        # out[o] = sum_k in[o - off_k]: the inverse table forward (a region has no mirror rule)
@@ -662,7 +662,7 @@ class MinkowskiPoolingTranspose(nn.Module):
                                       f"tensor stride {ts}: only onto a cached finer coordinate set; generating new "
                                       "coordinates is not supported")
         fine = ts // 2
-        down, _, v_fine, v_coarse, K, _, _ = cm.kernel_map(fine, *geom, region=self.region)    # the strided map fine -> ts
+        down, _, v_fine, v_coarse, K, _, _ = cm.kernel_map_tables(fine, *geom, region=self.region)    # the strided map fine -> ts
         up = cm.kernel_map_inverse(fine, *geom, region=self.region)           # [K, v_fine]: the coarse row a fine row feeds
         y = Fn.sparse_pool(x._raw(), up, down, v_coarse, v_fine, K, 2)
         return x._like(y, tensor_stride=fine)

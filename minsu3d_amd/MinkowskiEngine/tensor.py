@@ -9,6 +9,7 @@ input rows, so `Sequential(BN, ReLU, Conv)` is one gather kernel and never mater
 activations.  Touching `.features` of such a tensor materialises it (one elementwise kernel).
 """
 import enum
+import functools
 import os
 
 import numpy as np
@@ -256,6 +257,15 @@ def target_key(coordinates, out_ts, device):
         while len(_TARGET_SETS) > 4:
             _TARGET_SETS.pop(next(iter(_TARGET_SETS)))
     return CoordinateMapKey(hit[0], out_ts)
+
+
+def _as_key(what, name):
+    """a CoordinateMapKey, or a SparseTensor (its key) -> the CoordinateMapKey"""
+    if isinstance(what, SparseTensor):
+        return what.coordinate_map_key
+    if not isinstance(what, CoordinateMapKey):
+        raise TypeError(f"{name}: a CoordinateMapKey or a SparseTensor, got {type(what).__name__}")
+    return what
 
 
 def _check_region_geometry(kernel_size, stride, dilation, region):
@@ -522,7 +532,177 @@ class CoordinateManager:
             return torch.where(rows >= 0, self.perm[rows.clamp(min=0).long()], rows.long()).to(torch.int32)
         return rows
 
+    @functools.singledispatchmethod
     def kernel_map(self, ts, kernel_size, stride=1, dilation=1, region=None):
+        """Two forms, chosen by the type of the first argument (a single-dispatch method: this is its base implementation).
+
+        kernel_map(ts, kernel_size, stride=1, dilation=1, region=None), ts a tensor stride: the ENGINE's form, the tables the
+        layers consume -- kernel_map_tables, unchanged (the layers call that name, past the dispatch).
+
+        kernel_map(in_key, out_key, stride=1, kernel_size=3, dilation=1, region_type=RegionType.HYPER_CUBE, region_offsets=None,
+        is_transpose=False, is_pool=False, kernel_generator=None), the keys CoordinateMapKeys or SparseTensors (their keys):
+        MinkowskiEngine's form -> dict {k: int64 [2, N_k]} of the offsets k that have at least one pair, in ascending k.
+        Column (i, o) of entry k: row i of in_key's `.coordinates` feeds row o of out_key's `.coordinates` through kernel[k], rows
+        as the CALLER sees them (a Morton-sorted set is renamed inside the export kernel):
+          forward     C_out[o] + off_k == C_in[i], off = kernel_offsets / region_offsets at the INPUT's tensor stride
+          transposed  C_out[o] - off_k == C_in[i], off at the OUTPUT's tensor stride (the rule of generate())
+        so y.F = sum_k index_add(o, x.F[i] @ W[k]) is the layer, and inside an entry o ascends.  The entries are views of
+        kernel_map_pairs' tensor (see there for the tables, the errors and the cache); the dict is cached with it.  int64 and
+        "only the offsets that have pairs" are MinkowskiEngine's conventions as recalled, not pinned."""
+        return self.kernel_map_tables(ts, kernel_size, stride, dilation, region=region)
+
+    def _kernel_map_of_keys(self, in_key, out_key, stride=1, kernel_size=3, dilation=1, region_type=RegionType.HYPER_CUBE,
+                            region_offsets=None, is_transpose=False, is_pool=False, kernel_generator=None):
+        """kernel_map's implementation for a CoordinateMapKey or a SparseTensor first (registered below the classes)"""
+        return self._pair_lists(in_key, out_key, stride, kernel_size, dilation, region_type, region_offsets, is_transpose,
+                                is_pool, kernel_generator)[2]
+
+    def kernel_map_pairs(self, in_key, out_key, stride=1, kernel_size=3, dilation=1, region_type=RegionType.HYPER_CUBE,
+                         region_offsets=None, is_transpose=False, is_pool=False, kernel_generator=None):
+        """the packed form of kernel_map(in_key, out_key, ...) -> (pairs int64 [2, P], start int32 [K + 1] on the device): row 0
+        the input rows, row 1 the output rows, offset k in columns start[k] .. start[k + 1] (backend.kmap_pairs, csrc/
+        kmap_pairs.hip).  An engine extra.
+        The table that is exported (all of them exist already): same manager, not transposed, out stride == in stride * stride:
+        kernel_map_tables(in stride, ...)[0]; same manager, transposed, in stride == out stride * stride: the inverse table of
+        kernel_map_tables(out stride, ...) (kernel_map_inverse); another manager -- a `coordinates=` target, an expanded,
+        generated or pruned set: target_map(in stride, out_key, ...).  The geometry is checked by KernelGenerator, so its
+        refusals apply (strides other than 1 and 2, an even kernel at stride 1, more than 254 offsets: NotImplementedError).
+        ValueError, before any backend is touched: the keys' tensor strides contradict `stride`; a key's manager holds no set of
+        its tensor stride; kernel_generator together with an argument that is not at its default and differs from the
+        generator's.  is_pool is accepted and changes nothing (pooling and convolution share their tables).  The work is done
+        by in_key's manager, whichever manager was asked.  A Morton-sorted stride-1 set hands its `inv` as out_order and its
+        `perm` as in_rename (int32 copies kept on the manager).  Cached on in_key's manager per (keys, geometry, direction); the
+        lists onto another manager are kept with the key, the sixteen newest, as target_map keeps its tables."""
+        return self._pair_lists(in_key, out_key, stride, kernel_size, dilation, region_type, region_offsets, is_transpose,
+                                is_pool, kernel_generator)[:2]
+
+    def _pair_lists(self, in_key, out_key, stride=1, kernel_size=3, dilation=1, region_type=RegionType.HYPER_CUBE,
+                    region_offsets=None, is_transpose=False, is_pool=False, kernel_generator=None):
+        """-> (pairs, start, dict) of kernel_map_pairs / kernel_map(in_key, out_key, ...)"""
+        in_key, out_key = _as_key(in_key, "in_key"), _as_key(out_key, "out_key")
+        cm, in_ts, out_ts = in_key.coordinate_manager, in_key.tensor_stride, out_key.tensor_stride
+        out_cm = out_key.coordinate_manager
+        for name, key in (("in_key", in_key), ("out_key", out_key)):
+            if key.tensor_stride not in key.coordinate_manager.coords:
+                raise ValueError(f"kernel_map: {name}'s manager holds no coordinate set of tensor stride {key.tensor_stride}")
+        given = dict(kernel_size=kernel_size, stride=stride, dilation=dilation, region_type=region_type,
+                     is_transpose=bool(is_transpose))
+        if kernel_generator is None:
+            kernel_generator = KernelGenerator(kernel_size, stride, dilation, bool(is_transpose), region_type, region_offsets)
+        else:
+            if not isinstance(kernel_generator, KernelGenerator):
+                raise TypeError(f"kernel_generator: a KernelGenerator, got {type(kernel_generator).__name__}")
+            defaults = dict(kernel_size=3, stride=1, dilation=1, region_type=RegionType.HYPER_CUBE, is_transpose=False)
+            for name, value in given.items():
+                if value != defaults[name] and value != getattr(kernel_generator, name):
+                    raise ValueError(f"kernel_map: {name}={value!r} contradicts kernel_generator ({kernel_generator!r})")
+            if region_offsets is not None:
+                theirs = kernel_generator.region_offsets
+                mine = torch.as_tensor(region_offsets).to(torch.int64).cpu()
+                if theirs is None or theirs.shape != mine.shape or not torch.equal(theirs.to(torch.int64), mine):
+                    raise ValueError(f"kernel_map: region_offsets contradicts kernel_generator ({kernel_generator!r})")
+        g = kernel_generator
+        transposed = g.is_transpose
+        if (in_ts != out_ts * g.stride) if transposed else (out_ts != in_ts * g.stride):
+            raise ValueError(f"kernel_map: tensor strides {in_ts} -> {out_ts} contradict stride={g.stride}"
+                             + (" of a transposed map (in == out * stride)" if transposed else " (out == in * stride)"))
+        own = out_cm is cm
+        cache = cm.__dict__.setdefault("_pair_lists_own" if own else "_pair_lists_onto", {})
+        ident = (in_ts, out_key, g.stride, transposed) + ((g.kernel_size, g.dilation) if g.region_key is None else (g.region_key,))
+        hit = cache.get(ident)
+        if hit is None:
+            be = get_backend()
+            if not hasattr(be, "kmap_pairs") or not cm.coords[in_ts].is_cuda:
+                raise NotImplementedError("kernel_map(in_key, out_key, ...) needs the HIP backend (ms3d_kmap_pairs_count)")
+            geom = (g.kernel_size, g.stride, g.dilation)
+            if not own:
+                nbr, _, vin, vout, K = cm.target_map(in_ts, out_key, *geom, transposed=transposed, region=g.region_key)
+            elif transposed:
+                _, _, vout, vin, K, _, _ = cm.kernel_map_tables(out_ts, *geom, region=g.region_key)
+                nbr = cm.kernel_map_inverse(out_ts, *geom, region=g.region_key)
+            else:
+                nbr, _, vin, vout, K, _, _ = cm.kernel_map_tables(in_ts, *geom, region=g.region_key)
+            pairs, start = be.kmap_pairs(nbr.contiguous(), K, vout, vin, out_cm._rows32("inv") if out_ts == 1 else None,
+                                         cm._rows32("perm") if in_ts == 1 else None)
+            s = start.tolist()
+            hit = cache[ident] = (pairs, start, {k: pairs[:, s[k]:s[k + 1]] for k in range(K) if s[k + 1] > s[k]})
+            while not own and len(cache) > 16:
+                cache.pop(next(iter(cache)))
+        return hit
+
+    def _rows32(self, which):
+        """`perm` / `inv` as int32 (what the export kernel reads), None on a manager that holds its rows in the caller's order"""
+        rows = getattr(self, which)
+        if rows is None:
+            return None
+        cache = self.__dict__.setdefault("_perm32", {})
+        if which not in cache:
+            cache[which] = rows.to(torch.int32).contiguous()
+        return cache[which]
+
+    def stride(self, key, stride=2):
+        """CoordinateMapKey of the set at key's tensor stride * stride on key's manager, made through k2 (one stride-2 step
+        per factor of two) when missing.  stride == 1 returns the key; anything but a power of two raises NotImplementedError."""
+        key = _as_key(key, "key")
+        cm, ts = key.coordinate_manager, key.tensor_stride
+        if isinstance(stride, bool) or not isinstance(stride, int) or stride < 1 or stride & (stride - 1):
+            raise NotImplementedError(f"stride={stride!r}: strides other than 1 and 2 are built from stride-2 steps, so only "
+                                      "powers of two are supported")
+        if ts not in cm.coords:
+            raise ValueError(f"stride: the key's manager holds no coordinate set of tensor stride {ts}")
+        if stride == 1:
+            return key
+        while stride > 1:
+            cm.k2(ts)
+            ts, stride = 2 * ts, stride // 2
+        return CoordinateMapKey(cm, ts)
+
+    def stride_map(self, in_key, stride_key):
+        """(in_rows int64 [V_in], out_rows int64 [V_in]): every row of the finer set in_key with its parent -- the row at
+        floor(c / s) * s -- in the coarser set stride_key of the SAME manager, rows as the caller sees both sets, in_rows
+        ascending (an arange).  stride_key's tensor stride is in_key's times a power of two >= 2; the levels in between are
+        made on the way.  From the k2 up-tables (one valid entry per column), chained across the levels; built once.  Keys of
+        different managers or a coarser -> finer order: ValueError."""
+        in_key, stride_key = _as_key(in_key, "in_key"), _as_key(stride_key, "stride_key")
+        cm, ts, top = in_key.coordinate_manager, in_key.tensor_stride, stride_key.tensor_stride
+        if stride_key.coordinate_manager is not cm:
+            raise ValueError("stride_map: the two keys name sets of different coordinate managers")
+        ratio = top // ts if isinstance(top, int) and isinstance(ts, int) and top % ts == 0 else 0
+        if ratio < 2 or ratio & (ratio - 1):
+            raise ValueError(f"stride_map: tensor strides {ts} -> {top}: the second key must name the COARSER set, at the "
+                             "first one's tensor stride times a power of two >= 2")
+        if ts not in cm.coords:
+            raise ValueError(f"stride_map: in_key's manager holds no coordinate set of tensor stride {ts}")
+        cache = cm.__dict__.setdefault("_stride_maps", {})
+        hit = cache.get((ts, top))
+        if hit is None:
+            parent, level = None, ts
+            while level < top:
+                up = cm.k2(level)[1].amax(0).long()[:cm.size(level)]          # [V_level]: the one valid entry of every column
+                parent = up if parent is None else up[parent]
+                level *= 2
+            if ts == 1 and cm.inv is not None:
+                parent = parent[cm.inv]
+            hit = cache[(ts, top)] = (torch.arange(parent.numel(), dtype=torch.int64, device=parent.device), parent.contiguous())
+        return hit
+
+    def origin_map(self, key):
+        """{0: int64 [2, V]}: row 0 the rows of the set as the caller sees them, ascending; row 1 the row of a
+        MinkowskiGlobal*Pooling output the sample of each row lands in: the rank of its batch index among the batch indices
+        present (batch_segments, which is how _GlobalPoolBase orders its output rows).  Built once per set."""
+        key = _as_key(key, "key")
+        cm, ts = key.coordinate_manager, key.tensor_stride
+        if ts not in cm.coords:
+            raise ValueError(f"origin_map: the key's manager holds no coordinate set of tensor stride {ts}")
+        cache = cm.__dict__.setdefault("_origin_maps", {})
+        if ts not in cache:
+            seg = cm.batch_segments(ts).long()
+            if ts == 1 and cm.inv is not None:
+                seg = seg[cm.inv]
+            cache[ts] = {0: torch.stack([torch.arange(seg.numel(), dtype=torch.int64, device=seg.device), seg])}
+        return cache[ts]
+
+    def kernel_map_tables(self, ts, kernel_size, stride=1, dilation=1, region=None):
         """-> (nbr_fwd [K, Vout], nbr_bwd [K, Vin], Vin, Vout, K, output tensor stride, mirror) for a layer from the
         coordinate set of tensor stride ts; built once per key.  (3, 1, 1), (2, 2, 1) and (1, 1, *) are the tables of
         k3() / k2() / identity().  Stride 1 (odd kernel sizes only): the output set is the input set, the table is its own
@@ -595,7 +775,7 @@ class CoordinateManager:
         """[K, Vin] table that names, per offset, the OUTPUT row an input row feeds (what a backward gather of a pooling
         layer walks): nbr_bwd of a strided map; for a submanifold map -- whose nbr_bwd is the forward table, to be read
         with mirrored offsets -- the inverse is built (and kept) here"""
-        nbr_fwd, nbr_bwd, vin, vout, K, _, mirror = self.kernel_map(ts, kernel_size, stride, dilation, region=region)
+        nbr_fwd, nbr_bwd, vin, vout, K, _, mirror = self.kernel_map_tables(ts, kernel_size, stride, dilation, region=region)
         if not mirror and nbr_bwd is not nbr_fwd:
             return nbr_bwd
         key = (ts, int(kernel_size), int(stride), int(dilation))
@@ -1127,6 +1307,11 @@ class SparseTensor:
         elif not isinstance(other, (int, float)):
             raise TypeError(f"unsupported operand for a SparseTensor: {type(other).__name__}")
         return fn(rows, other)
+
+
+# kernel_map(in_key, out_key, ...): the forms chosen by the type of the first argument (the classes exist only here)
+for _cls in (CoordinateMapKey, SparseTensor):
+    CoordinateManager.kernel_map.register(_cls, CoordinateManager._kernel_map_of_keys)
 
 
 class SparseTensorQuantizationMode(enum.Enum):

@@ -917,6 +917,35 @@ class _HipEngine:
                                              _lib.ptr(ws), C.c_size_t(ws.numel()), _lib.stream_handle()), "ms3d_kmap_region")
         return fwd, inv
 
+    def kmap_pairs(self, nbr, K, vout, vin, out_order=None, in_rename=None):
+        """a table nbr [K, Vout] (int32, -1 = none) as packed pair lists in the caller's row numbering (csrc/kmap_pairs.hip) ->
+        (pairs int64 [2, P]: row 0 the visible input row, row 1 the visible output row, offset k in columns start[k] ..
+        start[k + 1], ascending in the output row; start int32 [K + 1] on the device).  out_order int32 [Vout]: the held row of
+        visible output row j; in_rename int32 [Vin]: the visible row of held input row i; None = identity.  One host read
+        (P), as downsample and coords_expand have."""
+        nbr = self._dev(nbr)
+        K, vout, vin = int(K), int(vout), int(vin)
+        assert nbr.dtype == torch.int32 and nbr.is_contiguous() and nbr.dim() == 2 and nbr.size(0) == K \
+            and nbr.size(1) == max(vout, 1)
+        dev = nbr.device
+        for name, t, n in (("out_order", out_order, vout), ("in_rename", in_rename, vin)):
+            assert t is None or (t.dtype == torch.int32 and t.is_contiguous() and t.dim() == 1 and t.numel() == n
+                                 and t.device == dev), name
+        if K * vout > 2 ** 31 - 1:
+            _lib.check(_lib.E_UNSUPPORTED, f"ms3d_kmap_pairs_count ({K} offsets x {vout} rows: more than 2^31 - 1 entries)")
+        start = torch.empty(K + 1, dtype=torch.int32, device=dev)
+        if vout == 0:
+            start.zero_()
+        ws = self.ws.get("kmap_pairs", self.lib.ms3d_kmap_pairs_workspace_bytes(K, vout), dev)
+        args = (_lib.ptr(nbr), K, vout, vin, _lib.ptr(out_order))
+        _lib.check(self.lib.ms3d_kmap_pairs_count(*args, _lib.ptr(start), _lib.ptr(ws), C.c_size_t(ws.numel()),
+                                                  _lib.stream_handle()), "ms3d_kmap_pairs_count")
+        P = int(start[K].item())
+        pairs = torch.empty((2, P), dtype=torch.int64, device=dev)
+        _lib.check(self.lib.ms3d_kmap_pairs_fill(*args, _lib.ptr(in_rename), _lib.ptr(pairs), C.c_longlong(P), _lib.ptr(ws),
+                                                 C.c_size_t(ws.numel()), _lib.stream_handle()), "ms3d_kmap_pairs_fill")
+        return pairs, start
+
     # ---- coordinate sets that are generated or pruned
     def coords_expand(self, in_coords, offsets):
         """-> int32 [n, 4]: the distinct (b, xyz + offsets[k]) over all rows of in_coords and all offsets, in first-occurrence
