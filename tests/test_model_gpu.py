@@ -251,6 +251,35 @@ def test_proposal_voxel_coords_fused_vs_expression_chain(seed):
 
 
 @pytest.mark.gpu
+def test_proposal_voxel_coords_grid_stride():
+    """the same comparison with 2048 + 50 proposals of 1 to 5 points: pv_params_kernel's grid-stride loop (2048 blocks,
+    two __syncthreads per iteration, the LDS partials reused) runs a second iteration"""
+    from minsu3d_amd.backend import get_backend
+    from minsu3d_amd.model.general_model import proposal_voxel_coords_torch
+    g = torch.Generator().manual_seed(7)
+    P = 2048 + 50
+    sizes = torch.randint(1, 6, (P,), generator=g)
+    sizes[:5] = torch.tensor([1, 2, 5, 1, 3])
+    centre = torch.rand(P, 1, 3, generator=g) * torch.tensor([8.0, 6.0, 3.0])
+    radius = torch.where(torch.arange(P) % 7 == 0, 0.004, 0.3).view(P, 1, 1) * (torch.rand(P, 1, 1, generator=g) + 0.1)
+    coords = (centre + torch.randn(P, 5, 3, generator=g) * radius).view(-1, 3).contiguous()     # 5 candidates per proposal
+    member = torch.arange(5).expand(P, 5) < sizes[:, None]
+    prop, slot = torch.nonzero(member, as_tuple=True)
+    point = prop * 5 + slot
+    point[::11] = torch.randint(0, 5 * P, (point[::11].numel(),), generator=g)                   # some far, shared points
+    idx = torch.stack((prop, point), 1).long().cuda().contiguous()
+    off = torch.cat((torch.zeros(1, dtype=torch.int64), torch.cumsum(sizes, 0))).int().cuda()
+    coords = coords.cuda()
+    u = torch.rand(6, generator=g).cuda()
+    for scale, ss in ((50, 14), (3, 128)):
+        want = proposal_voxel_coords_torch(idx, off, coords, scale, ss, u[:3], u[3:])
+        got = get_backend().proposal_voxel_coords(idx, off, coords, scale, ss, u)
+        assert got.dtype == torch.int32 and torch.equal(got, want)
+        assert int(got[:, 1:].min()) >= 0 and int(got[:, 1:].max()) < ss
+        assert torch.equal(got[:, 0], idx[:, 0].int())
+
+
+@pytest.mark.gpu
 def test_one_launch_adam_matches_torch_adam():
     """minsu3d_amd.optim.Adam (one library launch per step) against torch.optim.Adam on the same parameters and
     gradients: tensors of 1 .. 300k elements (chunk boundaries, odd sizes), a sliced (unaligned) gradient, weight decay,

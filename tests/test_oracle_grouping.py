@@ -6,6 +6,9 @@ import os
 import numpy as np
 import pytest
 
+from segment_cases import (edge_offsets, mask_label_cases, mask_label_expected, mask_label_points, shifted,
+                           special_values)
+
 
 def _cases(golden_dir):
     return sorted(glob.glob(os.path.join(golden_dir, "bfs_case*.npz")))
@@ -131,3 +134,94 @@ def test_iou_small(oracle):
     assert np.allclose(iou, want.astype(np.float32), rtol=0, atol=1e-7)
     ml, mlm = oracle.get_mask_label(prop_idx, prop_off, inst, np.array([5, -1], np.int16), iou, -1, 0.3)
     assert mlm.tolist() == [True] * 4 + [False] * 3 and ml.tolist() == [True, True, False, False, False, False, False]
+
+
+# ------------------------------------------------------------------ the oracle on the edge / special-value inputs
+# (tests/segment_cases.py) against a transcription of the reference's serial loops in np.float32, compared by bit
+# pattern: the expectation tests/test_segment_edges_gpu.py holds the HIP kernels to is validated here, without a GPU
+
+def _bits(a):
+    return np.ascontiguousarray(a, np.float32).view(np.int32)
+
+
+def _serial_segment_ops(x, off):
+    """sec_mean.cu:12-79 and roipool.cu:12-80 row by row: the mean divides before adding, the average pool sums and
+    then divides, min / max compare strictly so the first extremum (and never a NaN) wins"""
+    P, C = len(off) - 1, x.shape[1]
+    out = {k: np.zeros((P, C), np.float32) for k in ("mean", "min", "max", "avg")}
+    out["argmax"] = np.zeros((P, C), np.int32)
+    with np.errstate(all="ignore"):
+        for p in range(P):
+            s, e = int(off[p]), int(off[p + 1])
+            count = np.float32(e - s)
+            mean = np.zeros(C, np.float32); total = np.zeros(C, np.float32)
+            lo = np.full(C, np.inf, np.float32); hi = np.full(C, -np.inf, np.float32); am = np.full(C, -1, np.int32)
+            for i in range(s, e):
+                row = x[i]
+                mean = mean + row / count
+                total = total + row
+                lt = row < lo
+                lo = np.where(lt, row, lo)
+                gt = row > hi
+                hi = np.where(gt, row, hi); am = np.where(gt, np.int32(i), am)
+            out["mean"][p], out["min"][p], out["max"][p], out["argmax"][p] = mean, lo, hi, am
+            out["avg"][p] = total / count
+    return out
+
+
+@pytest.mark.parametrize("C_", [3, 4, 19, 65])
+@pytest.mark.parametrize("start", [0, 7])
+def test_segment_ops_edges_and_special_values_vs_serial_numpy(oracle, C_, start):
+    rng = np.random.default_rng(50 + C_)
+    off = edge_offsets(C_)
+    if C_ == 65:                                          # the reduced set: one tile of the 1-channel stage
+        lens = np.diff(off)
+        off = np.concatenate([[0], np.cumsum(lens[lens <= 2100])]).astype(np.int32)
+    x, where = special_values(rng.standard_normal((int(off[-1]), C_)).astype(np.float32), off, rng)
+    if start:
+        x, off = shifted(x, off, front=start)
+    want = _serial_segment_ops(x, off)
+    lens = np.diff(off)
+    # the inputs hold what they claim: an argmax of -1 exactly for the empty, all-NaN and all--inf segments
+    none = (lens == 0)
+    none[[where["all_nan"], where["all_neg_inf"]]] = True
+    assert np.array_equal((want["argmax"] < 0).all(1), none) and np.array_equal((want["argmax"] < 0).any(1), none)
+    assert np.array_equal(want["argmax"][where["constant"]], np.full(C_, off[where["constant"]]))
+    assert np.isnan(want["avg"][where["inf"]]).all() and np.isnan(want["mean"][where["some_nan"]]).all()
+    assert set(np.unique(_bits(want["max"][where["zeros"]]))) == {0, -2 ** 31}      # both zeros come first somewhere
+    assert np.array_equal(_bits(oracle.sec_mean(x, off)), _bits(want["mean"]))
+    assert np.array_equal(_bits(oracle.sec_min(x, off)), _bits(want["min"]))
+    assert np.array_equal(_bits(oracle.sec_max(x, off)), _bits(want["max"]))
+    mx, am = oracle.roipool_fp(x, off)
+    assert np.array_equal(_bits(mx), _bits(want["max"])) and np.array_equal(am, want["argmax"])
+    assert np.array_equal(_bits(oracle.global_avg_pool_fp(x, off)), _bits(want["avg"]))
+    # backward of the average: every row of proposal p receives g[p] / n, rows outside every proposal stay +0.0
+    g = rng.standard_normal((len(off) - 1, C_)).astype(np.float32)
+    S = x.shape[0]
+    d = np.zeros((S, C_), np.float32)
+    for p in range(len(off) - 1):
+        if lens[p]:
+            d[off[p]:off[p + 1]] = g[p] / np.float32(lens[p])
+    assert np.array_equal(_bits(oracle.global_avg_pool_bp(g, off, S)), _bits(d))
+
+
+@pytest.mark.parametrize("case", mask_label_cases(), ids=lambda c: c["name"])
+def test_mask_label_crafted_ties_vs_serial_python(oracle, case):
+    pidx, off, inst = mask_label_points(case)
+    iou, cls, thr, I = case["iou"], case["inst_cls"], case["thr"], case["I"]
+    ml = np.zeros(pidx.size, bool); mlm = np.zeros(pidx.size, bool)
+    for p in range(iou.shape[0]):                         # cal_iou_and_masklabel.cu:84-103
+        max_iou, max_ind = np.float32(0), 0
+        for k in range(I):
+            if iou[p, k] > max_iou and cls[k] != -1:
+                max_iou, max_ind = iou[p, k], k
+        assert max_ind == case["want"][p] or not case["written"][p]
+        if max_iou >= thr:
+            for i in range(off[p], off[p + 1]):
+                if inst[pidx[i]] == max_ind:
+                    ml[i] = True
+                mlm[i] = True
+    wml, wmlm = mask_label_expected(case)
+    assert np.array_equal(ml, wml) and np.array_equal(mlm, wmlm)       # the rows are what they were crafted to be
+    got = oracle.get_mask_label(pidx, off, inst, cls, iou, -1, float(thr))
+    assert np.array_equal(got[0], ml) and np.array_equal(got[1], mlm)
