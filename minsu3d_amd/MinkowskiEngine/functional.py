@@ -472,17 +472,9 @@ class GatherRowsFn(torch.autograd.Function):
         ctx.n_rows, ctx.max_dup, ctx.sorted = x.size(0), max_dup, None
         be = get_backend()
         if idx.is_cuda and (max_dup is None or max_dup > 2) and hasattr(be, "presort_rows") and be.deterministic():
-            # the backward sums in a fixed order over a stable sort of idx: take the one the loader's prefetch left on the
-            # tensor, or queue it now on the helper thread / side stream
-            cached = getattr(idx, "_ms3d_sorted", None)
-            queued = getattr(idx, "_ms3d_presort", None)
-            if cached is not None and cached[2] == idx._version:
-                ctx.sorted = cached               # the whole entry: it carries the event of the stream that sorted
-            elif queued is not None and queued[1] == idx._version:
-                ctx.sorted = queued[0]            # a second gather over the same index (HAIS: features and mask scores)
-            elif idx.numel() >= GatherRowsFn.PRESORT_MIN_ROWS:
-                ctx.sorted = be.presort_rows(idx)
-                idx._ms3d_presort = (ctx.sorted, idx._version)
+            # the backward sums in a fixed order over a stable sort of idx: the one the loader's prefetch or an earlier
+            # gather over the same index (HAIS: features and mask scores) left, or one queued now on the helper thread
+            ctx.sorted = be.presort_rows(idx, GatherRowsFn.PRESORT_MIN_ROWS)
         return _rows(x, idx)
 
     @staticmethod

@@ -969,9 +969,9 @@ def prefetch_coordinates(coordinates, n_levels, wait_current_stream=True, channe
                 # bench.py's roofline wants the valid-pair count of every table (algorithmic bytes): counted here, on the
                 # prefetch stream, instead of by two torch launches per table inside a sampled (timed) step
                 for t in list(cm._k3.values()) + [x for pair in cm._k2.values() for x in pair]:
-                    t._ms3d_pairs_dev = (t >= 0).sum()
+                    be.table(t).pair_count()
             if point_map is not None and point_map.is_cuda and point_map.dtype == torch.int64 and be.deterministic():
-                cm._aux_tensors = list(be.sorted_rows(point_map))
+                be.sorted_rows(point_map)    # its record orders every consumer behind this stream by itself (backend.SortedIndex)
             ev = torch.cuda.Event()
             ev.record(side)
             return cm, ev
@@ -991,17 +991,14 @@ def _take_prefetched(coordinates):
     cur = torch.cuda.current_stream()
     cur.wait_event(ev)
     # everything was allocated under the side stream and is used (and eventually freed) under this one
-    held = [cm.perm, cm.inv] + list(cm.coords.values()) + list(cm._k3.values()) + [t for pair in cm._k2.values() for t in pair]
-    held.extend(getattr(cm, "_aux_tensors", ()))
+    tables = [t for t in list(cm._k3.values()) + [t for pair in cm._k2.values() for t in pair] if t is not None]
+    held = [cm.perm, cm.inv] + list(cm.coords.values()) + tables
     ext = getattr(cm, "coords_external", None)
     if ext is not None and ext is not coordinates:
         held.append(ext)     # an int32 copy made on the side stream (the caller's coordinates had another dtype)
-    for t in list(held):
-        if t is not None:
-            for pl in (getattr(t, "_ms3d_pairlist", None) or {}).values():      # {rows per tile: (tile_start, entries)}
-                if isinstance(pl, tuple):                                       # (+ "dense": the table's density verdict)
-                    held.extend(x for x in pl if x is not None)
-            held.extend(x for x in (getattr(t, "_ms3d_offsetlist", None) or ()) if x is not None)
+    table = get_backend().table
+    for t in tables:
+        held.extend(table(t).tensors())      # the lists (and the pair count) the prefetch derived from the table
     for t in held:
         if t is not None and t.is_cuda:
             t.record_stream(cur)

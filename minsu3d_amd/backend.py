@@ -8,6 +8,7 @@ nothing in this package imports the oracle.
 """
 import ctypes as C
 import os
+import weakref
 
 import numpy as np
 import torch
@@ -42,15 +43,15 @@ class _HandleTable:
     """What the library knows about a tensor it produced (or was shown) that the reference's tensor-only operator
     signatures (bfs_cluster.h:15-19) have no argument for: an entry per tensor OBJECT -- keyed by id() and guarded by a weak
     reference (an address or an id may be recycled, a live object is not) and by the tensor's version counter (an in-place
-    write voids it).  Round 6: replaces the `_ms3d_capped` / `_ms3d_max_scene` attributes that rode on the
-    tensors themselves; a copy / slice / host round trip of the tensor is simply not in the table and takes the general
-    route (BFS: the validated one; ball query: one device->host read)."""
+    write voids it).  Nothing derived rides on the tensors themselves: the hints of the grouping operators (GRAPHS,
+    SCENE_BOUNDS) and the caches of derived data (TABLES, SORTS) all live here.  A copy / slice / host round trip of the
+    tensor, or one written in place, is simply not in the table and takes the general route (BFS: the validated one;
+    ball query: one device->host read; pair lists and sorts: a rebuild)."""
 
     def __init__(self):
         self._entries = {}
 
     def put(self, tensor, value):
-        import weakref
         key = id(tensor)
         entries = self._entries
 
@@ -69,6 +70,103 @@ class _HandleTable:
 
 GRAPHS = _HandleTable()        # start_len tensor of a ball query -> its `capped` flag (0 / 1)
 SCENE_BOUNDS = _HandleTable()  # batch_offsets tensor -> points of its largest scene
+TABLES = _HandleTable()        # neighbour table of a kernel map -> its TableLists (HipBackend.table)
+SORTS = _HandleTable()         # int64 row index -> its SortedIndex (HipBackend.sorted_rows / presort_rows)
+
+
+class PairList(tuple):
+    """(tile_start, entries) of a tile-compacted pair list -- it unpacks and indexes as that pair -- and `rows`, the tile
+    height it was built for (0 = no list: the kernel walks the table itself)"""
+
+    def __new__(cls, tile_start, entries, rows):
+        self = super().__new__(cls, (tile_start, entries))
+        self.rows = rows
+        return self
+
+
+NO_PAIRLIST = PairList(None, None, 0)
+
+
+class TableLists:
+    """What has been derived from one neighbour table [K, V]; every convolution over the table shares it."""
+
+    def __init__(self, nbr):
+        self._nbr = weakref.ref(nbr)
+        self.pairlists = {}         # rows per tile (32 / 64 / 128) -> PairList
+        self.dense = None           # density verdict (which list a 32 -> 32 layer walks: HipBackend.pairlist); None = undecided
+        self.offsetlist = None      # (kt_start, entries); (None, None) = decided, none wanted; None = not asked yet
+        self._pairs = None
+
+    def pair_count(self):
+        """valid (in, out) pairs of the table as a device scalar: counted once, on the stream of the first caller"""
+        if self._pairs is None:
+            self._pairs = (self._nbr() >= 0).sum()
+        return self._pairs
+
+    def tensors(self):
+        """every device tensor held here: what a consumer on another stream than the builder's has to record_stream"""
+        held = [t for pl in self.pairlists.values() for t in pl]
+        held.extend(t for t in self.offsetlist or () if t is not None)
+        if self._pairs is not None:
+            held.append(self._pairs)
+        return held
+
+
+def table_lists(nbr):
+    """the TableLists of a neighbour table tensor, made on first use (a copy, a slice or a table written in place since
+    gets a fresh, empty one)"""
+    rec = TABLES.get(nbr)
+    if rec is None:
+        rec = TableLists(nbr)
+        TABLES.put(nbr, rec)
+    return rec
+
+
+class SortedIndex:
+    """(keys, order) of the STABLE ascending sort of an int64 row index, with the ordering its consumers need: sorted
+    at once on the caller's stream (an event is recorded behind the sort: it often runs on the prefetch stream), or --
+    queue=True, scheduling only -- on the helper thread and the side stream (the forward of a row gather: ~200 us of
+    radix sort for 800k rows that the backward would otherwise wait for on the critical path)."""
+
+    def __init__(self, idx, queue=False):
+        self._future = self.event = self.stream = None
+        if not queue:
+            self.keys, self.order = torch.sort(idx, stable=True)
+            if idx.is_cuda:
+                self.stream = torch.cuda.current_stream(idx.device)
+                self.event = torch.cuda.Event()
+                self.event.record(self.stream)
+            return
+        ready = torch.cuda.Event()
+        ready.record(torch.cuda.current_stream(idx.device))
+        side = self.stream = side_stream(idx.device)
+        self._idx = weakref.ref(idx)
+
+        def job():
+            with torch.cuda.stream(side), torch.no_grad():
+                side.wait_event(ready)
+                idx.record_stream(side)      # the sort may still be reading it when the last reference on the caller's side dies
+                keys, order = torch.sort(idx, stable=True)
+                done = torch.cuda.Event()
+                done.record(side)
+                return keys, order, done
+        self._future = worker().submit(job)
+
+    def on_current_stream(self):
+        """-> (keys, order), ordered behind the sort on the CURRENT stream"""
+        queued = self._future
+        if queued is not None:
+            self.keys, self.order, self.event = queued.result()
+            self._future = None
+            idx = self._idx()
+            if idx is not None:
+                idx.record_stream(self.stream)
+        if self.event is not None:
+            cur = torch.cuda.current_stream(self.keys.device)
+            if cur != self.stream:
+                cur.wait_event(self.event)
+                self.keys.record_stream(cur); self.order.record_stream(cur)
+        return self.keys, self.order
 
 
 class _Workspace:
@@ -417,61 +515,29 @@ class HipBackend:
         return out
 
     def sorted_rows(self, idx):
-        """(keys, order) of a STABLE ascending sort of an int64 row index, cached on the tensor: what the fixed-order
-        scatter-add needs.  Callers that know the index ahead of its backward (the loader's voxel_point_map) call this
-        early, off the critical path; torch's radix sort (rocPRIM) is plumbing, not a hot kernel."""
-        return self._use_sorted(self._sorted_cache(idx))
+        """(keys, order) of a STABLE ascending sort of an int64 row index, kept in SORTS: what the fixed-order scatter-add
+        needs.  Callers that know the index ahead of its backward (the loader's voxel_point_map) call this early, off the
+        critical path; torch's radix sort (rocPRIM) is plumbing, not a hot kernel."""
+        rec = SORTS.get(idx)
+        if rec is None:
+            rec = SortedIndex(idx)
+            SORTS.put(idx, rec)
+        return rec.on_current_stream()
 
-    def _sorted_cache(self, idx):
-        """the cache entry (keys, order, version of idx, event recorded behind the sort, the stream it ran on): the sort is
-        often queued on the prefetch stream, so the entry carries its own ordering instead of relying on an unrelated
-        wait of the consumer"""
-        cached = getattr(idx, "_ms3d_sorted", None)
-        if cached is None or cached[2] != idx._version:
-            keys, order = torch.sort(idx, stable=True)
-            ev, st = None, None
-            if idx.is_cuda:
-                st = torch.cuda.current_stream(idx.device)
-                ev = torch.cuda.Event()
-                ev.record(st)
-            cached = idx._ms3d_sorted = (keys, order, idx._version, ev, st)
-        return cached
-
-    @staticmethod
-    def _use_sorted(cached):
-        """(keys, order) of a cache entry, ordered behind its sort on the CURRENT stream"""
-        keys, order = cached[0], cached[1]
-        if len(cached) >= 5 and cached[3] is not None:
-            cur = torch.cuda.current_stream(keys.device)
-            if cur != cached[4]:
-                cur.wait_event(cached[3])
-                keys.record_stream(cur); order.record_stream(cur)
-        return keys, order
-
-    def presort_rows(self, idx):
-        """Scheduling only: the stable sort of `idx` queued on the helper thread and the side stream NOW (the forward of
-        a row gather: ~200 us of radix sort for 800k rows that the backward would otherwise wait for on the critical
-        path) -> a handle for scatter_add_rows(sorted_=...)"""
-        main = torch.cuda.current_stream(idx.device)
-        ready = torch.cuda.Event()
-        ready.record(main)
-        side = side_stream(idx.device)
-
-        def job():
-            with torch.cuda.stream(side), torch.no_grad():
-                side.wait_event(ready)
-                idx.record_stream(side)      # the sort may still be reading it when the last reference on the caller's side dies
-                keys, order = torch.sort(idx, stable=True)
-                done = torch.cuda.Event()
-                done.record(side)
-                return keys, order, done
-        return (worker().submit(job), side)
+    def presort_rows(self, idx, min_rows):
+        """the forward of a row gather over `idx`: the SortedIndex that is already there (finished or queued), else one
+        queued NOW when the index has min_rows entries or more, else None -> a handle for scatter_add_rows(sorted_=...)"""
+        rec = SORTS.get(idx)
+        if rec is None and idx.numel() >= min_rows:
+            rec = SortedIndex(idx, queue=True)
+            SORTS.put(idx, rec)
+        return rec
 
     def scatter_add_rows(self, src, idx, n_rows, max_dup=None, sorted_=None):
         """dst[idx[i]] += src[i] -> dst [n_rows, C], bit-reproducible: rows that may collect more than two sources are
         summed in ascending source order over a stable sort of the index (ms3d_scatter_add_rows_sorted); max_dup <= 2
         (the caller knows no row has more than two sources: a + b = b + a exactly) keeps the one-launch float atomics,
-        as does MS3D_DETERMINISTIC=0.  sorted_: (keys, order) of that sort, or a presort_rows handle."""
+        as does MS3D_DETERMINISTIC=0.  sorted_: the SortedIndex of idx (presort_rows)."""
         src = self._dev(src); idx = self._dev(idx)
         assert idx.dtype == torch.int64
         dst = torch.zeros((n_rows, src.size(1)), dtype=torch.float32, device=src.device)
@@ -479,15 +545,7 @@ class HipBackend:
             _lib.check(self.lib.ms3d_scatter_add_rows(_lib.ptr(src), _lib.ptr(idx), C.c_long(src.size(0)), int(src.size(1)),
                                                       _lib.ptr(dst), _lib.stream_handle()), "ms3d_scatter_add_rows")
             return dst
-        if sorted_ is not None and not torch.is_tensor(sorted_[0]):
-            keys, order, done = sorted_[0].result()
-            cur = torch.cuda.current_stream(src.device)
-            cur.wait_event(done)
-            keys.record_stream(cur); order.record_stream(cur); idx.record_stream(sorted_[1])
-        elif sorted_ is not None:
-            keys, order = self._use_sorted(sorted_)
-        else:
-            keys, order = self.sorted_rows(idx)
+        keys, order = sorted_.on_current_stream() if sorted_ is not None else self.sorted_rows(idx)
         _lib.check(self.lib.ms3d_scatter_add_rows_sorted(_lib.ptr(src), _lib.ptr(keys), _lib.ptr(order),
                                                          C.c_long(src.size(0)), int(src.size(1)), _lib.ptr(dst),
                                                          _lib.stream_handle()), "ms3d_scatter_add_rows_sorted")
@@ -614,10 +672,7 @@ class KernelTimer:
         """kind: 'fwd' (forward / backward-data, the same kernels) or 'wgrad' -> (ev_start, ev_stop) or None"""
         if not self.sampling:
             return None
-        pairs = getattr(nbr, "_ms3d_pairs_dev", None)   # valid (in, out) pairs of the table: counted on the device, read
-        if pairs is None:                                # back only in summary() (no host sync inside a step)
-            pairs = (nbr >= 0).sum()
-            nbr._ms3d_pairs_dev = pairs
+        pairs = table_lists(nbr).pair_count()   # counted on the device, read back only in summary() (no host sync inside a step)
         ev = (self._event(), self._event())
         self.records.append((("spconv_" + kind, K, cin, cout, rows), ev[0], ev[1],
                              (pairs, (cin + cout) * 4 + 8, K * cin * cout * 4), 2 * cin * cout))
@@ -631,11 +686,7 @@ class KernelTimer:
         ev = (self._event(), self._event())
         parts = []
         for K, cin, cout, rows, nbr in layers:
-            pairs = getattr(nbr, "_ms3d_pairs_dev", None)
-            if pairs is None:
-                pairs = (nbr >= 0).sum()
-                nbr._ms3d_pairs_dev = pairs
-            parts.append((pairs, (cin + cout) * 4 + 8, K * cin * cout * 4, 2 * cin * cout))
+            parts.append((table_lists(nbr).pair_count(), (cin + cout) * 4 + 8, K * cin * cout * 4, 2 * cin * cout))
         K, cin, cout, rows, _ = layers[0]
         self.records.append((("spconv_" + kind, K, cin, cout, rows, len(layers)), ev[0], ev[1], parts, None))
         return ev
@@ -1429,23 +1480,23 @@ class _HipEngine:
             self._ident[(n, device)] = t
         return t
 
+    table = staticmethod(table_lists)
+
     def pairlist(self, nbr, K, vout, cin=16, cout=16):
-        """tile-compacted pair list of an offset-major table for a convolution of this shape, built on first use and cached
-        on the table tensor (every convolution of a level shares it) -> (tile_start, entries) or (None, None) when the
-        shape takes a kernel that walks the table itself.  Layers with more than 32 channels on a side want 128-row
+        """tile-compacted pair list of an offset-major table for a convolution of this shape, built on first use and kept in
+        the table's record (every convolution of a level shares it) -> PairList (tile_start, entries), or (None, None)
+        when the shape takes a kernel that walks the table itself.  Layers with more than 32 channels on a side want 128-row
         tiles, the others 64-row tiles (ms3d_spconv_pairlist_rows)."""
         rows = self._geom("ms3d_spconv_pairlist_rows", vout, K, cin, cout)
         if rows == 0:
-            return (None, None)
-        cache = getattr(nbr, "_ms3d_pairlist", None)
-        if cache is None:
-            cache = nbr._ms3d_pairlist = {}
+            return NO_PAIRLIST
+        rec = table_lists(nbr)
         dense_rows = self._geom("ms3d_spconv_pairlist_rows_dense", vout, K, cin, cout)
         if dense_rows != rows:
             # a layer shape with a second kernel variant for DENSE tables (32 -> 32: both column blocks per wave on 32-row
             # tiles).  The table's pair count decides, once per table: a 32-row tile of a full-resolution level (5.5 of 27
             # neighbours) pads 6.5 pairs per offset to 16 and loses 11 %, at 10 neighbours the variant saves 10-12 %.
-            dense = cache.get("dense")
+            dense = rec.dense
             if dense is None:
                 import threading
                 mode = os.environ.get("MS3D_PL_NARROW", "1")
@@ -1455,16 +1506,13 @@ class _HipEngine:
                     # one device->host read per table -- ONLY on the input pipeline's thread (ME.prefetch_coordinates builds
                     # the lists there, on its own stream): on the calling thread the read would drain the queue the
                     # interpreter has run ahead of, which costs more than the variant saves.  (3 = read wherever it is asked)
-                    pairs = getattr(nbr, "_ms3d_pairs_dev", None)
-                    if pairs is None:
-                        pairs = nbr._ms3d_pairs_dev = (nbr >= 0).sum()
-                    dense = float(pairs) >= float(os.environ.get("MS3D_PL_NARROW_DENSITY", "8.0")) * max(int(vout), 1)
+                    dense = float(rec.pair_count()) >= float(os.environ.get("MS3D_PL_NARROW_DENSITY", "8.0")) * max(int(vout), 1)
                 else:
                     dense = False          # a table built on the calling thread: the 64-row list (deterministic per configuration)
-                cache["dense"] = dense
+                rec.dense = dense
             if dense:
                 rows = dense_rows
-        pl = cache.get(rows)
+        pl = rec.pairlists.get(rows)
         if pl is None:
             self.lib.ms3d_kmap_pairlist_capacity_rows.restype = C.c_size_t
             cap = self.lib.ms3d_kmap_pairlist_capacity_rows(int(K), int(vout), rows)
@@ -1475,17 +1523,14 @@ class _HipEngine:
             _lib.check(self.lib.ms3d_kmap_pairlist_build_rows(_lib.ptr(nbr), int(K), int(vout), rows, _lib.ptr(tile_start),
                                                               _lib.ptr(entries), _lib.ptr(ws), C.c_size_t(ws.numel()),
                                                               _lib.stream_handle()), "ms3d_kmap_pairlist_build_rows")
-            pl = cache[rows] = (tile_start, entries)
+            pl = rec.pairlists[rows] = PairList(tile_start, entries, rows)
         return pl
 
-    def _pl_rows(self, pl):
-        """rows per tile of a pair list (0 = no list): what ms3d_spconv_partial_blocks wants to know about it"""
-        return int(self.lib.ms3d_kmap_pairlist_rows_of(_lib.ptr(pl[0]))) if pl[0] is not None else 0
-
     def offsetlist(self, nbr, K, vout):
-        """offset-major pair list of a table for the backward-weight kernel, cached on the table tensor
+        """offset-major pair list of a table for the backward-weight kernel, kept in the table's record
         -> (kt_start, entries) or (None, None) for small levels"""
-        ol = getattr(nbr, "_ms3d_offsetlist", None)
+        rec = table_lists(nbr)
+        ol = rec.offsetlist
         if ol is None:
             ol = (None, None)
             if self.lib.ms3d_kmap_pairlist_wanted(int(K), int(vout)):
@@ -1500,7 +1545,7 @@ class _HipEngine:
                                                                _lib.ptr(entries), _lib.ptr(ws), C.c_size_t(ws.numel()),
                                                                _lib.stream_handle()), "ms3d_kmap_offsetlist_build")
                 ol = (kt_start, entries)
-            nbr._ms3d_offsetlist = ol
+            rec.offsetlist = ol
         return ol
 
     def conv_forward(self, x, wf, nbr, vout, K, cin, cout, pre=None, pre_relu=False, residual=None, bn_bwd=None,
@@ -1515,7 +1560,7 @@ class _HipEngine:
         bnargs = [None] * 5
         pl = self.pairlist(nbr, K, vout, cin, cout)
         if bn_bwd is not None or out_stats:
-            nparts = self.lib.ms3d_spconv_partial_blocks(int(vout), int(K), int(cin), int(cout), self._pl_rows(pl))
+            nparts = self.lib.ms3d_spconv_partial_blocks(int(vout), int(K), int(cin), int(cout), pl.rows)
             partial = torch.empty((nparts, 2, cout), dtype=torch.float32, device=x.device)
         if bn_bwd is not None:
             bnargs = [_f32(t) for t in bn_bwd]
@@ -1666,7 +1711,7 @@ class _HipEngine:
         dev = x.device
         wf_buf = wf_ready if wf_ready is not None else torch.empty(self.wf_floats(K, cin, cout), dtype=torch.float32, device=dev)
         pl = self.pairlist(nbr_fwd, K, vout, cin, cout)
-        nparts = self._geom("ms3d_spconv_partial_blocks", vout, K, cin, cout, self._pl_rows(pl)) if want_stats else 0
+        nparts = self._geom("ms3d_spconv_partial_blocks", vout, K, cin, cout, pl.rows) if want_stats else 0
         ps, pb = (pre if pre is not None else (None, None))
         timer = self.kernel_timer
         tok = timer.conv("fwd", K, cin, cout, nbr_fwd, vout) if timer is not None else None
@@ -1698,7 +1743,7 @@ class _HipEngine:
                 or os.environ.get("MS3D_RESBLOCK_EXT", "1") == "0"):
             return None
         pl = self.pairlist(nbr, 27, V, c, c)
-        nparts = self._geom("ms3d_spconv_partial_blocks", V, 27, c, c, self._pl_rows(pl))
+        nparts = self._geom("ms3d_spconv_partial_blocks", V, 27, c, c, pl.rows)
         y1, y2, st2, o0, o1 = ext.res_block_forward(
             x, stats_in, wf1, wf2, nbr, V, c, pl[0], pl[1], nparts, bool(want_stats), _f32(g0), _f32(b0), bn0.running_mean,
             bn0.running_var, bn0.eps, bn0.momentum, _f32(g1), _f32(b1), bn1.running_mean, bn1.running_var, bn1.eps, bn1.momentum,

@@ -1,4 +1,5 @@
-"""CPU: host-side logic added in round 6 -- the handle table that replaced the tensor-attribute hints, the stream plan of a
+"""CPU: host-side logic added in round 6 -- the handle table that replaced the tensor-attribute hints (and the records of
+derived data kept in it since: a neighbour table's lists, the stable sort of a row index), the stream plan of a
 rank, and the launch-geometry queries of the C library that Python sizes buffers from (no compute calls: no GPU here)."""
 import gc
 import os
@@ -27,6 +28,71 @@ def test_handle_table_follows_object_identity_and_version():
     assert not t._entries                       # the entry dies with the tensor (ids are recycled, objects are not)
     b = torch.zeros(8, dtype=torch.int32)
     assert t.get(b) is None
+
+
+def test_table_record_follows_the_table_tensor():
+    """HipBackend.table: one TableLists per neighbour-table OBJECT; copies, views and a table written in place start empty"""
+    from minsu3d_amd import backend
+    from minsu3d_amd.backend import HipBackend, PairList
+    be = HipBackend()
+    gc.collect()
+    before = set(backend.TABLES._entries)
+    t = torch.arange(-4, 50, dtype=torch.int32).view(27, 2)
+    rec = be.table(t)
+    assert be.table(t) is rec
+    assert rec.pairlists == {} and rec.dense is None and rec.offsetlist is None and rec.tensors() == []
+    # filled by hand: tensors() lists every tensor put in, and nothing else
+    put = [torch.zeros(n, dtype=torch.int32) for n in (3, 4, 5, 6, 7, 8)]
+    rec.pairlists[64] = PairList(put[0], put[1], 64)
+    rec.pairlists[32] = PairList(put[2], put[3], 32)
+    rec.dense = True
+    assert [id(x) for x in rec.tensors()] == [id(x) for x in put[:4]]
+    rec.offsetlist = (None, None)                       # decided, none wanted: not "not asked yet", and nothing to hold
+    assert len(rec.tensors()) == 4
+    rec.offsetlist = (put[4], put[5])
+    count = rec.pair_count()
+    assert int(count) == 50 and rec.pair_count() is count
+    assert sorted(id(x) for x in rec.tensors()) == sorted(id(x) for x in put + [count])
+    pl = rec.pairlists[32]
+    tile_start, entries = pl
+    assert tile_start is put[2] and pl[1] is put[3] and pl.rows == 32 and pl == (put[2], put[3])
+    assert tuple(backend.NO_PAIRLIST) == (None, None) and backend.NO_PAIRLIST.rows == 0
+    for other in (t.clone(), t[:3], t.view(2, 27)):
+        r = be.table(other)
+        assert r is not rec and r.tensors() == [] and r.dense is None
+    assert be.table(t) is rec
+    t.add_(0)                                           # an in-place write voids the record
+    fresh = be.table(t)
+    assert fresh is not rec and fresh.tensors() == [] and be.table(t) is fresh
+    del t, other, r                                     # (a view keeps its base alive)
+    gc.collect()
+    assert set(backend.TABLES._entries) <= before       # the records die with their tensors
+
+
+def test_sorted_rows_is_one_record_per_index_tensor():
+    from minsu3d_amd import backend
+    from minsu3d_amd.backend import HipBackend
+    be = HipBackend()
+    gc.collect()
+    before = set(backend.SORTS._entries)
+    g = torch.Generator().manual_seed(3)
+    idx = torch.randint(0, 40, (500,), generator=g)                 # many repeats: only a stable sort gives this order
+    keys, order = be.sorted_rows(idx)
+    wk, wo = torch.sort(idx, stable=True)
+    assert torch.equal(keys, wk) and torch.equal(order, wo)
+    rec = backend.SORTS.get(idx)
+    assert rec is not None and rec.on_current_stream()[0] is keys
+    k2, o2 = be.sorted_rows(idx)
+    assert k2 is keys and o2 is order and backend.SORTS.get(idx) is rec     # served from the same record
+    assert be.presort_rows(idx, 1 << 16) is rec                             # a gather's forward finds it as well
+    assert backend.SORTS.get(idx.clone()) is None and be.presort_rows(idx.clone(), 1 << 16) is None
+    idx[0] = 39; idx[499] = 0                                       # in place: recomputed, and follows the new contents
+    k3, o3 = be.sorted_rows(idx)
+    wk, wo = torch.sort(idx, stable=True)
+    assert k3 is not keys and torch.equal(k3, wk) and torch.equal(o3, wo) and backend.SORTS.get(idx) is not rec
+    del idx
+    gc.collect()
+    assert set(backend.SORTS._entries) <= before                    # the entry dies with the tensor
 
 
 def test_stream_plan_keeps_a_data_parallel_rank_inside_four_hardware_queues(monkeypatch):
