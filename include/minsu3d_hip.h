@@ -384,6 +384,46 @@ int ms3d_chconv_wgrad_rows_per_part(void);
 int ms3d_chconv_wgrad_parts(int Vout);
 size_t ms3d_chconv_wgrad_ws_floats(int Vout, int K, int C);
 
+/* ---- local multi-head attention over a kernel map (csrc/kattn.hip; float32 throughout).  q [Vout][C], k / v [Vin][C] row-
+ * contiguous, C = H * D (H heads of D channels); nbr [K][Vout] the forward table, nbr_inv [K][Vin] its inverse (int32, -1 =
+ * none; the offset index is NOT mirrored, as in ms3d_chconv_forward's backward-data); rel_bias [K][H] or NULL; i = nbr[kk][o]:
+ *   s[o][kk][h] = scale * sum_d q[o][hD+d] * k[i][hD+d] + rel_bias[kk][h]        over the PRESENT kk (i >= 0)
+ *   p[o][kk][h] = exp(s - m[o][h]) / sum_kk' exp(s' - m[o][h]),  m = the maximum over the present kk (always subtracted)
+ *   out[o][hD+d] = sum_kk p[o][kk][h] * v[i][hD+d];   lse[o][h] = m + log sum exp(s - m)
+ * A row without a present input gives out = 0 and lse = 0 and contributes to no gradient.
+ * forward: out [Vout][C] and lse [Vout][H], one online-softmax sweep over ascending kk; rows are read by index where they lie,
+ * nothing of size [pairs, .] is written.
+ * backward_q walks the forward table: p recomputed from lse, ds = p * (dout[o][h][:] . v[i][h][:] - sum_d dout * out), evaluated
+ * as ds = p * (e - delta[o][h]) with e = sum_d dout[o][hD+d] * (v[i][hD+d] - out[o][hD+d]) and delta[o][h] = sum_kk p * e: the
+ * difference is taken per channel before the sum, so a row whose weight sits on one input (out = that v) does not subtract
+ * two nearly equal dot products, and delta -- zero for an exactly rounded out -- takes back what the float32 rounding of the
+ * saved out costs; the ds of a row sum to zero.  delta [Vout][H] is written for backward_kv.
+ * dq[o][h][:] = scale * sum_kk ds * k[i][h][:]; dbias[kk][h] = sum_o ds in two stages without atomics: one [K][H] partial per run of ms3d_kattn_rows_per_part() consecutive output rows (a constant of the
+ * library, independent of the device, so the order of the sum is too), then the partials added in ascending part order.
+ * partial_ws: ms3d_kattn_dbias_ws_floats(Vout, K, H) = ms3d_kattn_dbias_parts(Vout) * K * H floats, parts = ceil(Vout /
+ * rows_per_part) (pure host arithmetic; 0 for Vout <= 0), read only when dbias != NULL.  dq and dbias may each be NULL
+ * (skipped; both NULL: delta alone); dbias != NULL needs rel_bias and partial_ws.
+ * backward_kv gathers through nbr_inv: for o = nbr_inv[kk][i] >= 0, dv[i][h][:] += p * dout[o][h][:] and dk[i][h][:] += scale *
+ * ds * q[o][h][:], p and ds recomputed from q[o], k[i], v[i], rel_bias[kk][h], lse[o][h], the row out[o] and delta[o][h]; dk or
+ * dv may be NULL (not both).
+ * Every sum runs in one fixed order that depends on the shapes only; no atomics; the same bytes on every run, in all three.
+ * 16-byte row accesses when D % 4 == 0 and every row pointer is 16-byte aligned, a scalar path otherwise; 64-bit offsets.
+ * Limits: 1 <= K <= 254, H >= 1, 1 <= D <= 128; H * D is bounded only by int (H * D and K * H <= 2^31 - 1), far past the
+ * H * D <= 1024 of practical layers.  Outside them, or a NULL pointer that would be read or written: MS3D_E_UNSUPPORTED; a short
+ * workspace: MS3D_E_WORKSPACE; both decided on the host before any launch.  Vout <= 0 (Vin <= 0 in backward_kv) with a served
+ * shape: 0, nothing is launched, no pointer is looked at (dbias is not written). */
+int ms3d_kattn_forward(const float *q, const float *k, const float *v, const float *rel_bias, const int *nbr, int Vout, int K,
+                       int H, int D, float scale, float *out, float *lse, ms3d_stream_t stream);
+int ms3d_kattn_backward_q(const float *q, const float *k, const float *v, const float *rel_bias, const int *nbr,
+                          const float *out, const float *lse, const float *dout, int Vout, int K, int H, int D, float scale,
+                          float *dq, float *dbias, float *delta, float *partial_ws, size_t ws_floats, ms3d_stream_t stream);
+int ms3d_kattn_backward_kv(const float *q, const float *k, const float *v, const float *rel_bias, const int *nbr_inv,
+                           const float *out, const float *lse, const float *delta, const float *dout, int Vin, int K, int H,
+                           int D, float scale, float *dk, float *dv, ms3d_stream_t stream);
+int ms3d_kattn_rows_per_part(void);
+int ms3d_kattn_dbias_parts(int Vout);
+size_t ms3d_kattn_dbias_ws_floats(int Vout, int K, int H);
+
 /* ---- instance normalisation: per batch index (segment) and channel (csrc/inorm.hip; float32 rows and parameters, any C >= 1;
  * every sum, the statistics mean / invstd (DOUBLE [B, C]) and the arithmetic of the row passes are float64, rounded once at the
  * store: with few rows in a segment dx is a difference of nearly equal terms that float32 statistics cannot resolve; a lane takes four

@@ -137,6 +137,29 @@ Labels and batches in -- what a segmentation, completion or detection script cal
     ValueError.  batched_coordinates floors float input and numbers the samples by their position in the list, empty
     samples included; sparse_collate hands a list of labels that are not arrays back as it is.
 
+Local attention over a kernel map -- the block of window / neighbourhood transformers (engine extras: MinkowskiEngine has
+no such layer, and nothing here is pinned to it):
+
+    kernel_attention(q, k, v, num_heads, rel_bias=None, scale=None, kernel_size=3, stride=1, dilation=1,
+    kernel_generator=None) -> a SparseTensor on q's coordinate set;
+    MinkowskiKernelAttention(in_channels, num_heads, kernel_size=3, dilation=1, qkv_bias=True, rel_pos_bias=True,
+    dimension=3, kernel_generator=None): proj(kernel_attention(q, k, v)) of qkv(x) on the tensor's own set; parameters
+    qkv.weight, qkv.bias, proj.weight, proj.bias (nn.Linear) and rel_bias (K, num_heads), zero-initialised
+
+    out[o, h, :] = sum_kk softmax_kk(scale * <q[o, h], k[i, h]> + rel_bias[kk, h]) v[i, h, :] over the inputs i that the
+    kernel's offsets reach from row o and that are PRESENT (the pairs of CoordinateManager.kernel_map, the offsets in its
+    order); C = num_heads * D, scale = D ** -0.5 unless given; a row that reaches no input is zero.  k and v share a
+    coordinate set of tensor stride ts; q sits on the same manager at ts * stride or on a set of another manager at that stride
+    (target_map); the geometries and their refusals are the convolutions', regions included.  csrc/kattn.hip: three float32
+    gather kernels over the layers' own tables -- forward (one online-softmax sweep, the maximum always subtracted, saves the
+    log-sum-exp), backward for q and rel_bias along the forward table, backward for k and v through the inverse table; the
+    probabilities are recomputed, nothing of the size of the pair list is ever stored; no atomics, every sum in an order
+    fixed by the shapes (the rel_bias gradient: one partial per run of ms3d_kattn_rows_per_part() rows, added in order), the
+    same bytes on every run.  K <= 254, D <= 128.  Frozen k and v skip the kv pass; a frozen q and rel_bias skip the q pass when k and v
+    are frozen too (the kv pass reads a per-row residual the q pass leaves).
+    Out of scope: attention dropout, masks, a value head dimension different from D, float16 / bfloat16 rows, gradients
+    through the coordinates.  Outside prepare_conv_weights: the block is not a dense-weight convolution.
+
 Not supported (each raises NotImplementedError naming it): `axis_types` of a KernelGenerator, a region of more than 254
 offsets, a dense grid of more than 2^31 - 1 cells, to_sparse of a tensor
 that is not 5-D ([B, C, X, Y, Z]: dimension 3) or in a format other than "BCXXX" / "BXXXC", dense() on a per-axis tensor stride, strides other than 1 and 2, a generative layer at stride 2 on an odd
@@ -164,6 +187,7 @@ from .modules import (MinkowskiConvolution, MinkowskiConvolutionTranspose, Minko
                       MinkowskiBroadcastConcatenation, MinkowskiBroadcast, MinkowskiSigmoid,
                       MinkowskiPoolingTranspose, MinkowskiInterpolation, MinkowskiChannelwiseConvolution,
                       MinkowskiInstanceNorm, MinkowskiStableInstanceNorm,
+                      MinkowskiKernelAttention, kernel_attention,
                       MinkowskiToSparseTensor, MinkowskiToDenseTensor, MinkowskiToFeature,
                       MinkowskiELU, MinkowskiLeakyReLU, MinkowskiPReLU, MinkowskiSELU, MinkowskiCELU, MinkowskiGELU,
                       MinkowskiSiLU, MinkowskiTanh, MinkowskiSoftplus, MinkowskiHardswish, MinkowskiHardtanh,

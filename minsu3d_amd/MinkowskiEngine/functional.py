@@ -594,6 +594,49 @@ def channelwise_conv(x, w, bias, nbr_fwd, nbr_inv, vin, vout, K):
     return ChannelwiseConvFn.apply(x, w, bias, nbr_fwd, nbr_inv, vin, vout, K)
 
 
+class KernelAttentionFn(torch.autograd.Function):
+    """out[o, h, :] = sum_kk softmax_kk(scale * <q[o, h], k[i, h]> + rel_bias[kk, h]) * v[i, h, :] over the present inputs
+    i = nbr_fwd[kk][o] (csrc/kattn.hip; float32, C = num_heads * D; a row without input is zero).  Saves q, k, v, out and the
+    log-sum-exp lse [vout, H]; the backward recomputes the probabilities from lse.  The q pass walks the forward table (dq,
+    dbias in two stages, and delta [vout, H], the residual the kv pass subtracts), the kv pass gathers through the inverse
+    table: no atomics, the same bytes on every run.  Frozen q and bias skip the q pass unless the kv pass needs its delta
+    (the pass then stores nothing else); frozen k and v skip the kv pass."""
+
+    @staticmethod
+    def forward(ctx, q, k, v, rel_bias, nbr_fwd, nbr_inv, vin, vout, K, num_heads, scale):
+        be = get_backend()
+        if not hasattr(be, "kattn_forward"):
+            raise NotImplementedError("kernel-map attention needs the HIP backend (ms3d_kattn_forward)")
+        q, k, v = q.contiguous(), k.contiguous(), v.contiguous()
+        out, lse = be.kattn_forward(q, k, v, rel_bias, nbr_fwd, vout, K, num_heads, scale)
+        ctx.save_for_backward(q, k, v, rel_bias, out, lse)
+        ctx.geom = (nbr_fwd, nbr_inv, vin, vout, K, num_heads, scale)
+        return out
+
+    @staticmethod
+    def backward(ctx, dout):
+        q, k, v, rel_bias, out, lse = ctx.saved_tensors
+        nbr_fwd, nbr_inv, vin, vout, K, H, scale = ctx.geom
+        need_q, need_k, need_v = ctx.needs_input_grad[:3]
+        need_b = rel_bias is not None and ctx.needs_input_grad[3]
+        be = get_backend()
+        dout = dout.contiguous()
+        dq = dk = dv = db = None
+        if need_q or need_b or need_k or need_v:
+            dq, db, delta = be.kattn_backward_q(q, k, v, rel_bias, nbr_fwd, out, lse, dout, vout, K, H, scale,
+                                                need_dq=need_q, need_dbias=need_b)
+            if need_k or need_v:
+                dk, dv = be.kattn_backward_kv(q, k, v, rel_bias, nbr_inv, out, lse, delta, dout, vin, K, H, scale,
+                                              need_dk=need_k, need_dv=need_v)
+        return dq, dk, dv, db, None, None, None, None, None, None, None
+
+
+def kernel_attention_rows(q, k, v, rel_bias, nbr_fwd, nbr_inv, vin, vout, K, num_heads, scale):
+    """attention of the rows q [vout, C] over k / v [vin, C] through the tables of a kernel map (rows as the managers hold
+    them) -> out [vout, C]"""
+    return KernelAttentionFn.apply(q, k, v, rel_bias, nbr_fwd, nbr_inv, vin, vout, K, num_heads, scale)
+
+
 class InstanceNormFn(torch.autograd.Function):
     """y[r, c] = (x[r, c] - mean[s, c]) * invstd[s, c] * weight[c] + bias[c] with the statistics of the row's segment s (its
     batch index) and the biased variance (csrc/inorm.hip).  group = (order, seg_start, seg_of_row): CoordinateManager.

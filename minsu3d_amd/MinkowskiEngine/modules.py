@@ -422,6 +422,96 @@ class MinkowskiChannelwiseConvolution(nn.Module):
                 f"bias={self.bias is not None}" + _region_name(self.region))
 
 
+def kernel_attention(q, k, v, num_heads, rel_bias=None, scale=None, kernel_size=3, stride=1, dilation=1, kernel_generator=None):
+    """Local multi-head attention over a kernel map (an engine extra: MinkowskiEngine has no such layer).  Row o of q attends
+    to the rows of k / v that the kernel's offsets reach from its coordinate -- the inputs a convolution of the same geometry
+    would sum for it --:  out[o, h, :] = sum_kk softmax_kk(scale * <q[o, h], k[i, h]> + rel_bias[kk, h]) * v[i, h, :], the
+    softmax over the inputs PRESENT; a row that reaches none is zero.  q, k, v: SparseTensors of the same channel count C =
+    num_heads * D; k and v on one coordinate set of tensor stride ts; q on the same manager at ts * stride (the layer's own
+    output set: kernel_map_tables / kernel_map_inverse), or on any set of another manager at that stride (target_map).
+    rel_bias: a float32 tensor (K, num_heads) in the kernel's offset order, or None; scale defaults to D ** -0.5.
+    -> a SparseTensor on q's coordinate set.  A pending BatchNorm / ReLU on q, k or v is materialised first.  float32 HIP gather
+    kernels without atomics (csrc/kattn.hip): forward and every gradient are the same bytes on every run.
+    Not offered: attention dropout, masks, a value head dimension other than D, float16 / bfloat16 rows, gradients through the
+    coordinates."""
+    # (the default kernel size beside a generator is "not given", as in CoordinateManager.kernel_map(in_key, out_key, ...))
+    given_ks = -1 if kernel_generator is not None and kernel_size == 3 else kernel_size
+    kernel_size, stride, dilation, region, _, K = _layer_geometry("kernel_attention", given_ks, stride, dilation,
+                                                                  kernel_generator)
+    cm, ts = k.coordinate_manager, k.tensor_stride
+    if v.coordinate_manager is not cm or v.tensor_stride != ts:
+        raise ValueError("kernel_attention: k and v must be on the same coordinate set (one manager, one tensor stride)")
+    C = k._F.size(1)
+    if q._F.size(1) != C or v._F.size(1) != C:
+        raise ValueError(f"kernel_attention: q, k and v must have the same number of channels, got {q._F.size(1)}, {C}, "
+                         f"{v._F.size(1)}")
+    if not isinstance(num_heads, int) or num_heads < 1 or C % num_heads != 0:
+        raise ValueError(f"kernel_attention: {C} channels do not divide into num_heads={num_heads}")
+    if q.tensor_stride != ts * stride:
+        raise ValueError(f"kernel_attention: q is at tensor stride {q.tensor_stride}, k and v at {ts}: stride={stride} needs q "
+                         f"at {ts * stride}")
+    if rel_bias is not None and tuple(rel_bias.shape) != (K, num_heads):
+        raise ValueError(f"kernel_attention: rel_bias must have shape (K, num_heads) = ({K}, {num_heads}), got "
+                         f"{tuple(rel_bias.shape)}")
+    if scale is None:
+        scale = (C // num_heads) ** -0.5
+    geom = (kernel_size, stride, dilation)
+    if q.coordinate_manager is cm:
+        nbr_fwd, _, vin, vout, K, _, _ = cm.kernel_map_tables(ts, *geom, region=region)
+        nbr_inv = cm.kernel_map_inverse(ts, *geom, region=region)
+    else:
+        nbr_fwd, nbr_inv, vin, vout, K = cm.target_map(ts, q.coordinate_map_key, *geom, region=region)
+    rows = q._raw()
+    y = rows[:0] if vout == 0 else Fn.kernel_attention_rows(rows, k._raw(), v._raw(), rel_bias, nbr_fwd, nbr_inv, vin, vout, K,
+                                                            num_heads, float(scale))
+    return q._like(y)
+
+
+class MinkowskiKernelAttention(nn.Module):
+    """The stride-1 self-attention block on the tensor's own coordinate set (an engine extra: MinkowskiEngine has no such
+    layer): forward(x) = proj(kernel_attention(q, k, v)) with (q, k, v) = the three C-wide column blocks of qkv(x).  `qkv` is
+    nn.Linear(C, 3C) (bias when qkv_bias), `proj` nn.Linear(C, C), `rel_bias` a (K, num_heads) parameter initialised to zero --
+    one learned bias per kernel offset and head, absent with rel_pos_bias=False; scale = (C / num_heads) ** -0.5.  The
+    geometries are the stride-1 convolutions' (an odd kernel size, any dilation, a cross or custom region through
+    kernel_generator=).
+
+    Not a _ConvBase: prepare_conv_weights lays out (K, cin, cout) weight images, and this block has none."""
+
+    def __init__(self, in_channels, num_heads, kernel_size=3, dilation=1, qkv_bias=True, rel_pos_bias=True, dimension=3,
+                 kernel_generator=None):
+        super().__init__()
+        if dimension != 3:
+            raise NotImplementedError(f"dimension={dimension}: only 3-D sparse tensors are supported")
+        given_ks = -1 if kernel_generator is not None and kernel_size == 3 else kernel_size
+        kernel_size, stride, dilation, self.region, _, K = _layer_geometry(type(self).__name__, given_ks, 1, dilation,
+                                                                          kernel_generator)
+        if stride != 1:
+            raise ValueError(f"{type(self).__name__}: a self-attention block works at stride 1, the kernel_generator has "
+                             f"stride={stride}")
+        if not isinstance(num_heads, int) or num_heads < 1 or in_channels % num_heads != 0:
+            raise ValueError(f"{type(self).__name__}: {in_channels} channels do not divide into num_heads={num_heads}")
+        self.in_channels = self.out_channels = in_channels
+        self.num_heads = num_heads
+        self.kernel_size, self.stride, self.dilation = kernel_size, 1, dilation
+        self.kernel_volume = K
+        self.kernel_generator = kernel_generator
+        self.scale = (in_channels // num_heads) ** -0.5
+        self.qkv = nn.Linear(in_channels, 3 * in_channels, bias=qkv_bias)
+        self.proj = nn.Linear(in_channels, in_channels)
+        self.rel_bias = nn.Parameter(torch.zeros((K, num_heads), dtype=torch.float32)) if rel_pos_bias else None
+
+    def forward(self, x: SparseTensor):
+        C = self.in_channels
+        q, k, v = (x._like(t.contiguous()) for t in self.qkv(x._raw()).split(C, dim=1))
+        y = kernel_attention(q, k, v, self.num_heads, self.rel_bias, self.scale, self.kernel_size, 1, self.dilation,
+                             self.kernel_generator)
+        return x._like(self.proj(y._raw()))
+
+    def extra_repr(self):
+        return (f"in={self.in_channels}, num_heads={self.num_heads}, kernel_size={self.kernel_size}, dilation={self.dilation}, "
+                f"rel_pos_bias={self.rel_bias is not None}" + _region_name(self.region))
+
+
 class MinkowskiPruning(nn.Module):
     """forward(x, mask): the rows of x whose entry of the bool mask [V] is set -- mask in the order of x.features /
     x.coordinates -- on a coordinate manager of their own, rooted at x's tensor stride.  .features is x.features[mask] and

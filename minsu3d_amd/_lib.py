@@ -26,7 +26,7 @@ def lib():
         for name in ("ms3d_ballquery_workspace_bytes", "ms3d_bfs_workspace_bytes", "ms3d_hais_workspace_bytes",
                      "ms3d_coord_workspace_bytes", "ms3d_coords_expand_workspace_bytes",
                      "ms3d_coords_union_workspace_bytes", "ms3d_broadcast_reduce_workspace_bytes",
-                     "ms3d_chconv_wgrad_ws_floats", "ms3d_inorm_workspace_bytes",
+                     "ms3d_chconv_wgrad_ws_floats", "ms3d_kattn_dbias_ws_floats", "ms3d_inorm_workspace_bytes",
                      "ms3d_dense_occupancy_workspace_bytes", "ms3d_kmap_pairs_workspace_bytes"):
             if hasattr(_lib, name):
                 getattr(_lib, name).restype = C.c_size_t

@@ -1226,6 +1226,66 @@ class _HipEngine:
                    "ms3d_chconv_backward_weight")
         return dW
 
+    # ---- local multi-head attention over a kernel map (csrc/kattn.hip)
+    def _kattn_check(self, q, k, v, rel_bias, nbr, rows, K, H):
+        """-> (q, k, v, rel_bias) contiguous on the device, head dimension D; nbr is the [K, rows] int32 table of the call"""
+        q, k, v = self._dev(q), self._dev(k), self._dev(v)
+        assert q.dtype == k.dtype == v.dtype == torch.float32 and q.dim() == k.dim() == v.dim() == 2
+        c = q.size(1)
+        assert k.size(1) == c and tuple(v.shape) == tuple(k.shape) and H >= 1 and c % H == 0
+        assert nbr.dtype == torch.int32 and nbr.numel() == K * rows
+        if rel_bias is not None:
+            rel_bias = self._dev(rel_bias)
+            assert rel_bias.dtype == torch.float32 and tuple(rel_bias.shape) == (K, H)
+        return q, k, v, rel_bias, c // H
+
+    def kattn_forward(self, q, k, v, rel_bias, nbr, vout, K, H, scale):
+        """-> (out [vout, C], lse [vout, H]): softmax over the present inputs nbr[kk][o] of scale * <q[o, h], k[i, h]> +
+        rel_bias[kk, h], applied to v; q [vout, C], k / v [vin, C], C = H * D, rel_bias [K, H] or None"""
+        q, k, v, rel_bias, d = self._kattn_check(q, k, v, rel_bias, nbr, vout, K, H)
+        assert q.size(0) == vout
+        out = torch.empty((vout, q.size(1)), dtype=torch.float32, device=q.device)
+        lse = torch.empty((vout, H), dtype=torch.float32, device=q.device)
+        _lib.check(self.lib.ms3d_kattn_forward(_lib.ptr(q), _lib.ptr(k), _lib.ptr(v), _lib.ptr(rel_bias), _lib.ptr(nbr),
+                                               int(vout), int(K), int(H), int(d), C.c_float(scale), _lib.ptr(out),
+                                               _lib.ptr(lse), _lib.stream_handle()), "ms3d_kattn_forward")
+        return out, lse
+
+    def kattn_backward_q(self, q, k, v, rel_bias, nbr, out, lse, dout, vout, K, H, scale, need_dq=True, need_dbias=True):
+        """-> (dq [vout, C] or None, dbias [K, H] or None, delta [vout, H]); delta, the residual sum_kk p <dout, v - out> per
+        row and head, is what kattn_backward_kv reads.  dbias: one partial per fixed run of output rows, summed in part order"""
+        q, k, v, rel_bias, d = self._kattn_check(q, k, v, rel_bias, nbr, vout, K, H)
+        dout = self._dev(dout)
+        assert tuple(dout.shape) == tuple(q.shape) == tuple(out.shape) and dout.dtype == torch.float32
+        need_dbias = need_dbias and rel_bias is not None
+        dev = q.device
+        dq = torch.empty_like(q) if need_dq else None
+        delta = torch.empty((vout, H), dtype=torch.float32, device=dev)
+        dbias = ws = None
+        if need_dbias:
+            dbias = torch.zeros((K, H), dtype=torch.float32, device=dev) if vout <= 0 else \
+                torch.empty((K, H), dtype=torch.float32, device=dev)
+            ws = self.ws.get("kattn_dbias", 4 * self.lib.ms3d_kattn_dbias_ws_floats(int(vout), int(K), int(H)), dev)
+        _lib.check(self.lib.ms3d_kattn_backward_q(_lib.ptr(q), _lib.ptr(k), _lib.ptr(v), _lib.ptr(rel_bias), _lib.ptr(nbr),
+                                                  _lib.ptr(out), _lib.ptr(lse), _lib.ptr(dout), int(vout), int(K), int(H),
+                                                  int(d), C.c_float(scale), _lib.ptr(dq), _lib.ptr(dbias), _lib.ptr(delta),
+                                                  _lib.ptr(ws), C.c_size_t(0 if ws is None else ws.numel() // 4),
+                                                  _lib.stream_handle()), "ms3d_kattn_backward_q")
+        return dq, dbias, delta
+
+    def kattn_backward_kv(self, q, k, v, rel_bias, nbr_inv, out, lse, delta, dout, vin, K, H, scale, need_dk=True, need_dv=True):
+        """-> (dk, dv) [vin, C] (None where not asked for): a gather through the inverse table nbr_inv [K, vin]"""
+        q, k, v, rel_bias, d = self._kattn_check(q, k, v, rel_bias, nbr_inv, vin, K, H)
+        dout = self._dev(dout)
+        assert k.size(0) == vin and tuple(dout.shape) == tuple(q.shape) == tuple(out.shape) and (need_dk or need_dv)
+        dk = torch.empty_like(k) if need_dk else None
+        dv = torch.empty_like(v) if need_dv else None
+        _lib.check(self.lib.ms3d_kattn_backward_kv(_lib.ptr(q), _lib.ptr(k), _lib.ptr(v), _lib.ptr(rel_bias), _lib.ptr(nbr_inv),
+                                                   _lib.ptr(out), _lib.ptr(lse), _lib.ptr(delta), _lib.ptr(dout), int(vin), int(K), int(H),
+                                                   int(d), C.c_float(scale), _lib.ptr(dk), _lib.ptr(dv),
+                                                   _lib.stream_handle()), "ms3d_kattn_backward_kv")
+        return dk, dv
+
     # ---- instance normalisation over the batch grouping of a coordinate set (csrc/inorm.hip)
     def _inorm_check(self, x, order, seg_start, seg_of_row):
         assert x.dtype == torch.float32 and x.dim() == 2

@@ -1,0 +1,168 @@
+"""Times ME.kernel_attention (csrc/kattn.hip) on a surface-like cloud of about 100k voxels (points on a few planes, the
+generator of tests/test_sparse_gpu.py's surface_coords; the voxel count is printed), C = 64, 4 heads, kernel size 3 (K = 27),
+with a relative-position bias, against the torch composition over CoordinateManager.kernel_map pairs -- how this result is
+computed without the fused kernels: two [P, C] gathers, a segmented softmax from scatter_reduce / index_add_, a weighted
+index_add_, backward through autograd.  Both run in the same process and take turns round by round.
+Device events, 3 warm-up calls, rounds of about 50 ms until every candidate has a window of at least --window seconds.
+Peak memory: torch.cuda.max_memory_allocated over one call, minus what was allocated before it (inputs and tables excluded).
+Needs a GPU: without one it fails, it does not fall back.
+
+usage: python tools/kattn_micro.py [--out profiles/kattn_micro.txt] [--window 0.5] [--seed 0]"""
+import argparse
+import os
+import sys
+
+import numpy as np
+import torch
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+C, H, KS = 64, 4, 3
+
+
+def surface_coords(rng, B, n, extent):
+    pts = []
+    for b in range(B):
+        m = n // B
+        u, v = rng.integers(0, extent, m), rng.integers(0, extent, m)
+        which = rng.integers(0, 3, m)
+        w = rng.integers(0, 2, m) + extent // 3
+        xyz = np.stack([np.where(which == 0, w, u), np.where(which == 1, w, v),
+                        np.where(which == 2, w, np.where(which == 0, v, u))], 1)
+        pts.append(np.concatenate([np.full((m, 1), b), xyz], 1))
+    c = np.unique(np.concatenate(pts, 0).astype(np.int32), axis=0)
+    rng.shuffle(c)
+    return c
+
+
+def event_ms(fn, n):
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    e0.record()
+    for _ in range(n):
+        fn()
+    e1.record()
+    torch.cuda.synchronize()
+    return e0.elapsed_time(e1) / n
+
+
+def measure(cands, window_s):
+    """cands: {name: fn} -> {name: (mean ms, min ms, max ms, calls)}; the candidates take turns, one round each"""
+    reps, rounds, spent = {}, {n: [] for n in cands}, {n: 0.0 for n in cands}
+    for name, fn in cands.items():
+        for _ in range(3):
+            fn()
+        torch.cuda.synchronize()
+        reps[name] = max(1, int(50.0 / max(event_ms(fn, 2), 1e-3)))
+    while min(spent.values()) < window_s * 1e3:
+        for name, fn in cands.items():
+            ms = event_ms(fn, reps[name])
+            rounds[name].append(ms)
+            spent[name] += ms * reps[name]
+    return {n: (float(np.mean(r)), min(r), max(r), len(r) * reps[n]) for n, r in rounds.items()}
+
+
+def peak_mb(fn):
+    torch.cuda.synchronize()
+    base = torch.cuda.memory_allocated()
+    torch.cuda.reset_peak_memory_stats()
+    fn()
+    torch.cuda.synchronize()
+    return (torch.cuda.max_memory_allocated() - base) / 2 ** 20
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "kattn_micro.txt"))
+    ap.add_argument("--window", type=float, default=0.5)
+    ap.add_argument("--seed", type=int, default=0)
+    args = ap.parse_args()
+    if not torch.cuda.is_available():
+        raise SystemExit("kattn_micro: no GPU present -- this tool measures on the device and has no fallback")
+    import minsu3d_amd.MinkowskiEngine as ME
+
+    dev = torch.device("cuda", 0)
+    coords = torch.from_numpy(surface_coords(np.random.default_rng(args.seed), 5, 1000000, 104)).to(dev)
+    x0 = ME.SparseTensor(torch.zeros((coords.size(0), 1), device=dev), coordinates=coords)
+    cm, key = x0.coordinate_manager, x0.coordinate_map_key
+    V, K, D = cm.size(1), KS ** 3, C // H
+    scale = D ** -0.5
+    pairs, start = cm.kernel_map_pairs(key, key, kernel_size=KS)
+    i_rows, o_rows = pairs[0], pairs[1]
+    P = pairs.size(1)
+    kk_of = torch.repeat_interleave(torch.arange(K, device=dev), (start[1:] - start[:-1]).long())
+    o_h = o_rows[:, None].expand(-1, H)
+
+    torch.manual_seed(1)
+    fq, fk, fv = (torch.randn(V, C, device=dev, requires_grad=True) for _ in range(3))
+    bias = torch.randn(K, H, device=dev, requires_grad=True)
+    g = torch.randn(V, C, device=dev)
+    leaves = (fq, fk, fv, bias)
+
+    def fused():
+        q, k, v = (ME.SparseTensor(f, coordinate_map_key=key) for f in (fq, fk, fv))
+        return ME.kernel_attention(q, k, v, H, rel_bias=bias, kernel_size=KS).F
+
+    def composed():
+        qh, kh, vh = fq.view(V, H, D), fk.view(V, H, D), fv.view(V, H, D)
+        s = scale * (qh[o_rows] * kh[i_rows]).sum(-1) + bias[kk_of]                                   # [P, H]
+        m = torch.full((V, H), float("-inf"), device=dev).scatter_reduce(0, o_h, s.detach(), "amax")
+        e = torch.exp(s - m[o_rows])
+        den = torch.zeros((V, H), device=dev).index_add_(0, o_rows, e)
+        p = e / den[o_rows]
+        return torch.zeros((V, H, D), device=dev).index_add_(0, o_rows, p.unsqueeze(-1) * vh[i_rows]).view(V, C)
+
+    def clear():
+        for t in leaves:
+            t.grad = None
+
+    def fwd(fn):
+        def run():
+            with torch.no_grad():
+                return fn()
+        return run
+
+    def fwd_bwd(fn):
+        def run():
+            clear()
+            fn().backward(g)
+        return run
+
+    # faster and different is not faster: the two agree on this input before anything is timed
+    errs = []
+    fwd_bwd(composed)()
+    want = [fwd(composed)()] + [t.grad.clone() for t in leaves]
+    fwd_bwd(fused)()
+    got = [fwd(fused)()] + [t.grad.clone() for t in leaves]
+    for name, a, b in zip(("out", "dq", "dk", "dv", "dbias"), got, want):
+        errs.append(f"{name} {float((a - b).abs().max() / b.abs().max()):.1e}")
+
+    cands = {"fused fwd": fwd(fused), "torch-composed fwd": fwd(composed), "fused fwd+bwd": fwd_bwd(fused),
+             "torch-composed fwd+bwd": fwd_bwd(composed)}
+    res = measure(cands, args.window)
+    clear()
+    mem = {name: peak_mb(fn) for name, fn in cands.items()}
+    lines = [f"kattn_micro: {torch.cuda.get_device_name(0)}; surface cloud seed {args.seed}: V = {V} voxels "
+             f"(manager {'Morton-sorted' if cm.perm is not None else 'in caller order'}), C = {C}, H = {H}, D = {D}, K = {K}, "
+             f"present pairs P = {P} ({P / V:.2f} per row); window >= {args.window} s per candidate, rounds alternate",
+             "times: ms per call, mean over the rounds (min .. max of the rounds); fwd+bwd = forward, then backward from a fixed "
+             "dout with gradients for q, k, v and rel_bias; peak MiB: allocated above the inputs and tables during one call",
+             "fused vs torch-composed on this input, max abs difference over the composed tensor's max: " + ", ".join(errs), ""]
+    for name, (mean, lo, hi, calls) in res.items():
+        lines.append(f"  {name:<24} {mean:9.4f} ms  ({lo:.4f} .. {hi:.4f}; {calls} calls)   peak {mem[name]:9.1f} MiB")
+    lines.append(f"  torch-composed / fused: fwd {res['torch-composed fwd'][0] / res['fused fwd'][0]:.1f}x time, "
+                 f"{mem['torch-composed fwd'] / max(mem['fused fwd'], 1e-9):.1f}x peak memory; fwd+bwd "
+                 f"{res['torch-composed fwd+bwd'][0] / res['fused fwd+bwd'][0]:.1f}x time, "
+                 f"{mem['torch-composed fwd+bwd'] / max(mem['fused fwd+bwd'], 1e-9):.1f}x peak memory")
+    b_fwd = 4 * K * V + 4 * C * (2 * P + 2 * V) + 4 * H * V
+    lines.append(f"  algorithmic bytes of a fused forward (table, gathered k and v rows, q and out rows, lse): {b_fwd / 1e6:.1f} MB "
+                 f"-> {b_fwd / (res['fused fwd'][0] * 1e-3) / 1e9:.0f} GB/s achieved (an algorithmic rate, not a counter reading)")
+    print("\n".join(lines), flush=True)
+    os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+    with open(args.out, "w") as f:
+        f.write("\n".join(lines) + "\n")
+    print("wrote", args.out)
+
+
+if __name__ == "__main__":
+    main()
