@@ -424,6 +424,59 @@ int ms3d_kattn_rows_per_part(void);
 int ms3d_kattn_dbias_parts(int Vout);
 size_t ms3d_kattn_dbias_ws_floats(int Vout, int K, int H);
 
+/* ---- per-sample query attention over voxel rows (csrc/qattn.hip; float32 throughout).  queries [B][Q][C], k / v [V][C] row-
+ * contiguous in the order the rows are HELD, C = H * D (H heads of D channels).  The rows of sample b are
+ * order[seg_start[b] .. seg_start[b + 1]) (order int64 [V], seg_start int32 [B + 1]: CoordinateManager.batch_rows); they are
+ * read by index where they lie.  mask [V][Q] bytes or NULL, non-zero = may not attend, one mask for all heads, its rows in the
+ * CALLER's order: the mask row of held row i is row_map[i] (int32 [V], the manager's held-to-caller index) or i when row_map
+ * is NULL.  Over the rows i of sample b that the mask does not block for query q:
+ *   s[b][q][i][h] = scale * sum_d queries[b][q][hD+d] * k[i][hD+d]
+ *   p             = exp(s - m) / sum_i' exp(s' - m),  m = the maximum over those rows (always subtracted)
+ *   out[b][q][hD+d] = sum_i p * v[i][hD+d];   lse[b][q][h] = m + log sum exp(s - m)
+ * A (b, q) without an unblocked row gives out = 0 and lse = 0, contributes to no gradient and receives none.
+ * Chunks: a segment is cut into runs of ms3d_qattn_rows_per_chunk() consecutive positions of `order` (a constant of the
+ * library, independent of the device, so the order of every sum is too).  ms3d_qattn_chunks(seg_start, B): the number of
+ * chunks, sum_b ceil(len_b / rows_per_chunk); ms3d_qattn_chunk_list fills chunk_seg [chunks] (the sample of every chunk) and
+ * chunk_first [B + 1] (the first chunk of every sample; chunk_first[B] = chunks): sorted by sample, then by run.  Both are
+ * pure HOST arithmetic over HOST arrays; the launches take DEVICE copies of chunk_seg and chunk_first.
+ * forward: one workgroup per chunk and tile of (query, head) items does one online-softmax sweep over the chunk's rows in
+ * ascending position and stores a partial (m, l, acc[D]) per item; a second kernel merges the partials of a sample in
+ * ascending chunk order and writes out [B][Q][C] and lse [B][Q][H].  ws: ms3d_qattn_ws_floats(chunks, Q, H, D) =
+ * chunks * Q * (H * D + 2 * H) floats, the only scratch; nothing of size [V][Q] is written.
+ * backward_q: the same sweep with p = exp(s - lse) recomputed; ds = p * (e - delta[b][q][h]) with e = sum_d dout[b][q][hD+d] *
+ * (v[i][hD+d] - out[b][q][hD+d]) -- the difference per channel before the sum, as in ms3d_kattn_backward_q -- and
+ * delta[b][q][h] = sum_i p * e, the residual that the float32 rounding of the saved out leaves.  Per chunk sum p e k, sum p k
+ * and sum p e are stored and added in ascending chunk order: dq[b][q][h][:] = scale * (sum p e k - delta * sum p k).  delta
+ * [B][Q][H] is always written (backward_kv reads it); dq may be NULL (delta alone).  ws: ms3d_qattn_backward_ws_floats(chunks,
+ * Q, H, D) = chunks * Q * (2 * H * D + H) floats.
+ * backward_kv: one (row, head) item per voxel row loops over the Q queries of its sample seg_of_row[i] (int32 [V], the segment
+ * of every held row: CoordinateManager.batch_segments) in ascending q: dv[i][h][:] = sum_q p * dout[b][q][h][:],
+ * dk[i][h][:] = scale * sum_q ds * queries[b][q][h][:]; one writer per element, no scratch; dk or dv may be NULL (not both).
+ * Every sum runs in one fixed order that depends on the shapes only; no atomics; the same bytes on every run, in all three.
+ * 16-byte row accesses when D % 4 == 0 and every row pointer (ws included) is 16-byte aligned, a scalar path otherwise;
+ * 64-bit offsets.
+ * Limits: 1 <= D <= 128, H >= 1, H * D <= 1024, 0 <= Q <= 1024, 0 <= B <= 65535, V >= 0, chunks >= 0.  Outside them, or a NULL
+ * pointer that would be read or written: MS3D_E_UNSUPPORTED; a short workspace: MS3D_E_WORKSPACE; both decided on the host
+ * before any launch.  V == 0, B == 0 or Q == 0 with a served shape: 0, nothing is launched, no pointer is looked at.  The
+ * index arrays are trusted: order and row_map name rows in [0, V), seg_of_row and chunk_seg samples in [0, B). */
+int ms3d_qattn_rows_per_chunk(void);
+long ms3d_qattn_chunks(const int *seg_start /*HOST [B + 1]*/, int B);
+int ms3d_qattn_chunk_list(const int *seg_start /*HOST [B + 1]*/, int B, int *chunk_seg /*HOST [chunks]*/,
+                          int *chunk_first /*HOST [B + 1]*/);
+size_t ms3d_qattn_ws_floats(long chunks, int Q, int H, int D);
+size_t ms3d_qattn_backward_ws_floats(long chunks, int Q, int H, int D);
+int ms3d_qattn_forward(const float *queries, const float *k, const float *v, const unsigned char *mask, const int *row_map,
+                       const long long *order, const int *seg_start, const int *chunk_seg, const int *chunk_first, long V, int B,
+                       int chunks, int Q, int H, int D, float scale, float *out, float *lse, float *ws, size_t ws_floats,
+                       ms3d_stream_t stream);
+int ms3d_qattn_backward_q(const float *queries, const float *k, const float *v, const unsigned char *mask, const int *row_map,
+                          const long long *order, const int *seg_start, const int *chunk_seg, const int *chunk_first,
+                          const float *out, const float *lse, const float *dout, long V, int B, int chunks, int Q, int H, int D,
+                          float scale, float *dq, float *delta, float *ws, size_t ws_floats, ms3d_stream_t stream);
+int ms3d_qattn_backward_kv(const float *queries, const float *k, const float *v, const unsigned char *mask, const int *row_map,
+                           const int *seg_of_row, const float *out, const float *lse, const float *delta, const float *dout,
+                           long V, int B, int Q, int H, int D, float scale, float *dk, float *dv, ms3d_stream_t stream);
+
 /* ---- instance normalisation: per batch index (segment) and channel (csrc/inorm.hip; float32 rows and parameters, any C >= 1;
  * every sum, the statistics mean / invstd (DOUBLE [B, C]) and the arithmetic of the row passes are float64, rounded once at the
  * store: with few rows in a segment dx is a difference of nearly equal terms that float32 statistics cannot resolve; a lane takes four

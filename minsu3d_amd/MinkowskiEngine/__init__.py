@@ -160,6 +160,35 @@ no such layer, and nothing here is pinned to it):
     Out of scope: attention dropout, masks, a value head dimension different from D, float16 / bfloat16 rows, gradients
     through the coordinates.  Outside prepare_conv_weights: the block is not a dense-weight convolution.
 
+Per-sample query attention -- the global block of a sparse transformer, the decoder step of the mask-transformer family
+(engine extras: MinkowskiEngine has no such layer, and nothing here is pinned to it):
+
+    query_attention(queries, k, v, num_heads, attn_mask=None, scale=None) -> a float32 tensor [B, Q, C];
+    MinkowskiQueryAttention(embed_dim, num_heads, in_channels=None, bias=True): forward(queries, x, attn_mask=None) =
+    out_proj(query_attention(q_proj(queries), k_proj(x), v_proj(x))); parameters q_proj, k_proj, v_proj, out_proj (nn.Linear;
+    k_proj and v_proj map in_channels to embed_dim)
+
+    out[b, q, h, :] = sum_i softmax_i(scale * <queries[b, q, h], k[i, h]>) v[i, h, :] over the rows i of sample b that attn_mask
+    does not block; C = num_heads * D, scale = D ** -0.5 unless given.  k and v: SparseTensors on one coordinate set; queries
+    [B, Q, C] with B the number of batch indices PRESENT, queries[b] for the b-th of them in ascending order (the numbering of
+    CoordinateManager.batch_rows, of origin_map and of the global pooling layers' output rows; gaps in the batch indices and
+    interleaved rows are fine; another B is a ValueError).  attn_mask: bool [V, Q], row i the i-th row of k.F / k.C as the
+    caller sees them, column q the query of that row's own sample, True = may NOT attend, one mask for all heads.  A (b, q)
+    whose rows are all blocked is zero, contributes to no gradient and receives none (torch.nn.MultiheadAttention gives NaN
+    there).  csrc/qattn.hip: the rows of a sample are batch_rows' segment, read by index where they are held (on a
+    Morton-sorted manager the mask row is found through the held-to-caller index); a segment is cut into chunks of
+    ms3d_qattn_rows_per_chunk() positions (CoordinateManager.batch_chunks: one host read per coordinate set), one workgroup
+    per chunk and tile of (query, head) items does an online-softmax sweep and leaves a partial, a second kernel merges the
+    partials in chunk order and saves the log-sum-exp; the backward recomputes the probabilities -- a second sweep for the
+    queries, a loop over the queries per voxel row for k and v.  Nothing of size V x Q is stored, no atomics, every sum in an
+    order fixed by the shapes, the same bytes on every run.  D <= 128, Q <= 1024, C <= 1024, B <= 65535.  Frozen k and v skip
+    their pass; frozen queries skip theirs when k and v are frozen too (the kv pass reads a per-query residual the q pass
+    leaves).
+    Out of scope (each raises ValueError, TypeError or NotImplementedError naming it): a different Q per sample, float or
+    per-head masks, attention dropout, a value head dimension different from D, float16 / bfloat16, the reverse direction
+    (voxels attending to queries), CPU tensors (NotImplementedError naming ms3d_qattn_forward).  The mask logits x.F @
+    queries[b].T are a per-sample matmul of the caller's.  Outside prepare_conv_weights.
+
 Not supported (each raises NotImplementedError naming it): `axis_types` of a KernelGenerator, a region of more than 254
 offsets, a dense grid of more than 2^31 - 1 cells, to_sparse of a tensor
 that is not 5-D ([B, C, X, Y, Z]: dimension 3) or in a format other than "BCXXX" / "BXXXC", dense() on a per-axis tensor stride, strides other than 1 and 2, a generative layer at stride 2 on an odd
@@ -187,7 +216,7 @@ from .modules import (MinkowskiConvolution, MinkowskiConvolutionTranspose, Minko
                       MinkowskiBroadcastConcatenation, MinkowskiBroadcast, MinkowskiSigmoid,
                       MinkowskiPoolingTranspose, MinkowskiInterpolation, MinkowskiChannelwiseConvolution,
                       MinkowskiInstanceNorm, MinkowskiStableInstanceNorm,
-                      MinkowskiKernelAttention, kernel_attention,
+                      MinkowskiKernelAttention, kernel_attention, MinkowskiQueryAttention, query_attention,
                       MinkowskiToSparseTensor, MinkowskiToDenseTensor, MinkowskiToFeature,
                       MinkowskiELU, MinkowskiLeakyReLU, MinkowskiPReLU, MinkowskiSELU, MinkowskiCELU, MinkowskiGELU,
                       MinkowskiSiLU, MinkowskiTanh, MinkowskiSoftplus, MinkowskiHardswish, MinkowskiHardtanh,

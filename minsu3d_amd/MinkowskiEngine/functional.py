@@ -637,6 +637,50 @@ def kernel_attention_rows(q, k, v, rel_bias, nbr_fwd, nbr_inv, vin, vout, K, num
     return KernelAttentionFn.apply(q, k, v, rel_bias, nbr_fwd, nbr_inv, vin, vout, K, num_heads, scale)
 
 
+class QueryAttentionFn(torch.autograd.Function):
+    """out[b, q, h, :] = sum_i softmax_i(scale * <queries[b, q, h], k[i, h]>) * v[i, h, :] over the rows i of sample b that
+    mask [V, Q] does not block (csrc/qattn.hip; float32, C = num_heads * D; a query with nothing to attend to is zero).  k / v:
+    rows as the manager holds them; mask: rows as the caller sees them, row_map the held -> caller index (None: the same);
+    group = (order, seg_start, chunk_seg, chunk_first, chunks) of CoordinateManager.batch_rows / batch_chunks, seg_of_row =
+    batch_segments.  Saves queries, k, v, out and the log-sum-exp lse [B, Q, H]; the backward recomputes the probabilities
+    from lse.  The q pass sweeps the chunks again (dq and delta [B, Q, H], the residual the kv pass subtracts; one partial per
+    chunk, added in chunk order), the kv pass loops over the queries per row: no atomics, the same bytes on every run.
+    Frozen queries skip the q pass unless the kv pass needs its delta (the pass then stores nothing else); frozen k and v
+    skip the kv pass."""
+
+    @staticmethod
+    def forward(ctx, queries, k, v, mask, row_map, group, seg_of_row, num_heads, scale):
+        be = get_backend()
+        if not hasattr(be, "qattn_forward"):
+            raise NotImplementedError("query attention needs the HIP backend (ms3d_qattn_forward)")
+        queries, k, v = queries.contiguous(), k.contiguous(), v.contiguous()
+        out, lse = be.qattn_forward(queries, k, v, mask, row_map, group, num_heads, scale)
+        ctx.save_for_backward(queries, k, v, out, lse)
+        ctx.geom = (mask, row_map, group, seg_of_row, num_heads, scale)
+        return out
+
+    @staticmethod
+    def backward(ctx, dout):
+        queries, k, v, out, lse = ctx.saved_tensors
+        mask, row_map, group, seg_of_row, H, scale = ctx.geom
+        need_q, need_k, need_v = ctx.needs_input_grad[:3]
+        be = get_backend()
+        dout = dout.contiguous()
+        dq = dk = dv = None
+        if need_q or need_k or need_v:
+            dq, delta = be.qattn_backward_q(queries, k, v, mask, row_map, group, out, lse, dout, H, scale, need_dq=need_q)
+            if need_k or need_v:
+                dk, dv = be.qattn_backward_kv(queries, k, v, mask, row_map, seg_of_row, out, lse, delta, dout, H, scale,
+                                              need_dk=need_k, need_dv=need_v)
+        return dq, dk, dv, None, None, None, None, None, None
+
+
+def query_attention_rows(queries, k, v, mask, row_map, group, seg_of_row, num_heads, scale):
+    """attention of queries [B, Q, C] over the rows k / v [V, C] of their own sample (rows as the manager holds them, the mask's
+    as the caller sees them) -> out [B, Q, C]"""
+    return QueryAttentionFn.apply(queries, k, v, mask, row_map, group, seg_of_row, num_heads, scale)
+
+
 class InstanceNormFn(torch.autograd.Function):
     """y[r, c] = (x[r, c] - mean[s, c]) * invstd[s, c] * weight[c] + bias[c] with the statistics of the row's segment s (its
     batch index) and the biased variance (csrc/inorm.hip).  group = (order, seg_start, seg_of_row): CoordinateManager.

@@ -512,6 +512,132 @@ class MinkowskiKernelAttention(nn.Module):
                 f"rel_pos_bias={self.rel_bias is not None}" + _region_name(self.region))
 
 
+_QATTN_MAX_D, _QATTN_MAX_Q, _QATTN_MAX_C, _QATTN_MAX_B = 128, 1024, 1024, 65535      # the limits of csrc/qattn.hip
+
+
+def query_attention(queries, k, v, num_heads, attn_mask=None, scale=None, dropout=0.0):
+    """Per-sample multi-head attention of a fixed number of queries over the voxels of their own sample (an engine extra:
+    MinkowskiEngine has no such layer) -- the decoder step of a mask transformer.  k, v: SparseTensors on one coordinate set
+    (one manager, one tensor stride) with V rows of C = num_heads * D float32 channels.  queries: a float32 tensor [B, Q, C] on
+    the same device; B is the number of batch indices PRESENT in the set and queries[b] belongs to the b-th of them in ascending
+    order -- the numbering of CoordinateManager.batch_rows, of origin_map and of the MinkowskiGlobal*Pooling output rows,
+    whatever gaps the batch indices have and wherever the rows of a sample lie.  For sample b, query q, head h, over the rows i
+    of that sample:  out[b, q, hD:hD+D] = sum_i softmax_i(scale * <queries[b, q, hD:hD+D], k[i, hD:hD+D]>) * v[i, hD:hD+D], scale =
+    D ** -0.5 unless given.  -> a float32 tensor [B, Q, C].
+
+    attn_mask: a bool tensor [V, Q] or None: row i is the i-th row of k.F / k.C as the caller sees them, column q the query of
+    that row's own sample, True = may NOT attend (torch's convention), one mask for all heads -- the layout in which a mask
+    transformer makes its mask (voxel features times query embeddings).  A (b, q) whose rows are all blocked gives out = 0,
+    contributes to no gradient and receives none -- the rule of kernel_attention for a row that reaches no input, and NOT that
+    of torch.nn.MultiheadAttention, which gives NaN there; a caller who wants "attend everywhere instead" clears those
+    mask columns first.
+
+    Gradients flow to queries, k.F and v.F.  A pending BatchNorm / ReLU on k or v is materialised first.  float32 HIP kernels
+    without atomics (csrc/qattn.hip): the rows are read where the manager holds them, nothing of size V x Q is stored, forward
+    and every gradient are the same bytes on every run.  D <= 128, Q <= 1024, C <= 1024, B <= 65535.
+    Not offered: a different Q per sample (pad the queries and block the padding's columns), float or per-head masks, attention
+    dropout, a value head dimension other than D, float16 / bfloat16, the reverse direction (voxels attending to queries), CPU
+    tensors."""
+    name = "query_attention"
+    if isinstance(queries, SparseTensor) or not isinstance(k, SparseTensor) or not isinstance(v, SparseTensor):
+        raise TypeError(f"{name}: queries is a dense tensor [B, Q, C], k and v are SparseTensors; the reverse direction (voxels "
+                        "attending to queries) is not offered")
+    if isinstance(queries, (list, tuple)):
+        raise NotImplementedError(f"{name}: a different Q per sample (a list of query tensors) is not offered: pad the queries to "
+                                  "one Q and block the padding's columns in attn_mask")
+    if not torch.is_tensor(queries):
+        raise TypeError(f"{name}: queries must be a float32 tensor [B, Q, C], got {type(queries).__name__}")
+    if dropout:
+        raise NotImplementedError(f"{name}: attention dropout (dropout={dropout}) is not offered")
+    cm, ts = k.coordinate_manager, k.tensor_stride
+    if v.coordinate_manager is not cm or v.tensor_stride != ts:
+        raise ValueError(f"{name}: k and v must be on the same coordinate set (one manager, one tensor stride)")
+    for what, t in (("queries", queries), ("k", k._F), ("v", v._F)):
+        if t.dtype != torch.float32:
+            raise TypeError(f"{name}: {what} is {t.dtype}; float32 only (float16 / bfloat16 are not offered)")
+    V, C = k._F.shape
+    if v._F.size(1) != C:
+        raise ValueError(f"{name}: v has {v._F.size(1)} channels, k has {C}: a value head dimension different from D is not "
+                         "offered")
+    if queries.dim() != 3 or queries.size(2) != C:
+        raise ValueError(f"{name}: queries must have shape [B, Q, C] with C = {C}, the channels of k and v, got "
+                         f"{tuple(queries.shape)}")
+    if not isinstance(num_heads, int) or num_heads < 1 or C % num_heads != 0:
+        raise ValueError(f"{name}: {C} channels do not divide into num_heads={num_heads}")
+    if queries.device != k._F.device:
+        raise ValueError(f"{name}: queries are on {queries.device}, k and v on {k._F.device}")
+    order, _, offsets, _ = cm.batch_rows(ts)
+    B, Q, D = offsets.numel() - 1, queries.size(1), C // num_heads
+    if queries.size(0) != B:
+        raise ValueError(f"{name}: queries has B = {queries.size(0)} samples, the coordinate set holds {B} batch indices")
+    if attn_mask is not None:
+        if not torch.is_tensor(attn_mask) or attn_mask.dtype != torch.bool:
+            raise TypeError(f"{name}: attn_mask must be a bool tensor [V, Q] (True = may not attend), got "
+                            f"{getattr(attn_mask, 'dtype', type(attn_mask).__name__)}; float masks are not offered")
+        if attn_mask.dim() == 3:
+            raise ValueError(f"{name}: attn_mask has shape {tuple(attn_mask.shape)}; per-head masks are not offered, one [V, Q] "
+                             "mask serves all heads")
+        if tuple(attn_mask.shape) != (V, Q):
+            raise ValueError(f"{name}: attn_mask must have shape [V, Q] = [{V}, {Q}], got {list(attn_mask.shape)}")
+        if attn_mask.device != k._F.device:
+            raise ValueError(f"{name}: attn_mask is on {attn_mask.device}, k and v on {k._F.device}")
+    for what, got, cap in (("head dimension D", D, _QATTN_MAX_D), ("Q", Q, _QATTN_MAX_Q), ("C = num_heads * D", C, _QATTN_MAX_C),
+                           ("B", B, _QATTN_MAX_B)):
+        if got > cap:
+            raise ValueError(f"{name}: {what} = {got} is above the kernels' limit of {cap}")
+    if B == 0 or Q == 0:
+        return queries.new_zeros((B, Q, C))
+    be = get_backend()
+    if not hasattr(be, "qattn_forward") or not k._F.is_cuda:
+        raise NotImplementedError(f"{name} needs the HIP backend and device tensors, CPU tensors are not offered "
+                                  "(ms3d_qattn_forward)")
+    if scale is None:
+        scale = D ** -0.5
+    group = (order, offsets) + cm.batch_chunks(ts)
+    mask = None if attn_mask is None else attn_mask.contiguous()
+    return Fn.query_attention_rows(queries, k._raw(), v._raw(), mask, cm.caller_rows(ts), group, cm.batch_segments(ts),
+                                   num_heads, float(scale))
+
+
+class MinkowskiQueryAttention(nn.Module):
+    """The cross-attention block of a mask-transformer decoder (an engine extra: MinkowskiEngine has no such layer):
+    forward(queries, x, attn_mask=None) = out_proj(query_attention(q_proj(queries), k_proj(x), v_proj(x), num_heads,
+    attn_mask)) -> [B, Q, embed_dim].  `q_proj` and `out_proj` are nn.Linear(embed_dim, embed_dim), `k_proj` and `v_proj`
+    nn.Linear(in_channels, embed_dim) applied to the rows of the SparseTensor x (in_channels defaults to embed_dim); `bias`
+    switches the bias of all four.  Positional terms are the caller's to add (x + pos works on a SparseTensor); a query whose
+    rows are all blocked comes out as out_proj's bias (query_attention gives zero there, not NaN).
+
+    Not a _ConvBase: prepare_conv_weights lays out (K, cin, cout) weight images, and this block has none."""
+
+    def __init__(self, embed_dim, num_heads, in_channels=None, bias=True, dropout=0.0):
+        super().__init__()
+        if dropout:
+            raise NotImplementedError(f"{type(self).__name__}: attention dropout (dropout={dropout}) is not offered")
+        if not isinstance(num_heads, int) or num_heads < 1 or embed_dim % num_heads != 0:
+            raise ValueError(f"{type(self).__name__}: {embed_dim} channels do not divide into num_heads={num_heads}")
+        self.embed_dim = int(embed_dim)
+        self.in_channels = self.embed_dim if in_channels is None else int(in_channels)
+        self.num_heads = num_heads
+        self.q_proj = nn.Linear(self.embed_dim, self.embed_dim, bias=bias)
+        self.k_proj = nn.Linear(self.in_channels, self.embed_dim, bias=bias)
+        self.v_proj = nn.Linear(self.in_channels, self.embed_dim, bias=bias)
+        self.out_proj = nn.Linear(self.embed_dim, self.embed_dim, bias=bias)
+
+    def forward(self, queries, x: SparseTensor, attn_mask=None):
+        if not isinstance(x, SparseTensor) or isinstance(queries, SparseTensor):
+            raise TypeError(f"{type(self).__name__}: forward(queries, x) takes a dense tensor [B, Q, C] and a SparseTensor; the "
+                            "reverse direction (voxels attending to queries) is not offered")
+        if x._F.size(1) != self.in_channels:
+            raise ValueError(f"{type(self).__name__}: the input has {x._F.size(1)} channels, the layer in_channels="
+                             f"{self.in_channels}")
+        rows = x._raw()
+        k, v = x._like(self.k_proj(rows)), x._like(self.v_proj(rows))
+        return self.out_proj(query_attention(self.q_proj(queries), k, v, self.num_heads, attn_mask))
+
+    def extra_repr(self):
+        return f"embed_dim={self.embed_dim}, num_heads={self.num_heads}, in_channels={self.in_channels}"
+
+
 class MinkowskiPruning(nn.Module):
     """forward(x, mask): the rows of x whose entry of the bool mask [V] is set -- mask in the order of x.features /
     x.coordinates -- on a coordinate manager of their own, rooted at x's tensor stride.  .features is x.features[mask] and

@@ -815,6 +815,29 @@ class CoordinateManager:
             cache[ts] = seg
         return seg
 
+    def batch_chunks(self, ts):
+        """the chunk list of query_attention over batch_rows(ts) -> (chunk_seg int32 [chunks]: the sample of every chunk,
+        chunk_first int32 [B + 1]: the first chunk of every sample, chunks): every segment cut into runs of
+        ms3d_qattn_rows_per_chunk() positions of `order`, sorted by sample, then by run -- a pure function of the segment
+        lengths (backend.qattn_chunk_list).  Its size needs the segment lengths on the host: one host read, once per tensor
+        stride, kept beside batch_rows.  An engine extra."""
+        cache = self.__dict__.setdefault("_batch_chunks", {})
+        hit = cache.get(ts)
+        if hit is None:
+            offsets = self.batch_rows(ts)[2]
+            chunk_seg, chunk_first = get_backend().qattn_chunk_list(offsets.cpu())
+            hit = cache[ts] = (chunk_seg.to(offsets.device), chunk_first.to(offsets.device), chunk_seg.numel())
+        return hit
+
+    def caller_rows(self, ts):
+        """int32 [V]: for every row of the set as it is HELD, the row of .coordinates / .features the caller sees it at; None
+        where the two orders are the same (no Morton permutation, or a coarser set).  Built once."""
+        if ts != 1 or self.perm is None:
+            return None
+        if "_caller_rows" not in self.__dict__:
+            self.__dict__["_caller_rows"] = self.perm.to(torch.int32).contiguous()
+        return self.__dict__["_caller_rows"]
+
     def extent(self, ts):
         """(per-axis minimum [3], per-axis maximum [3], largest batch index) of the coordinate set as Python ints, None for an
         empty set; one small host read, once per tensor stride.  An engine extra."""

@@ -1286,6 +1286,99 @@ class _HipEngine:
                                                    _lib.stream_handle()), "ms3d_kattn_backward_kv")
         return dk, dv
 
+    # ---- per-sample query attention over the batch grouping of a coordinate set (csrc/qattn.hip)
+    def qattn_rows_per_chunk(self):
+        return int(self.lib.ms3d_qattn_rows_per_chunk())
+
+    def qattn_chunk_list(self, seg_start):
+        """seg_start: HOST int32 [B + 1] (the offsets of CoordinateManager.batch_rows) -> (chunk_seg int32 [chunks], chunk_first
+        int32 [B + 1]) on the host: every segment in runs of qattn_rows_per_chunk() positions, by sample, then by run"""
+        seg_start = seg_start.to(torch.int32).contiguous()
+        assert not seg_start.is_cuda and seg_start.dim() == 1 and seg_start.numel() >= 1
+        B = seg_start.numel() - 1
+        chunks = int(self.lib.ms3d_qattn_chunks(_lib.ptr(seg_start), int(B)))
+        chunk_seg = torch.empty(chunks, dtype=torch.int32)
+        chunk_first = torch.empty(B + 1, dtype=torch.int32)
+        _lib.check(self.lib.ms3d_qattn_chunk_list(_lib.ptr(seg_start), int(B), _lib.ptr(chunk_seg), _lib.ptr(chunk_first)),
+                   "ms3d_qattn_chunk_list")
+        return chunk_seg, chunk_first
+
+    def _qattn_check(self, queries, k, v, mask, row_map, H):
+        """-> (queries, k, v) contiguous on the device and (V, B, Q, D)"""
+        queries, k, v = self._dev(queries), self._dev(k), self._dev(v)
+        assert queries.dtype == k.dtype == v.dtype == torch.float32 and queries.dim() == 3 and k.dim() == v.dim() == 2
+        c = k.size(1)
+        assert queries.size(2) == c and tuple(v.shape) == tuple(k.shape) and H >= 1 and c % H == 0
+        V, (B, Q) = k.size(0), queries.shape[:2]
+        if mask is not None:
+            assert mask.dtype == torch.bool and mask.is_contiguous() and tuple(mask.shape) == (V, Q) and mask.device == k.device
+        if row_map is not None:
+            assert row_map.dtype == torch.int32 and row_map.is_contiguous() and row_map.numel() == V
+        return queries, k, v, V, B, Q, c // H
+
+    @staticmethod
+    def _qattn_group(group, V, B):
+        order, seg_start, chunk_seg, chunk_first, chunks = group
+        assert order.dtype == torch.int64 and order.is_contiguous() and order.numel() == V
+        assert seg_start.dtype == torch.int32 and seg_start.is_contiguous() and seg_start.numel() == B + 1
+        assert chunk_seg.dtype == torch.int32 and chunk_seg.is_contiguous() and chunk_seg.numel() == chunks
+        assert chunk_first.dtype == torch.int32 and chunk_first.is_contiguous() and chunk_first.numel() == B + 1
+        return order, seg_start, chunk_seg, chunk_first, int(chunks)
+
+    def qattn_forward(self, queries, k, v, mask, row_map, group, H, scale):
+        """-> (out [B, Q, C], lse [B, Q, H]): per sample, softmax over the sample's rows that mask [V, Q] (bool, caller's row
+        order; None: none) does not block of scale * <queries[b, q, h], k[i, h]>, applied to v.  k / v [V, C] as held; row_map
+        int32 [V] held row -> caller's row, or None; group = (order, seg_start, chunk_seg, chunk_first, chunks):
+        CoordinateManager.batch_rows and batch_chunks.  A (b, q) without an unblocked row: out = 0, lse = 0."""
+        queries, k, v, V, B, Q, d = self._qattn_check(queries, k, v, mask, row_map, H)
+        order, seg_start, chunk_seg, chunk_first, chunks = self._qattn_group(group, V, B)
+        dev = k.device
+        out = torch.empty((B, Q, k.size(1)), dtype=torch.float32, device=dev)
+        lse = torch.empty((B, Q, H), dtype=torch.float32, device=dev)
+        ws = self.ws.get("qattn", 4 * self.lib.ms3d_qattn_ws_floats(C.c_long(chunks), int(Q), int(H), int(d)), dev)
+        _lib.check(self.lib.ms3d_qattn_forward(_lib.ptr(queries), _lib.ptr(k), _lib.ptr(v), _lib.ptr(mask), _lib.ptr(row_map),
+                                               _lib.ptr(order), _lib.ptr(seg_start), _lib.ptr(chunk_seg), _lib.ptr(chunk_first),
+                                               C.c_long(V), int(B), int(chunks), int(Q), int(H), int(d), C.c_float(scale),
+                                               _lib.ptr(out), _lib.ptr(lse), _lib.ptr(ws), C.c_size_t(ws.numel() // 4),
+                                               _lib.stream_handle()), "ms3d_qattn_forward")
+        return out, lse
+
+    def qattn_backward_q(self, queries, k, v, mask, row_map, group, out, lse, dout, H, scale, need_dq=True):
+        """-> (dq [B, Q, C] or None, delta [B, Q, H]); delta, the residual sum_i p <dout, v - out> per query and head, is what
+        qattn_backward_kv reads.  One partial per chunk, added in chunk order."""
+        queries, k, v, V, B, Q, d = self._qattn_check(queries, k, v, mask, row_map, H)
+        order, seg_start, chunk_seg, chunk_first, chunks = self._qattn_group(group, V, B)
+        dout = self._dev(dout)
+        assert tuple(dout.shape) == tuple(queries.shape) == tuple(out.shape) and dout.dtype == torch.float32
+        dev = k.device
+        dq = torch.empty_like(queries) if need_dq else None
+        delta = torch.empty((B, Q, H), dtype=torch.float32, device=dev)
+        ws = self.ws.get("qattn", 4 * self.lib.ms3d_qattn_backward_ws_floats(C.c_long(chunks), int(Q), int(H), int(d)), dev)
+        _lib.check(self.lib.ms3d_qattn_backward_q(_lib.ptr(queries), _lib.ptr(k), _lib.ptr(v), _lib.ptr(mask), _lib.ptr(row_map),
+                                                  _lib.ptr(order), _lib.ptr(seg_start), _lib.ptr(chunk_seg),
+                                                  _lib.ptr(chunk_first), _lib.ptr(out), _lib.ptr(lse), _lib.ptr(dout),
+                                                  C.c_long(V), int(B), int(chunks), int(Q), int(H), int(d), C.c_float(scale),
+                                                  _lib.ptr(dq), _lib.ptr(delta), _lib.ptr(ws), C.c_size_t(ws.numel() // 4),
+                                                  _lib.stream_handle()), "ms3d_qattn_backward_q")
+        return dq, delta
+
+    def qattn_backward_kv(self, queries, k, v, mask, row_map, seg_of_row, out, lse, delta, dout, H, scale, need_dk=True,
+                          need_dv=True):
+        """-> (dk, dv) [V, C] (None where not asked for): every row loops over the queries of its sample seg_of_row[i]
+        (CoordinateManager.batch_segments) in ascending order"""
+        queries, k, v, V, B, Q, d = self._qattn_check(queries, k, v, mask, row_map, H)
+        dout = self._dev(dout)
+        assert tuple(dout.shape) == tuple(queries.shape) == tuple(out.shape) and (need_dk or need_dv)
+        assert seg_of_row.dtype == torch.int32 and seg_of_row.is_contiguous() and seg_of_row.numel() == V
+        dk = torch.empty_like(k) if need_dk else None
+        dv = torch.empty_like(v) if need_dv else None
+        _lib.check(self.lib.ms3d_qattn_backward_kv(_lib.ptr(queries), _lib.ptr(k), _lib.ptr(v), _lib.ptr(mask), _lib.ptr(row_map),
+                                                   _lib.ptr(seg_of_row), _lib.ptr(out), _lib.ptr(lse), _lib.ptr(delta),
+                                                   _lib.ptr(dout), C.c_long(V), int(B), int(Q), int(H), int(d),
+                                                   C.c_float(scale), _lib.ptr(dk), _lib.ptr(dv), _lib.stream_handle()),
+                   "ms3d_qattn_backward_kv")
+        return dk, dv
+
     # ---- instance normalisation over the batch grouping of a coordinate set (csrc/inorm.hip)
     def _inorm_check(self, x, order, seg_start, seg_of_row):
         assert x.dtype == torch.float32 and x.dim() == 2
