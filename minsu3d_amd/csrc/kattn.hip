@@ -13,23 +13,11 @@
 //                KATTN_ROWS_PER_PART output rows, then the partials added in ascending part order; writes delta [Vout, H]
 //   backward_kv  a gather through the inverse table (o = nbr_inv[kk][i], the offset index NOT mirrored): dv += p dout[o],
 //                dk += scale * ds q[o], p and ds recomputed from q[o], k[i], v[i], rel_bias, lse[o], out[o], delta[o]
-// The textbook ds = p (<dout, v> - <dout, out>) subtracts two dot products that agree in every digit float32 keeps when one
-// input carries almost all of a row's weight (out is then that input's v): what is left is rounding noise of the size of
-// <dout, v>, not of ds, and it lands on the pair whose p is 1.  Here the difference is taken per channel BEFORE the dot
-// product, e = <dout, v - out> (v - out is exact where it is small), and what the float32 rounding of the saved `out` still
-// costs is measured and taken back: sum_kk p e would be zero for the exact out, so delta[o, h] = sum_kk p e is the
-// residual, and ds = p (e - delta).  The ds of a row then sum to zero as they must, and each keeps its relative accuracy.
-// In the q pass delta is known only after the sweep: dq = scale (sum ds' k - delta sum p k) with ds' = p e, both sums
-// kept per lane, and the dbias sums are corrected from the row's p, stashed in LDS.
+// Why ds is formed as p (e - delta) with e = <dout, v - out> is told in csrc/attn_core.h.  In the q pass delta is known only
+// after the sweep, so the dbias sums are taken over ds' = p e and corrected from the row's p, stashed in LDS.
 //
-// Layout: the work item is one (row, head).  A GROUP of G lanes (a power of two, <= 64, so a group never straddles a wave)
-// holds the D channels of that head: lane l the channels (it * G + l) * VEC + j, VEC = 4 (16-byte accesses: D % 4 == 0 and
-// 16-byte aligned rows) or 1 (any D, two rounds when D > 64).  Consecutive groups take consecutive heads of one row, so a
-// wave reads whole runs of a row, and 64 / G items share a wave when D is small.  A head's dot product is summed inside
-// its group by an xor butterfly, which leaves the same bits on every lane of the group.  The K table entries of a row are
-// read four at a time so that eight row gathers are in flight per lane.  No lane leaves before the last shuffle: a lane
-// without work runs the loops with every load switched off.
-#include "common.h"
+// Lane layout, accumulation steps and the four-row gather stages: csrc/attn_core.h.  Here a row's four are four K table entries.
+#include "attn_core.h"
 #include "../../include/minsu3d_hip.h"
 
 namespace {
@@ -40,77 +28,6 @@ constexpr int KATTN_THREADS = 256;
 constexpr int KATTN_ROWS_PER_PART = 64;   // output rows per dbias partial: a constant of the library, NOT derived from the
                                           // grid or the CU count -- the order of the sum is the same on every machine
 constexpr int KATTN_DB_FLOATS = 16384;    // LDS floats (64 KiB) of a backward_q workgroup's dbias sums: [groups][K]
-
-template <int VEC> struct Lane { static constexpr int NIT = VEC == 4 ? 1 : 2, N = NIT * VEC; };
-
-// the group size of a head: the smallest power of two that covers D / VEC lanes, 64 at most
-int group_of(int D, int VEC)
-{
-    const int n = (D + VEC - 1) / VEC;
-    int G = 1;
-    while (G < n && G < 64) G *= 2;
-    return G;
-}
-
-bool aligned16(const void *p) { return ((uintptr_t)p & 15) == 0; }
-
-// the slice of a head this lane holds: x[it * VEC + j] = p[(it * G + l) * VEC + j], zero past D or with the load off
-template <int VEC>
-__device__ __forceinline__ void load_slice(const float *__restrict__ p, int l, int G, int D, bool on, float (&x)[Lane<VEC>::N])
-{
-#pragma unroll
-    for (int it = 0; it < Lane<VEC>::NIT; it++) {
-        const int d0 = (it * G + l) * VEC;
-        if constexpr (VEC == 4) {
-            float4 r = make_float4(0.f, 0.f, 0.f, 0.f);
-            if (on && d0 < D) r = *reinterpret_cast<const float4 *>(p + d0);
-            x[it * 4 + 0] = r.x; x[it * 4 + 1] = r.y; x[it * 4 + 2] = r.z; x[it * 4 + 3] = r.w;
-        } else {
-            x[it] = (on && d0 < D) ? p[d0] : 0.f;
-        }
-    }
-}
-
-template <int VEC>
-__device__ __forceinline__ void store_slice(float *__restrict__ p, int l, int G, int D, bool on, const float (&x)[Lane<VEC>::N])
-{
-#pragma unroll
-    for (int it = 0; it < Lane<VEC>::NIT; it++) {
-        const int d0 = (it * G + l) * VEC;
-        if (!on || d0 >= D) continue;
-        if constexpr (VEC == 4)
-            *reinterpret_cast<float4 *>(p + d0) = make_float4(x[it * 4 + 0], x[it * 4 + 1], x[it * 4 + 2], x[it * 4 + 3]);
-        else
-            p[d0] = x[it];
-    }
-}
-
-// this lane's share of <a, b>: explicit fmaf in one order, so that all three kernels recompute a score to the same bits
-template <int N>
-__device__ __forceinline__ float dot_slice(const float (&a)[N], const float (&b)[N])
-{
-    float s = a[0] * b[0];
-#pragma unroll
-    for (int j = 1; j < N; j++) s = fmaf(a[j], b[j], s);
-    return s;
-}
-
-// this lane's share of <a, b - c>
-template <int N>
-__device__ __forceinline__ float dot_diff(const float (&a)[N], const float (&b)[N], const float (&c)[N])
-{
-    float s = a[0] * (b[0] - c[0]);
-#pragma unroll
-    for (int j = 1; j < N; j++) s = fmaf(a[j], b[j] - c[j], s);
-    return s;
-}
-
-// sum over the G lanes of a group (G a power of two, the group aligned to G): every lane ends with the same bits
-__device__ __forceinline__ float group_sum(float x, int G)
-{
-    for (int d = G >> 1; d >= 1; d >>= 1) x += __shfl_xor(x, d, 64);
-    return x;
-}
 
 // One group: the item (o, h) = blockIdx.x * (256 / G) + group.  Online softmax over ascending kk.
 template <int VEC>
@@ -126,6 +43,7 @@ __global__ __launch_bounds__(KATTN_THREADS) void kattn_forward_kernel(
     const int o = on ? (int)(item / H) : 0;
     const int h = on ? (int)(item - (long)o * H) : 0;
     const size_t C = (size_t)H * D, hoff = (size_t)h * D;
+    const Item it{C, hoff, H, h, l, G, D};
     float qv[N], acc[N];
     load_slice<VEC>(q + (size_t)o * C + hoff, l, G, D, on, qv);
 #pragma unroll
@@ -136,31 +54,17 @@ __global__ __launch_bounds__(KATTN_THREADS) void kattn_forward_kernel(
         float kr[4][N], vr[4][N], dot[4];
 #pragma unroll
         for (int u = 0; u < 4; u++) idx[u] = (on && k0 + u < K) ? nbr[(size_t)(k0 + u) * Vout + o] : -1;
-#pragma unroll
-        for (int u = 0; u < 4; u++) {
-            const size_t row = (size_t)(idx[u] >= 0 ? idx[u] : 0) * C + hoff;
-            load_slice<VEC>(k + row, l, G, D, idx[u] >= 0, kr[u]);
-            load_slice<VEC>(v + row, l, G, D, idx[u] >= 0, vr[u]);
-        }
-#pragma unroll
-        for (int u = 0; u < 4; u++) dot[u] = group_sum(dot_slice<N>(qv, kr[u]), G);
+        key_stage<VEC>(k, v, idx, it, qv, kr, vr, dot);
 #pragma unroll
         for (int u = 0; u < 4; u++) {
             if (idx[u] < 0) continue;
             const float s = fmaf(scale, dot[u], bias ? bias[(size_t)(k0 + u) * H + h] : 0.f);
-            const float mn = fmaxf(m, s);
-            const float c = expf(m - mn), p = expf(s - mn);          // (m = -inf on the first input: c = 0)
-            sum = fmaf(sum, c, p);
-#pragma unroll
-            for (int j = 0; j < N; j++) acc[j] = fmaf(acc[j], c, p * vr[u][j]);
-            m = mn;
+            push_softmax(s, vr[u], m, sum, acc);
         }
     }
-    const float inv = sum > 0.f ? 1.f / sum : 0.f;                   // one input: sum = 1, out = v to the bit
-#pragma unroll
-    for (int j = 0; j < N; j++) acc[j] *= inv;
+    const float ls = finish_softmax(m, sum, acc);
     store_slice<VEC>(out + (size_t)o * C + hoff, l, G, D, on, acc);
-    if (on && l == 0) lse[(size_t)o * H + h] = sum > 0.f ? m + logf(sum) : 0.f;
+    if (on && l == 0) lse[(size_t)o * H + h] = ls;
 }
 
 // One workgroup: the part blockIdx.x (KATTN_ROWS_PER_PART consecutive output rows) and the head tile blockIdx.y (HB heads).
@@ -186,6 +90,7 @@ __global__ __launch_bounds__(KATTN_THREADS) void kattn_backward_q_kernel(
     const int h = h0 + (hl < HBt ? hl : 0);
     const bool lane_on = rl < RG && hl < HBt;
     const size_t C = (size_t)H * D, hoff = (size_t)h * D;
+    const Item it{C, hoff, H, h, l, G, D};
     if (partial) {
         for (int e = threadIdx.x; e < GPB * K; e += T) s_db[e] = 0.f;
         __syncthreads();
@@ -208,17 +113,7 @@ __global__ __launch_bounds__(KATTN_THREADS) void kattn_backward_q_kernel(
             float kr[4][N], vr[4][N], dot[4], dp[4];
 #pragma unroll
             for (int u = 0; u < 4; u++) idx[u] = (on && k0 + u < K) ? nbr[(size_t)(k0 + u) * Vout + o] : -1;
-#pragma unroll
-            for (int u = 0; u < 4; u++) {
-                const size_t row = (size_t)(idx[u] >= 0 ? idx[u] : 0) * C + hoff;
-                load_slice<VEC>(k + row, l, G, D, idx[u] >= 0, kr[u]);
-                load_slice<VEC>(v + row, l, G, D, idx[u] >= 0, vr[u]);
-            }
-#pragma unroll
-            for (int u = 0; u < 4; u++) {
-                dot[u] = group_sum(dot_slice<N>(qv, kr[u]), G);
-                dp[u] = group_sum(dot_diff<N>(dov, vr[u], ov), G);
-            }
+            key_stage<VEC>(k, v, idx, it, qv, dov, ov, kr, vr, dot, dp);
 #pragma unroll
             for (int u = 0; u < 4; u++) {
                 const int kk = k0 + u;
@@ -226,13 +121,7 @@ __global__ __launch_bounds__(KATTN_THREADS) void kattn_backward_q_kernel(
                 if (idx[u] >= 0) {
                     const float s = fmaf(scale, dot[u], bias ? bias[(size_t)kk * H + h] : 0.f);
                     p = expf(s - ls);
-                    ds = p * dp[u];
-                    dl += ds;
-#pragma unroll
-                    for (int j = 0; j < N; j++) {
-                        acc[j] = fmaf(ds, kr[u][j], acc[j]);
-                        pk[j] = fmaf(p, kr[u][j], pk[j]);
-                    }
+                    ds = push_dq(p, dp[u], kr[u], dl, acc, pk);
                 }
                 if (partial && kk < K && l == (kk & (G - 1))) {      // (this lane is the only one that touches offset kk)
                     s_db[g * K + kk] += ds;
@@ -287,41 +176,29 @@ __global__ __launch_bounds__(KATTN_THREADS) void kattn_backward_kv_kernel(
     const int i = on ? (int)(item / H) : 0;
     const int h = on ? (int)(item - (long)i * H) : 0;
     const size_t C = (size_t)H * D, hoff = (size_t)h * D;
+    const Item it{C, hoff, H, h, l, G, D};
     float kv[N], vv[N], ak[N], av[N];
     load_slice<VEC>(k + (size_t)i * C + hoff, l, G, D, on, kv);
     load_slice<VEC>(v + (size_t)i * C + hoff, l, G, D, on, vv);
 #pragma unroll
     for (int j = 0; j < N; j++) ak[j] = av[j] = 0.f;
     for (int k0 = 0; k0 < K; k0 += 4) {
-        int idx[4];
-        float qr[4][N], dr[4][N], orow[4][N], dot[4], dp[4], ls[4], dl[4];
-#pragma unroll
-        for (int u = 0; u < 4; u++) idx[u] = (on && k0 + u < K) ? nbr_inv[(size_t)(k0 + u) * Vin + i] : -1;
+        bool live[4];
+        size_t o[4];
+        float qr[4][N], dr[4][N], dot[4], dp[4], ls[4], dl[4];
 #pragma unroll
         for (int u = 0; u < 4; u++) {
-            const size_t o = (size_t)(idx[u] >= 0 ? idx[u] : 0);
-            load_slice<VEC>(q + o * C + hoff, l, G, D, idx[u] >= 0, qr[u]);
-            load_slice<VEC>(dout + o * C + hoff, l, G, D, idx[u] >= 0, dr[u]);
-            load_slice<VEC>(out + o * C + hoff, l, G, D, idx[u] >= 0, orow[u]);
-            ls[u] = idx[u] >= 0 ? lse[o * H + h] : 0.f;
-            dl[u] = idx[u] >= 0 ? delta[o * H + h] : 0.f;
+            const int idx = (on && k0 + u < K) ? nbr_inv[(size_t)(k0 + u) * Vin + i] : -1;
+            live[u] = idx >= 0;
+            o[u] = (size_t)(live[u] ? idx : 0);
         }
+        query_stage<VEC>(q, dout, out, lse, delta, o, live, it, kv, vv, qr, dr, ls, dl, dot, dp);
 #pragma unroll
         for (int u = 0; u < 4; u++) {
-            dot[u] = group_sum(dot_slice<N>(qr[u], kv), G);
-            dp[u] = group_sum(dot_diff<N>(dr[u], vv, orow[u]), G);
-        }
-#pragma unroll
-        for (int u = 0; u < 4; u++) {
-            if (idx[u] < 0) continue;
+            if (!live[u]) continue;
             const float s = fmaf(scale, dot[u], bias ? bias[(size_t)(k0 + u) * H + h] : 0.f);
             const float p = expf(s - ls[u]);
-            const float ds = p * (dp[u] - dl[u]);
-#pragma unroll
-            for (int j = 0; j < N; j++) {
-                av[j] = fmaf(p, dr[u][j], av[j]);
-                ak[j] = fmaf(ds, qr[u][j], ak[j]);
-            }
+            push_dkv(p, p * (dp[u] - dl[u]), dr[u], qr[u], av, ak);
         }
     }
 #pragma unroll
@@ -362,15 +239,12 @@ int ms3d_kattn_forward(const float *q, const float *k, const float *v, const flo
     if (shape_check(K, H, D)) return MS3D_E_UNSUPPORTED;
     if (Vout <= 0) return 0;
     if (!q || !k || !v || !nbr || !out || !lse) return MS3D_E_UNSUPPORTED;
-    const bool v4 = D % 4 == 0 && aligned16(q) && aligned16(k) && aligned16(v) && aligned16(out);
+    const bool v4 = D % 4 == 0 && aligned16(q, k, v, out);
     const int G = group_of(D, v4 ? 4 : 1);
     const long per = KATTN_THREADS / G, blocks = ((long)Vout * H + per - 1) / per;
     if (blocks > 0x7fffffffL) return MS3D_E_UNSUPPORTED;
-    if (v4) kattn_forward_kernel<4><<<(unsigned)blocks, KATTN_THREADS, 0, stream>>>(q, k, v, rel_bias, nbr, Vout, K, H, D, G,
-                                                                                   scale, out, lse);
-    else kattn_forward_kernel<1><<<(unsigned)blocks, KATTN_THREADS, 0, stream>>>(q, k, v, rel_bias, nbr, Vout, K, H, D, G,
-                                                                                scale, out, lse);
-    MS3D_LAUNCH_CHECK();
+    ATTN_LAUNCH(v4, kattn_forward_kernel, (unsigned)blocks, KATTN_THREADS, 0, stream, q, k, v, rel_bias, nbr, Vout, K, H, D, G,
+                scale, out, lse);
     return 0;
 }
 
@@ -384,8 +258,7 @@ int ms3d_kattn_backward_q(const float *q, const float *k, const float *v, const 
     if (!q || !k || !v || !nbr || !out || !lse || !dout || !delta) return MS3D_E_UNSUPPORTED;
     if (dbias && (!rel_bias || !partial_ws)) return MS3D_E_UNSUPPORTED;
     if (dbias && ws_floats < ms3d_kattn_dbias_ws_floats(Vout, K, H)) return MS3D_E_WORKSPACE;
-    const bool v4 = D % 4 == 0 && aligned16(q) && aligned16(k) && aligned16(v) && aligned16(out) && aligned16(dout) &&
-                    (!dq || aligned16(dq));
+    const bool v4 = D % 4 == 0 && aligned16(q, k, v, out, dout, dq);
     const int G = group_of(D, v4 ? 4 : 1);
     int GPB = KATTN_THREADS / G;                                      // groups of a workgroup: a power of two
     if (dbias)
@@ -397,11 +270,8 @@ int ms3d_kattn_backward_q(const float *q, const float *k, const float *v, const 
     const int T = GPB * G;
     const size_t lds = dbias ? sizeof(float) * 2 * (size_t)GPB * K : 0;
     float *partial = dbias ? partial_ws : nullptr;
-    if (v4) kattn_backward_q_kernel<4><<<grid, T, lds, stream>>>(q, k, v, rel_bias, nbr, out, lse, dout, Vout, K, H, D, G, HB, RG,
-                                                                 scale, dq, delta, partial);
-    else kattn_backward_q_kernel<1><<<grid, T, lds, stream>>>(q, k, v, rel_bias, nbr, out, lse, dout, Vout, K, H, D, G, HB, RG,
-                                                              scale, dq, delta, partial);
-    MS3D_LAUNCH_CHECK();
+    ATTN_LAUNCH(v4, kattn_backward_q_kernel, grid, T, lds, stream, q, k, v, rel_bias, nbr, out, lse, dout, Vout, K, H, D, G, HB,
+                RG, scale, dq, delta, partial);
     if (dbias) {
         const int n = K * H;
         kattn_dbias_reduce_kernel<<<ms3d_divup(n, 256), 256, 0, stream>>>(partial_ws, parts, n, dbias);
@@ -418,17 +288,12 @@ int ms3d_kattn_backward_kv(const float *q, const float *k, const float *v, const
     if (shape_check(K, H, D)) return MS3D_E_UNSUPPORTED;
     if (Vin <= 0) return 0;
     if (!q || !k || !v || !nbr_inv || !out || !lse || !delta || !dout || (!dk && !dv)) return MS3D_E_UNSUPPORTED;
-    const bool v4 = D % 4 == 0 && aligned16(q) && aligned16(k) && aligned16(v) && aligned16(out) && aligned16(dout) &&
-                    (!dk || aligned16(dk)) &&
-                    (!dv || aligned16(dv));
+    const bool v4 = D % 4 == 0 && aligned16(q, k, v, out, dout, dk, dv);
     const int G = group_of(D, v4 ? 4 : 1);
     const long per = KATTN_THREADS / G, blocks = ((long)Vin * H + per - 1) / per;
     if (blocks > 0x7fffffffL) return MS3D_E_UNSUPPORTED;
-    if (v4) kattn_backward_kv_kernel<4><<<(unsigned)blocks, KATTN_THREADS, 0, stream>>>(q, k, v, rel_bias, nbr_inv, out, lse,
-                                                                                       delta, dout, Vin, K, H, D, G, scale, dk, dv);
-    else kattn_backward_kv_kernel<1><<<(unsigned)blocks, KATTN_THREADS, 0, stream>>>(q, k, v, rel_bias, nbr_inv, out, lse,
-                                                                                    delta, dout, Vin, K, H, D, G, scale, dk, dv);
-    MS3D_LAUNCH_CHECK();
+    ATTN_LAUNCH(v4, kattn_backward_kv_kernel, (unsigned)blocks, KATTN_THREADS, 0, stream, q, k, v, rel_bias, nbr_inv, out, lse,
+                delta, dout, Vin, K, H, D, G, scale, dk, dv);
     return 0;
 }
 

@@ -16,19 +16,16 @@
 //                ascending position, a partial (m, l, acc[D]) per item; the merge kernel folds the partials of a sample in
 //                ascending chunk order and writes out and lse
 //   backward_q   the same sweep with p = exp(s - lse) recomputed: per chunk sum p e k, sum p k and sum p e with
-//                e = <dout, v - out> taken per channel before the sum (see csrc/kattn.hip for why); the merge adds the chunks in
+//                e = <dout, v - out> taken per channel before the sum (see csrc/attn_core.h for why); the merge adds the chunks in
 //                ascending order, delta[b, q, h] = sum_i p e, dq = scale (sum p e k - delta sum p k)
 //   backward_kv  one (row, head) item per voxel row loops over the Q queries of its sample in ascending q: dv = sum p dout,
 //                dk = scale sum p (e - delta) q; one writer per element, no partials
 // No atomics of any kind, one writer per element, the same bytes on every run.
 //
-// Lane layout (that of csrc/kattn.hip): an item is served by a GROUP of G lanes (a power of two <= 64, never straddling a
-// wave) that hold the D channels of the head: lane l the channels (it * G + l) * VEC + j, VEC = 4 (16-byte accesses: D % 4 == 0
-// and 16-byte aligned rows) or 1 (any D, two rounds when D > 64).  A head's dot product is an xor butterfly inside its group,
-// which leaves the same bits on every lane.  Rows are taken four at a time so that eight row loads are in flight per lane; every
-// group of a workgroup walks the same rows, so they come from the cache.  No lane leaves before the last shuffle: a lane
-// without work runs the loops with every load switched off.
-#include "common.h"
+// Lane layout, accumulation steps and the four-row gather stages: csrc/attn_core.h.  Here an item is a (query, head) in the
+// sweeps and a (held row, head) in backward_kv; every group of a sweep's workgroup walks the same rows, so they come from the
+// cache.
+#include "attn_core.h"
 #include "../../include/minsu3d_hip.h"
 
 namespace {
@@ -40,77 +37,6 @@ constexpr int QATTN_MAX_B = 65535;
 constexpr int QATTN_THREADS = 256;
 constexpr int QATTN_ROWS_PER_CHUNK = 512;  // positions of `order` per chunk: a constant of the library, NOT derived from the
                                            // grid or the CU count -- the order of every sum is the same on every machine
-
-template <int VEC> struct Lane { static constexpr int NIT = VEC == 4 ? 1 : 2, N = NIT * VEC; };
-
-// the group size of a head: the smallest power of two that covers D / VEC lanes, 64 at most
-int group_of(int D, int VEC)
-{
-    const int n = (D + VEC - 1) / VEC;
-    int G = 1;
-    while (G < n && G < 64) G *= 2;
-    return G;
-}
-
-bool aligned16(const void *p) { return ((uintptr_t)p & 15) == 0; }
-
-// the slice of a head this lane holds: x[it * VEC + j] = p[(it * G + l) * VEC + j], zero past D or with the load off
-template <int VEC>
-__device__ __forceinline__ void load_slice(const float *__restrict__ p, int l, int G, int D, bool on, float (&x)[Lane<VEC>::N])
-{
-#pragma unroll
-    for (int it = 0; it < Lane<VEC>::NIT; it++) {
-        const int d0 = (it * G + l) * VEC;
-        if constexpr (VEC == 4) {
-            float4 r = make_float4(0.f, 0.f, 0.f, 0.f);
-            if (on && d0 < D) r = *reinterpret_cast<const float4 *>(p + d0);
-            x[it * 4 + 0] = r.x; x[it * 4 + 1] = r.y; x[it * 4 + 2] = r.z; x[it * 4 + 3] = r.w;
-        } else {
-            x[it] = (on && d0 < D) ? p[d0] : 0.f;
-        }
-    }
-}
-
-template <int VEC>
-__device__ __forceinline__ void store_slice(float *__restrict__ p, int l, int G, int D, bool on, const float (&x)[Lane<VEC>::N])
-{
-#pragma unroll
-    for (int it = 0; it < Lane<VEC>::NIT; it++) {
-        const int d0 = (it * G + l) * VEC;
-        if (!on || d0 >= D) continue;
-        if constexpr (VEC == 4)
-            *reinterpret_cast<float4 *>(p + d0) = make_float4(x[it * 4 + 0], x[it * 4 + 1], x[it * 4 + 2], x[it * 4 + 3]);
-        else
-            p[d0] = x[it];
-    }
-}
-
-// this lane's share of <a, b>: explicit fmaf in one order, so that all three sweeps recompute a score to the same bits
-template <int N>
-__device__ __forceinline__ float dot_slice(const float (&a)[N], const float (&b)[N])
-{
-    float s = a[0] * b[0];
-#pragma unroll
-    for (int j = 1; j < N; j++) s = fmaf(a[j], b[j], s);
-    return s;
-}
-
-// this lane's share of <a, b - c>
-template <int N>
-__device__ __forceinline__ float dot_diff(const float (&a)[N], const float (&b)[N], const float (&c)[N])
-{
-    float s = a[0] * (b[0] - c[0]);
-#pragma unroll
-    for (int j = 1; j < N; j++) s = fmaf(a[j], b[j] - c[j], s);
-    return s;
-}
-
-// sum over the G lanes of a group (G a power of two, the group aligned to G): every lane ends with the same bits
-__device__ __forceinline__ float group_sum(float x, int G)
-{
-    for (int d = G >> 1; d >= 1; d >>= 1) x += __shfl_xor(x, d, 64);
-    return x;
-}
 
 // what every kernel is told about the call
 struct Shape {
@@ -125,6 +51,21 @@ __device__ __forceinline__ void chunk_range(const int *__restrict__ seg_start, c
     b = chunk_seg[c];
     p0 = (long)seg_start[b] + (long)(c - chunk_first[b]) * QATTN_ROWS_PER_CHUNK;
     p1 = min(p0 + QATTN_ROWS_PER_CHUNK, (long)seg_start[b + 1]);
+}
+
+// the held rows at the positions r0 .. r0 + 3 of `order` that query q may attend to; -1 past p1, where the mask blocks, or off
+__device__ __forceinline__ void rows_of_query(const long long *__restrict__ order, const unsigned char *__restrict__ mask,
+                                              const int *__restrict__ row_map, long r0, long p1, bool on, int Q, int q,
+                                              long (&idx)[4])
+{
+#pragma unroll
+    for (int u = 0; u < 4; u++) {
+        idx[u] = (on && r0 + u < p1) ? (long)order[r0 + u] : -1;
+        if (idx[u] >= 0 && mask) {
+            const size_t mr = row_map ? (size_t)row_map[idx[u]] : (size_t)idx[u];
+            if (mask[mr * Q + q]) idx[u] = -1;
+        }
+    }
 }
 
 // Forward sweep.  Workgroup (blockIdx.x = chunk, blockIdx.y = item tile); group g takes the item blockIdx.y * (256 / G) + g of
@@ -147,6 +88,7 @@ __global__ __launch_bounds__(QATTN_THREADS) void qattn_forward_kernel(
     int b;
     long p0, p1;
     chunk_range(seg_start, chunk_seg, chunk_first, c, b, p0, p1);
+    const Item it{C, hoff, H, h, l, G, D};
     float qv[N], acc[N];
     load_slice<VEC>(queries + ((size_t)b * Q + q) * C + hoff, l, G, D, on, qv);
 #pragma unroll
@@ -155,32 +97,12 @@ __global__ __launch_bounds__(QATTN_THREADS) void qattn_forward_kernel(
     for (long r0 = p0; r0 < p1; r0 += 4) {
         long idx[4];
         float kr[4][N], vr[4][N], dot[4];
-#pragma unroll
-        for (int u = 0; u < 4; u++) {
-            idx[u] = (on && r0 + u < p1) ? (long)order[r0 + u] : -1;
-            if (idx[u] >= 0 && mask) {
-                const size_t mr = row_map ? (size_t)row_map[idx[u]] : (size_t)idx[u];
-                if (mask[mr * Q + q]) idx[u] = -1;
-            }
-        }
-#pragma unroll
-        for (int u = 0; u < 4; u++) {
-            const size_t row = (size_t)(idx[u] >= 0 ? idx[u] : 0) * C + hoff;
-            load_slice<VEC>(k + row, l, G, D, idx[u] >= 0, kr[u]);
-            load_slice<VEC>(v + row, l, G, D, idx[u] >= 0, vr[u]);
-        }
-#pragma unroll
-        for (int u = 0; u < 4; u++) dot[u] = group_sum(dot_slice<N>(qv, kr[u]), G);
+        rows_of_query(order, mask, row_map, r0, p1, on, Q, q, idx);
+        key_stage<VEC>(k, v, idx, it, qv, kr, vr, dot);
 #pragma unroll
         for (int u = 0; u < 4; u++) {
             if (idx[u] < 0) continue;
-            const float s = sh.scale * dot[u];
-            const float mn = fmaxf(m, s);
-            const float cf = expf(m - mn), p = expf(s - mn);         // (m = -inf on the first row: cf = 0)
-            sum = fmaf(sum, cf, p);
-#pragma unroll
-            for (int j = 0; j < N; j++) acc[j] = fmaf(acc[j], cf, p * vr[u][j]);
-            m = mn;
+            push_softmax(sh.scale * dot[u], vr[u], m, sum, acc);
         }
     }
     store_slice<VEC>(w_acc + ((size_t)c * Q + q) * C + hoff, l, G, D, on, acc);
@@ -222,11 +144,9 @@ __global__ __launch_bounds__(QATTN_THREADS) void qattn_forward_merge_kernel(
             for (int j = 0; j < N; j++) acc[j] = fmaf(a[j], w, acc[j]);
         }
     }
-    const float inv = sum > 0.f ? 1.f / sum : 0.f;
-#pragma unroll
-    for (int j = 0; j < N; j++) acc[j] *= inv;
+    const float ls = finish_softmax(M, sum, acc);
     store_slice<VEC>(out + ((size_t)b * Q + q) * C + hoff, l, G, D, true, acc);
-    if (l == 0) lse[(size_t)b * QH + item] = sum > 0.f ? M + logf(sum) : 0.f;
+    if (l == 0) lse[(size_t)b * QH + item] = ls;
 }
 
 // Backward sweep for the queries: the forward's walk with p = exp(s - lse).  Partials: w_a [chunks][Q][C] = sum p e k,
@@ -251,6 +171,7 @@ __global__ __launch_bounds__(QATTN_THREADS) void qattn_backward_q_kernel(
     long p0, p1;
     chunk_range(seg_start, chunk_seg, chunk_first, c, b, p0, p1);
     const size_t qrow = ((size_t)b * Q + q) * C + hoff;
+    const Item it{C, hoff, H, h, l, G, D};
     float qv[N], dov[N], ov[N], acc[N], pk[N];
     load_slice<VEC>(queries + qrow, l, G, D, on, qv);
     load_slice<VEC>(dout + qrow, l, G, D, on, dov);
@@ -262,36 +183,12 @@ __global__ __launch_bounds__(QATTN_THREADS) void qattn_backward_q_kernel(
     for (long r0 = p0; r0 < p1; r0 += 4) {
         long idx[4];
         float kr[4][N], vr[4][N], dot[4], dp[4];
-#pragma unroll
-        for (int u = 0; u < 4; u++) {
-            idx[u] = (on && r0 + u < p1) ? (long)order[r0 + u] : -1;
-            if (idx[u] >= 0 && mask) {
-                const size_t mr = row_map ? (size_t)row_map[idx[u]] : (size_t)idx[u];
-                if (mask[mr * Q + q]) idx[u] = -1;
-            }
-        }
-#pragma unroll
-        for (int u = 0; u < 4; u++) {
-            const size_t row = (size_t)(idx[u] >= 0 ? idx[u] : 0) * C + hoff;
-            load_slice<VEC>(k + row, l, G, D, idx[u] >= 0, kr[u]);
-            load_slice<VEC>(v + row, l, G, D, idx[u] >= 0, vr[u]);
-        }
-#pragma unroll
-        for (int u = 0; u < 4; u++) {
-            dot[u] = group_sum(dot_slice<N>(qv, kr[u]), G);
-            dp[u] = group_sum(dot_diff<N>(dov, vr[u], ov), G);
-        }
+        rows_of_query(order, mask, row_map, r0, p1, on, Q, q, idx);
+        key_stage<VEC>(k, v, idx, it, qv, dov, ov, kr, vr, dot, dp);
 #pragma unroll
         for (int u = 0; u < 4; u++) {
             if (idx[u] < 0) continue;
-            const float p = expf(sh.scale * dot[u] - ls);
-            const float ds = p * dp[u];
-            dl += ds;
-#pragma unroll
-            for (int j = 0; j < N; j++) {
-                acc[j] = fmaf(ds, kr[u][j], acc[j]);
-                pk[j] = fmaf(p, kr[u][j], pk[j]);
-            }
+            push_dq(expf(sh.scale * dot[u] - ls), dp[u], kr[u], dl, acc, pk);
         }
     }
     if (rows) {
@@ -358,6 +255,7 @@ __global__ __launch_bounds__(QATTN_THREADS) void qattn_backward_kv_kernel(
     const int b = on ? seg_of_row[i] : 0;
     const unsigned char *__restrict__ mrow =
         (on && mask) ? mask + (row_map ? (size_t)row_map[i] : (size_t)i) * Q : nullptr;
+    const Item it{C, hoff, H, h, l, G, D};
     float kv[N], vv[N], ak[N], av[N];
     load_slice<VEC>(k + (size_t)i * C + hoff, l, G, D, on, kv);
     load_slice<VEC>(v + (size_t)i * C + hoff, l, G, D, on, vv);
@@ -365,32 +263,19 @@ __global__ __launch_bounds__(QATTN_THREADS) void qattn_backward_kv_kernel(
     for (int j = 0; j < N; j++) ak[j] = av[j] = 0.f;
     for (int q0 = 0; q0 < Q; q0 += 4) {
         bool live[4];
-        float qr[4][N], dr[4][N], orow[4][N], dot[4], dp[4], ls[4], dl[4];
+        size_t qh[4];
+        float qr[4][N], dr[4][N], dot[4], dp[4], ls[4], dl[4];
 #pragma unroll
         for (int u = 0; u < 4; u++) {
             live[u] = on && q0 + u < Q && !(mrow && mrow[q0 + u]);
-            const size_t qh = ((size_t)b * Q + (live[u] ? q0 + u : 0));
-            load_slice<VEC>(queries + qh * C + hoff, l, G, D, live[u], qr[u]);
-            load_slice<VEC>(dout + qh * C + hoff, l, G, D, live[u], dr[u]);
-            load_slice<VEC>(out + qh * C + hoff, l, G, D, live[u], orow[u]);
-            ls[u] = live[u] ? lse[qh * H + h] : 0.f;
-            dl[u] = live[u] ? delta[qh * H + h] : 0.f;
+            qh[u] = (size_t)b * Q + (live[u] ? q0 + u : 0);
         }
-#pragma unroll
-        for (int u = 0; u < 4; u++) {
-            dot[u] = group_sum(dot_slice<N>(qr[u], kv), G);
-            dp[u] = group_sum(dot_diff<N>(dr[u], vv, orow[u]), G);
-        }
+        query_stage<VEC>(queries, dout, out, lse, delta, qh, live, it, kv, vv, qr, dr, ls, dl, dot, dp);
 #pragma unroll
         for (int u = 0; u < 4; u++) {
             if (!live[u]) continue;
             const float p = expf(sh.scale * dot[u] - ls[u]);
-            const float ds = p * (dp[u] - dl[u]);
-#pragma unroll
-            for (int j = 0; j < N; j++) {
-                av[j] = fmaf(p, dr[u][j], av[j]);
-                ak[j] = fmaf(ds, qr[u][j], ak[j]);
-            }
+            push_dkv(p, p * (dp[u] - dl[u]), dr[u], qr[u], av, ak);
         }
     }
 #pragma unroll
@@ -472,22 +357,17 @@ int ms3d_qattn_forward(const float *queries, const float *k, const float *v, con
     if (ws_floats < ms3d_qattn_ws_floats(chunks, Q, H, D)) return MS3D_E_WORKSPACE;
     const size_t C = (size_t)H * D, nacc = (size_t)chunks * Q * C, nqh = (size_t)chunks * Q * H;
     float *w_acc = ws, *w_m = ws + nacc, *w_l = ws + nacc + nqh;
-    const bool v4 = D % 4 == 0 && aligned16(queries) && aligned16(k) && aligned16(v) && aligned16(out) && aligned16(ws);
+    const bool v4 = D % 4 == 0 && aligned16(queries, k, v, out, ws);
     const Shape sh{B, Q, H, D, group_of(D, v4 ? 4 : 1), scale};
     const unsigned tiles = item_tiles(Q, H, sh.G);
     if (!tiles) return MS3D_E_UNSUPPORTED;
     if (chunks > 0) {
         const dim3 grid((unsigned)chunks, tiles);
-        if (v4) qattn_forward_kernel<4><<<grid, QATTN_THREADS, 0, stream>>>(queries, k, v, mask, row_map, order, seg_start,
-                                                                            chunk_seg, chunk_first, sh, w_acc, w_m, w_l);
-        else qattn_forward_kernel<1><<<grid, QATTN_THREADS, 0, stream>>>(queries, k, v, mask, row_map, order, seg_start,
-                                                                         chunk_seg, chunk_first, sh, w_acc, w_m, w_l);
-        MS3D_LAUNCH_CHECK();
+        ATTN_LAUNCH(v4, qattn_forward_kernel, grid, QATTN_THREADS, 0, stream, queries, k, v, mask, row_map, order, seg_start,
+                    chunk_seg, chunk_first, sh, w_acc, w_m, w_l);
     }
     const dim3 mgrid((unsigned)B, tiles);
-    if (v4) qattn_forward_merge_kernel<4><<<mgrid, QATTN_THREADS, 0, stream>>>(chunk_first, sh, w_acc, w_m, w_l, out, lse);
-    else qattn_forward_merge_kernel<1><<<mgrid, QATTN_THREADS, 0, stream>>>(chunk_first, sh, w_acc, w_m, w_l, out, lse);
-    MS3D_LAUNCH_CHECK();
+    ATTN_LAUNCH(v4, qattn_forward_merge_kernel, mgrid, QATTN_THREADS, 0, stream, chunk_first, sh, w_acc, w_m, w_l, out, lse);
     return 0;
 }
 
@@ -505,26 +385,18 @@ int ms3d_qattn_backward_q(const float *queries, const float *k, const float *v, 
     if (ws_floats < ms3d_qattn_backward_ws_floats(chunks, Q, H, D)) return MS3D_E_WORKSPACE;
     const size_t C = (size_t)H * D, nacc = (size_t)chunks * Q * C;
     float *w_a = ws, *w_p = ws + nacc, *w_d = ws + 2 * nacc;
-    const bool v4 = D % 4 == 0 && aligned16(queries) && aligned16(k) && aligned16(v) && aligned16(out) && aligned16(dout) &&
-                    aligned16(ws) && (!dq || aligned16(dq));
+    const bool v4 = D % 4 == 0 && aligned16(queries, k, v, out, dout, ws, dq);
     const Shape sh{B, Q, H, D, group_of(D, v4 ? 4 : 1), scale};
     const unsigned tiles = item_tiles(Q, H, sh.G);
     if (!tiles) return MS3D_E_UNSUPPORTED;
     if (chunks > 0) {
         const dim3 grid((unsigned)chunks, tiles);
         const int rows = dq != nullptr;
-        if (v4) qattn_backward_q_kernel<4><<<grid, QATTN_THREADS, 0, stream>>>(queries, k, v, mask, row_map, order, seg_start,
-                                                                               chunk_seg, chunk_first, out, lse, dout, sh, rows,
-                                                                               w_a, w_p, w_d);
-        else qattn_backward_q_kernel<1><<<grid, QATTN_THREADS, 0, stream>>>(queries, k, v, mask, row_map, order, seg_start,
-                                                                            chunk_seg, chunk_first, out, lse, dout, sh, rows, w_a,
-                                                                            w_p, w_d);
-        MS3D_LAUNCH_CHECK();
+        ATTN_LAUNCH(v4, qattn_backward_q_kernel, grid, QATTN_THREADS, 0, stream, queries, k, v, mask, row_map, order, seg_start,
+                    chunk_seg, chunk_first, out, lse, dout, sh, rows, w_a, w_p, w_d);
     }
     const dim3 mgrid((unsigned)B, tiles);
-    if (v4) qattn_backward_q_merge_kernel<4><<<mgrid, QATTN_THREADS, 0, stream>>>(chunk_first, sh, w_a, w_p, w_d, dq, delta);
-    else qattn_backward_q_merge_kernel<1><<<mgrid, QATTN_THREADS, 0, stream>>>(chunk_first, sh, w_a, w_p, w_d, dq, delta);
-    MS3D_LAUNCH_CHECK();
+    ATTN_LAUNCH(v4, qattn_backward_q_merge_kernel, mgrid, QATTN_THREADS, 0, stream, chunk_first, sh, w_a, w_p, w_d, dq, delta);
     return 0;
 }
 
@@ -536,16 +408,12 @@ int ms3d_qattn_backward_kv(const float *queries, const float *k, const float *v,
     if (shape_check(V, B, Q, H, D)) return MS3D_E_UNSUPPORTED;
     if (V == 0 || B == 0 || Q == 0) return 0;                         // (dk / dv are not written: the caller's zero)
     if (!queries || !k || !v || !seg_of_row || !out || !lse || !delta || !dout || (!dk && !dv)) return MS3D_E_UNSUPPORTED;
-    const bool v4 = D % 4 == 0 && aligned16(queries) && aligned16(k) && aligned16(v) && aligned16(out) && aligned16(dout) &&
-                    (!dk || aligned16(dk)) && (!dv || aligned16(dv));
+    const bool v4 = D % 4 == 0 && aligned16(queries, k, v, out, dout, dk, dv);
     const Shape sh{B, Q, H, D, group_of(D, v4 ? 4 : 1), scale};
     const long per = QATTN_THREADS / sh.G, blocks = (V * H + per - 1) / per;
     if (blocks > 0x7fffffffL) return MS3D_E_UNSUPPORTED;
-    if (v4) qattn_backward_kv_kernel<4><<<(unsigned)blocks, QATTN_THREADS, 0, stream>>>(queries, k, v, mask, row_map, seg_of_row,
-                                                                                       out, lse, delta, dout, V, sh, dk, dv);
-    else qattn_backward_kv_kernel<1><<<(unsigned)blocks, QATTN_THREADS, 0, stream>>>(queries, k, v, mask, row_map, seg_of_row, out,
-                                                                                    lse, delta, dout, V, sh, dk, dv);
-    MS3D_LAUNCH_CHECK();
+    ATTN_LAUNCH(v4, qattn_backward_kv_kernel, (unsigned)blocks, QATTN_THREADS, 0, stream, queries, k, v, mask, row_map, seg_of_row,
+                out, lse, delta, dout, V, sh, dk, dv);
     return 0;
 }
 

@@ -42,7 +42,7 @@ def r():
 
 
 def group_lanes(D):
-    """lanes of a (row, head) group on the 16-byte path (D % 4 == 0): kattn.hip group_of(D, 4)"""
+    """lanes of a (row, head) group on the 16-byte path (D % 4 == 0): attn_core.h group_of(D, 4)"""
     g = 1
     while g < D // 4:
         g *= 2

@@ -37,7 +37,7 @@ def R():
 
 
 def items_per_tile(D):
-    """(query, head) items of a workgroup: 256 / G with G the lanes of a group -- qattn.hip group_of(D, 4) when D % 4 == 0 (the
+    """(query, head) items of a workgroup: 256 / G with G the lanes of a group -- attn_core.h group_of(D, 4) when D % 4 == 0 (the
     16-byte route: the test tensors are allocations of their own, so aligned), group_of(D, 1) otherwise"""
     n = D // 4 if D % 4 == 0 else D
     g = 1
