@@ -477,6 +477,49 @@ int ms3d_qattn_backward_kv(const float *queries, const float *k, const float *v,
                            const int *seg_of_row, const float *out, const float *lse, const float *delta, const float *dout,
                            long V, int B, int Q, int H, int D, float scale, float *dk, float *dv, ms3d_stream_t stream);
 
+/* ---- per-sample voxel attention: every voxel row attends to the queries of its own sample (csrc/vattn.hip; float32
+ * throughout) -- the reverse direction of the block above.  x [V][C] row-contiguous in the order the rows are HELD, keys /
+ * values [B][Q][C], C = H * D.  The sample of held row i is seg_of_row[i] (int32 [V]: CoordinateManager.batch_segments); mask
+ * [V][Q] bytes or NULL is the mask of ms3d_qattn_forward, the same object: non-zero = may not attend, one mask for all heads,
+ * its rows in the CALLER's order, the mask row of held row i is row_map[i] or i when row_map is NULL.  Over the queries q of
+ * sample b = seg_of_row[i] that the mask does not block for row i:
+ *   s[i][q][h] = scale * sum_d x[i][hD+d] * keys[b][q][hD+d]
+ *   p          = exp(s - m) / sum_q' exp(s' - m),  m = the maximum over those queries (always subtracted)
+ *   out[i][hD+d] = sum_q p * values[b][q][hD+d];   lse[i][h] = m + log sum exp(s - m)
+ * A row whose queries are all blocked gives out = 0 and lse = 0, contributes to no gradient and receives none.
+ * forward: one (held row, head) item per group of lanes loops over the Q queries in ascending q, four at a time, one
+ * online-softmax sweep; writes out [V][C] and lse [V][H]; no scratch.
+ * backward_x: the same sweep with p = exp(s - lse) recomputed; ds = p * (e - delta[i][h]) with e = sum_d dout[i][hD+d] *
+ * (values[b][q][hD+d] - out[i][hD+d]) -- the difference per channel before the sum, as in ms3d_kattn_backward_q -- and
+ * delta[i][h] = sum_q p * e, complete when the row's sweep ends: dx[i][h][:] = scale * (sum p e keys - delta * sum p keys).
+ * delta [V][H] is always written (backward_kv reads it); dx may be NULL (delta alone).  No scratch.
+ * backward_kv: dvalues[b][q][h][:] = sum_i p * dout[i][h][:], dkeys[b][q][h][:] = scale * sum_i ds * x[i][h][:] over the rows i
+ * of sample b that the mask does not block for q.  The rows of sample b are order[seg_start[b] .. seg_start[b + 1]) cut into
+ * the chunks of ms3d_qattn_chunk_list (the SAME chunk list, ms3d_qattn_rows_per_chunk() positions each): one workgroup per
+ * chunk and tile of (query, head) items walks the chunk's rows in ascending position and stores one partial of each sum; a
+ * second kernel adds the partials of a sample in ascending chunk order and writes EVERY element of dkeys / dvalues [B][Q][C]
+ * (zero for a (b, q) that no row may attend to).  ws: ms3d_vattn_backward_kv_ws_floats(chunks, Q, H, D) = chunks * Q * 2 * H * D
+ * floats (0 for empty shapes), the only scratch; dkeys or dvalues may be NULL (not both).
+ * Every sum runs in one fixed order that depends on the shapes only; no atomics; the same bytes on every run, in all three.
+ * 16-byte row accesses when D % 4 == 0 and every row pointer (ws included) is 16-byte aligned, a scalar path otherwise;
+ * 64-bit offsets.
+ * Limits: 1 <= D <= 128, H >= 1, H * D <= 1024, 0 <= Q <= 1024, 0 <= B <= 65535, V >= 0, chunks >= 0; V * H row items in at most
+ * 2^31 - 1 workgroups.  Outside them, or a NULL pointer that would be read or written: MS3D_E_UNSUPPORTED; a short workspace:
+ * MS3D_E_WORKSPACE; both decided on the host before any launch.  V == 0, B == 0 or Q == 0 with a served shape: 0, nothing is
+ * launched, no pointer is looked at.  The index arrays are trusted, as in the block above. */
+size_t ms3d_vattn_backward_kv_ws_floats(long chunks, int Q, int H, int D);
+int ms3d_vattn_forward(const float *x, const float *keys, const float *values, const unsigned char *mask, const int *row_map,
+                       const int *seg_of_row, long V, int B, int Q, int H, int D, float scale, float *out, float *lse,
+                       ms3d_stream_t stream);
+int ms3d_vattn_backward_x(const float *x, const float *keys, const float *values, const unsigned char *mask, const int *row_map,
+                          const int *seg_of_row, const float *out, const float *lse, const float *dout, long V, int B, int Q,
+                          int H, int D, float scale, float *dx, float *delta, ms3d_stream_t stream);
+int ms3d_vattn_backward_kv(const float *x, const float *keys, const float *values, const unsigned char *mask, const int *row_map,
+                           const long long *order, const int *seg_start, const int *chunk_seg, const int *chunk_first,
+                           const float *out, const float *lse, const float *delta, const float *dout, long V, int B, int chunks,
+                           int Q, int H, int D, float scale, float *dkeys, float *dvalues, float *ws, size_t ws_floats,
+                           ms3d_stream_t stream);
+
 /* ---- instance normalisation: per batch index (segment) and channel (csrc/inorm.hip; float32 rows and parameters, any C >= 1;
  * every sum, the statistics mean / invstd (DOUBLE [B, C]) and the arithmetic of the row passes are float64, rounded once at the
  * store: with few rows in a segment dx is a difference of nearly equal terms that float32 statistics cannot resolve; a lane takes four

@@ -185,9 +185,34 @@ Per-sample query attention -- the global block of a sparse transformer, the deco
     their pass; frozen queries skip theirs when k and v are frozen too (the kv pass reads a per-query residual the q pass
     leaves).
     Out of scope (each raises ValueError, TypeError or NotImplementedError naming it): a different Q per sample, float or
-    per-head masks, attention dropout, a value head dimension different from D, float16 / bfloat16, the reverse direction
-    (voxels attending to queries), CPU tensors (NotImplementedError naming ms3d_qattn_forward).  The mask logits x.F @
-    queries[b].T are a per-sample matmul of the caller's.  Outside prepare_conv_weights.
+    per-head masks, attention dropout, a value head dimension different from D, float16 / bfloat16, CPU tensors
+    (NotImplementedError naming ms3d_qattn_forward); the reverse direction (voxels attending to queries) is voxel_attention
+    below, and the TypeError says so.  The mask logits x.F @ queries[b].T are a per-sample matmul of the caller's.  Outside
+    prepare_conv_weights.
+
+Per-sample voxel attention -- the reverse direction, every voxel reads the queries of its own sample back: the second leg of
+a two-way mask-transformer decoder (engine extras: MinkowskiEngine has no such layer, and nothing here is pinned to it):
+
+    voxel_attention(x, keys, values, num_heads, attn_mask=None, scale=None) -> a SparseTensor on x's coordinate set;
+    MinkowskiVoxelAttention(embed_dim, num_heads, query_channels=None, bias=True): forward(x, queries, attn_mask=None) =
+    out_proj(voxel_attention(q_proj(x), k_proj(queries), v_proj(queries))); parameters q_proj, k_proj, v_proj, out_proj
+    (nn.Linear; k_proj and v_proj map query_channels to embed_dim)
+
+    out[i, h, :] = sum_q softmax_q(scale * <x[i, h], keys[b, q, h]>) values[b, q, h, :] over the queries q of the row's sample b
+    that attn_mask does not block; C = num_heads * D, scale = D ** -0.5 unless given.  x: a SparseTensor; keys, values
+    [B, Q, C] with the sample numbering of query_attention (another B is a ValueError).  attn_mask: the same object
+    query_attention takes -- bool [V, Q], rows as the caller sees them, True = may NOT attend, one mask for all heads -- so one
+    mask serves both legs.  A row whose queries are all blocked is zero, contributes to no gradient and receives none; a (b, q)
+    that no row may attend to gets a zero gradient.  csrc/vattn.hip: forward and the backward for x are one loop over the Q
+    queries per (held row, head) item -- an online-softmax sweep that saves the log-sum-exp, then the probabilities recomputed
+    -- without scratch; the backward for keys and values sweeps the chunks of query_attention (the same
+    CoordinateManager.batch_chunks list: no second host read), one partial per chunk, merged in chunk order.  The keys and
+    values of a sample are read through the cache.  Nothing of size V x Q is stored, no atomics, every sum in an order fixed
+    by the shapes, the same bytes on every run.  D <= 128, Q <= 1024, C <= 1024, B <= 65535.  Frozen keys and values skip their
+    pass; a frozen x skips its own when keys and values are frozen too (the kv pass reads a per-row residual the x pass leaves).
+    Out of scope (each raises ValueError, TypeError or NotImplementedError naming it): a different Q per sample, float or
+    per-head masks, attention dropout, keys.shape != values.shape, float16 / bfloat16, CPU tensors (NotImplementedError naming
+    ms3d_vattn_forward).  Outside prepare_conv_weights.
 
 Not supported (each raises NotImplementedError naming it): `axis_types` of a KernelGenerator, a region of more than 254
 offsets, a dense grid of more than 2^31 - 1 cells, to_sparse of a tensor
@@ -217,6 +242,7 @@ from .modules import (MinkowskiConvolution, MinkowskiConvolutionTranspose, Minko
                       MinkowskiPoolingTranspose, MinkowskiInterpolation, MinkowskiChannelwiseConvolution,
                       MinkowskiInstanceNorm, MinkowskiStableInstanceNorm,
                       MinkowskiKernelAttention, kernel_attention, MinkowskiQueryAttention, query_attention,
+                      MinkowskiVoxelAttention, voxel_attention,
                       MinkowskiToSparseTensor, MinkowskiToDenseTensor, MinkowskiToFeature,
                       MinkowskiELU, MinkowskiLeakyReLU, MinkowskiPReLU, MinkowskiSELU, MinkowskiCELU, MinkowskiGELU,
                       MinkowskiSiLU, MinkowskiTanh, MinkowskiSoftplus, MinkowskiHardswish, MinkowskiHardtanh,

@@ -681,6 +681,48 @@ def query_attention_rows(queries, k, v, mask, row_map, group, seg_of_row, num_he
     return QueryAttentionFn.apply(queries, k, v, mask, row_map, group, seg_of_row, num_heads, scale)
 
 
+class VoxelAttentionFn(torch.autograd.Function):
+    """out[i, h, :] = sum_q softmax_q(scale * <x[i, h], keys[b, q, h]>) * values[b, q, h, :] over the queries q of the row's
+    sample b = seg_of_row[i] that mask [V, Q] does not block (csrc/vattn.hip; float32, C = num_heads * D; a row with nothing to
+    attend to is zero) -- QueryAttentionFn's reverse direction, on the same mask, row_map, group and seg_of_row.  Saves x, keys,
+    values, out and the log-sum-exp lse [V, H]; the backward recomputes the probabilities from lse.  The x pass loops over the
+    queries per row again (dx and delta [V, H], the residual the kv pass subtracts), the kv pass sweeps the chunks of every
+    sample (one partial per chunk, added in chunk order): no atomics, the same bytes on every run.  Frozen keys and values
+    skip the kv pass; a frozen x skips the x pass unless the kv pass needs its delta (the pass then stores nothing else)."""
+
+    @staticmethod
+    def forward(ctx, x, keys, values, mask, row_map, group, seg_of_row, num_heads, scale):
+        be = get_backend()
+        if not hasattr(be, "vattn_forward"):
+            raise NotImplementedError("voxel attention needs the HIP backend (ms3d_vattn_forward)")
+        x, keys, values = x.contiguous(), keys.contiguous(), values.contiguous()
+        out, lse = be.vattn_forward(x, keys, values, mask, row_map, seg_of_row, num_heads, scale)
+        ctx.save_for_backward(x, keys, values, out, lse)
+        ctx.geom = (mask, row_map, group, seg_of_row, num_heads, scale)
+        return out
+
+    @staticmethod
+    def backward(ctx, dout):
+        x, keys, values, out, lse = ctx.saved_tensors
+        mask, row_map, group, seg_of_row, H, scale = ctx.geom
+        need_x, need_k, need_v = ctx.needs_input_grad[:3]
+        be = get_backend()
+        dout = dout.contiguous()
+        dx = dk = dv = None
+        if need_x or need_k or need_v:
+            dx, delta = be.vattn_backward_x(x, keys, values, mask, row_map, seg_of_row, out, lse, dout, H, scale, need_dx=need_x)
+            if need_k or need_v:
+                dk, dv = be.vattn_backward_kv(x, keys, values, mask, row_map, group, out, lse, delta, dout, H, scale,
+                                              need_dk=need_k, need_dv=need_v)
+        return dx, dk, dv, None, None, None, None, None, None
+
+
+def voxel_attention_rows(x, keys, values, mask, row_map, group, seg_of_row, num_heads, scale):
+    """attention of the rows x [V, C] (as the manager holds them, the mask's as the caller sees them) over the queries keys /
+    values [B, Q, C] of their own sample -> out [V, C]"""
+    return VoxelAttentionFn.apply(x, keys, values, mask, row_map, group, seg_of_row, num_heads, scale)
+
+
 class InstanceNormFn(torch.autograd.Function):
     """y[r, c] = (x[r, c] - mean[s, c]) * invstd[s, c] * weight[c] + bias[c] with the statistics of the row's segment s (its
     batch index) and the biased variance (csrc/inorm.hip).  group = (order, seg_start, seg_of_row): CoordinateManager.

@@ -536,12 +536,12 @@ def query_attention(queries, k, v, num_heads, attn_mask=None, scale=None, dropou
     without atomics (csrc/qattn.hip): the rows are read where the manager holds them, nothing of size V x Q is stored, forward
     and every gradient are the same bytes on every run.  D <= 128, Q <= 1024, C <= 1024, B <= 65535.
     Not offered: a different Q per sample (pad the queries and block the padding's columns), float or per-head masks, attention
-    dropout, a value head dimension other than D, float16 / bfloat16, the reverse direction (voxels attending to queries), CPU
-    tensors."""
+    dropout, a value head dimension other than D, float16 / bfloat16, CPU tensors.  The reverse direction (voxels attending to
+    queries) is voxel_attention."""
     name = "query_attention"
     if isinstance(queries, SparseTensor) or not isinstance(k, SparseTensor) or not isinstance(v, SparseTensor):
         raise TypeError(f"{name}: queries is a dense tensor [B, Q, C], k and v are SparseTensors; the reverse direction (voxels "
-                        "attending to queries) is not offered")
+                        "attending to queries) is voxel_attention(x, keys, values, ...)")
     if isinstance(queries, (list, tuple)):
         raise NotImplementedError(f"{name}: a different Q per sample (a list of query tensors) is not offered: pad the queries to "
                                   "one Q and block the padding's columns in attn_mask")
@@ -605,7 +605,8 @@ class MinkowskiQueryAttention(nn.Module):
     attn_mask)) -> [B, Q, embed_dim].  `q_proj` and `out_proj` are nn.Linear(embed_dim, embed_dim), `k_proj` and `v_proj`
     nn.Linear(in_channels, embed_dim) applied to the rows of the SparseTensor x (in_channels defaults to embed_dim); `bias`
     switches the bias of all four.  Positional terms are the caller's to add (x + pos works on a SparseTensor); a query whose
-    rows are all blocked comes out as out_proj's bias (query_attention gives zero there, not NaN).
+    rows are all blocked comes out as out_proj's bias (query_attention gives zero there, not NaN).  The reverse direction
+    (voxels attending to queries) is MinkowskiVoxelAttention.
 
     Not a _ConvBase: prepare_conv_weights lays out (K, cin, cout) weight images, and this block has none."""
 
@@ -626,7 +627,7 @@ class MinkowskiQueryAttention(nn.Module):
     def forward(self, queries, x: SparseTensor, attn_mask=None):
         if not isinstance(x, SparseTensor) or isinstance(queries, SparseTensor):
             raise TypeError(f"{type(self).__name__}: forward(queries, x) takes a dense tensor [B, Q, C] and a SparseTensor; the "
-                            "reverse direction (voxels attending to queries) is not offered")
+                            "reverse direction (voxels attending to queries) is MinkowskiVoxelAttention")
         if x._F.size(1) != self.in_channels:
             raise ValueError(f"{type(self).__name__}: the input has {x._F.size(1)} channels, the layer in_channels="
                              f"{self.in_channels}")
@@ -636,6 +637,127 @@ class MinkowskiQueryAttention(nn.Module):
 
     def extra_repr(self):
         return f"embed_dim={self.embed_dim}, num_heads={self.num_heads}, in_channels={self.in_channels}"
+
+
+def voxel_attention(x, keys, values, num_heads, attn_mask=None, scale=None, dropout=0.0):
+    """Per-sample multi-head attention of every voxel over the queries of its own sample (an engine extra: MinkowskiEngine has
+    no such layer) -- the reverse direction of query_attention, the second leg of a two-way mask-transformer decoder: the voxel
+    features read the refined queries back.  x: a SparseTensor with V rows of C = num_heads * D float32 channels.  keys, values:
+    float32 tensors [B, Q, C] on the same device; B is the number of batch indices PRESENT in x's coordinate set and keys[b]
+    belongs to the b-th of them in ascending order -- the numbering of query_attention, of CoordinateManager.batch_rows, of
+    origin_map and of the MinkowskiGlobal*Pooling output rows.  For row i of sample b, head h, over the queries q:
+    out[i, hD:hD+D] = sum_q softmax_q(scale * <x[i, hD:hD+D], keys[b, q, hD:hD+D]>) * values[b, q, hD:hD+D], scale = D ** -0.5
+    unless given.  -> a SparseTensor on x's coordinate set, its rows in the caller's order as x's are.
+
+    attn_mask: the very object query_attention takes, so one mask serves both legs: a bool tensor [V, Q] or None, row i the
+    i-th row of x.F / x.C as the caller sees them, column q the query of that row's own sample, True = may NOT attend, one
+    mask for all heads.  A row whose queries are all blocked gives out = 0, contributes to no gradient and receives none --
+    NOT the NaN of torch.nn.MultiheadAttention; a (b, q) that no row of its sample may attend to gets a zero gradient.
+
+    Gradients flow to x.F, keys and values.  A pending BatchNorm / ReLU on x is materialised first.  float32 HIP kernels
+    without atomics (csrc/vattn.hip): the rows are read where the manager holds them, nothing of size V x Q is stored, forward
+    and every gradient are the same bytes on every run.  D <= 128, Q <= 1024, C <= 1024, B <= 65535.
+    Not offered: a different Q per sample (pad the queries and block the padding's columns), float or per-head masks, attention
+    dropout, a value head dimension other than D, float16 / bfloat16, CPU tensors."""
+    name = "voxel_attention"
+    if not isinstance(x, SparseTensor) or isinstance(keys, SparseTensor) or isinstance(values, SparseTensor):
+        raise TypeError(f"{name}: x is a SparseTensor, keys and values are dense tensors [B, Q, C]; queries attending to voxels is "
+                        "query_attention(queries, k, v, ...)")
+    if isinstance(keys, (list, tuple)) or isinstance(values, (list, tuple)):
+        raise NotImplementedError(f"{name}: a different Q per sample (a list of query tensors) is not offered: pad the queries to "
+                                  "one Q and block the padding's columns in attn_mask")
+    if not torch.is_tensor(keys) or not torch.is_tensor(values):
+        raise TypeError(f"{name}: keys and values must be float32 tensors [B, Q, C], got {type(keys).__name__} and "
+                        f"{type(values).__name__}")
+    if dropout:
+        raise NotImplementedError(f"{name}: attention dropout (dropout={dropout}) is not offered")
+    cm, ts = x.coordinate_manager, x.tensor_stride
+    for what, t in (("x", x._F), ("keys", keys), ("values", values)):
+        if t.dtype != torch.float32:
+            raise TypeError(f"{name}: {what} is {t.dtype}; float32 only (float16 / bfloat16 are not offered)")
+    V, C = x._F.shape
+    if keys.dim() != 3 or keys.size(2) != C:
+        raise ValueError(f"{name}: keys must have shape [B, Q, C] with C = {C}, the channels of x, got {tuple(keys.shape)}")
+    if tuple(values.shape) != tuple(keys.shape):
+        raise ValueError(f"{name}: values has shape {tuple(values.shape)}, keys {tuple(keys.shape)}: keys.shape != values.shape, "
+                         "a value head dimension different from D is not offered")
+    if not isinstance(num_heads, int) or num_heads < 1 or C % num_heads != 0:
+        raise ValueError(f"{name}: {C} channels do not divide into num_heads={num_heads}")
+    if keys.device != x._F.device or values.device != x._F.device:
+        raise ValueError(f"{name}: keys and values are on {keys.device} and {values.device}, x on {x._F.device}")
+    order, _, offsets, _ = cm.batch_rows(ts)
+    B, Q, D = offsets.numel() - 1, keys.size(1), C // num_heads
+    if keys.size(0) != B:
+        raise ValueError(f"{name}: keys has B = {keys.size(0)} samples, the coordinate set holds {B} batch indices")
+    if attn_mask is not None:
+        if not torch.is_tensor(attn_mask) or attn_mask.dtype != torch.bool:
+            raise TypeError(f"{name}: attn_mask must be a bool tensor [V, Q] (True = may not attend), got "
+                            f"{getattr(attn_mask, 'dtype', type(attn_mask).__name__)}; float masks are not offered")
+        if attn_mask.dim() == 3:
+            raise ValueError(f"{name}: attn_mask has shape {tuple(attn_mask.shape)}; per-head masks are not offered, one [V, Q] "
+                             "mask serves all heads")
+        if tuple(attn_mask.shape) != (V, Q):
+            raise ValueError(f"{name}: attn_mask must have shape [V, Q] = [{V}, {Q}], got {list(attn_mask.shape)}")
+        if attn_mask.device != x._F.device:
+            raise ValueError(f"{name}: attn_mask is on {attn_mask.device}, x on {x._F.device}")
+    for what, got, cap in (("head dimension D", D, _QATTN_MAX_D), ("Q", Q, _QATTN_MAX_Q), ("C = num_heads * D", C, _QATTN_MAX_C),
+                           ("B", B, _QATTN_MAX_B)):
+        if got > cap:
+            raise ValueError(f"{name}: {what} = {got} is above the kernels' limit of {cap}")
+    if B == 0 or Q == 0:
+        return x._like(x._F.new_zeros((V, C)))
+    be = get_backend()
+    if not hasattr(be, "vattn_forward") or not x._F.is_cuda:
+        raise NotImplementedError(f"{name} needs the HIP backend and device tensors, CPU tensors are not offered "
+                                  "(ms3d_vattn_forward)")
+    if scale is None:
+        scale = D ** -0.5
+    group = (order, offsets) + cm.batch_chunks(ts)
+    mask = None if attn_mask is None else attn_mask.contiguous()
+    return x._like(Fn.voxel_attention_rows(x._raw(), keys, values, mask, cm.caller_rows(ts), group, cm.batch_segments(ts),
+                                           num_heads, float(scale)))
+
+
+class MinkowskiVoxelAttention(nn.Module):
+    """The second leg of a two-way mask-transformer decoder, the mirror of MinkowskiQueryAttention (an engine extra:
+    MinkowskiEngine has no such layer): forward(x, queries, attn_mask=None) = out_proj(voxel_attention(q_proj(x),
+    k_proj(queries), v_proj(queries), num_heads, attn_mask)) -> a SparseTensor of embed_dim channels on x's coordinate set.
+    `q_proj` and `out_proj` are nn.Linear(embed_dim, embed_dim) applied to the rows of the SparseTensor x, `k_proj` and `v_proj`
+    nn.Linear(query_channels, embed_dim) applied to the dense queries [B, Q, query_channels] (query_channels defaults to
+    embed_dim); `bias` switches the bias of all four.  A row whose queries are all blocked comes out as out_proj's bias
+    (voxel_attention gives zero there, not NaN).
+
+    Not a _ConvBase: prepare_conv_weights lays out (K, cin, cout) weight images, and this block has none."""
+
+    def __init__(self, embed_dim, num_heads, query_channels=None, bias=True, dropout=0.0):
+        super().__init__()
+        if dropout:
+            raise NotImplementedError(f"{type(self).__name__}: attention dropout (dropout={dropout}) is not offered")
+        if not isinstance(num_heads, int) or num_heads < 1 or embed_dim % num_heads != 0:
+            raise ValueError(f"{type(self).__name__}: {embed_dim} channels do not divide into num_heads={num_heads}")
+        self.embed_dim = int(embed_dim)
+        self.query_channels = self.embed_dim if query_channels is None else int(query_channels)
+        self.num_heads = num_heads
+        self.q_proj = nn.Linear(self.embed_dim, self.embed_dim, bias=bias)
+        self.k_proj = nn.Linear(self.query_channels, self.embed_dim, bias=bias)
+        self.v_proj = nn.Linear(self.query_channels, self.embed_dim, bias=bias)
+        self.out_proj = nn.Linear(self.embed_dim, self.embed_dim, bias=bias)
+
+    def forward(self, x: SparseTensor, queries, attn_mask=None):
+        if not isinstance(x, SparseTensor) or isinstance(queries, SparseTensor):
+            raise TypeError(f"{type(self).__name__}: forward(x, queries) takes a SparseTensor and a dense tensor [B, Q, C]; queries "
+                            "attending to voxels is MinkowskiQueryAttention")
+        if x._F.size(1) != self.embed_dim:
+            raise ValueError(f"{type(self).__name__}: the input has {x._F.size(1)} channels, the layer embed_dim={self.embed_dim}")
+        if not torch.is_tensor(queries) or queries.dim() != 3 or queries.size(2) != self.query_channels:
+            raise ValueError(f"{type(self).__name__}: queries must have shape [B, Q, {self.query_channels}] (query_channels), got "
+                             f"{tuple(queries.shape) if torch.is_tensor(queries) else type(queries).__name__}")
+        q = x._like(self.q_proj(x._raw()))
+        y = voxel_attention(q, self.k_proj(queries), self.v_proj(queries), self.num_heads, attn_mask)
+        return y._like(self.out_proj(y._raw()))
+
+    def extra_repr(self):
+        return f"embed_dim={self.embed_dim}, num_heads={self.num_heads}, query_channels={self.query_channels}"
 
 
 class MinkowskiPruning(nn.Module):

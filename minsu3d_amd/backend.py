@@ -1379,6 +1379,73 @@ class _HipEngine:
                    "ms3d_qattn_backward_kv")
         return dk, dv
 
+    # ---- per-sample voxel attention, the reverse direction: rows attend to the queries of their sample (csrc/vattn.hip)
+    def _vattn_check(self, x, keys, values, mask, row_map, seg_of_row, H):
+        """-> (x, keys, values) contiguous on the device and (V, B, Q, D); the checks of _qattn_check with the roles swapped"""
+        x, keys, values = self._dev(x), self._dev(keys), self._dev(values)
+        assert x.dtype == keys.dtype == values.dtype == torch.float32 and x.dim() == 2 and keys.dim() == values.dim() == 3
+        c = x.size(1)
+        assert keys.size(2) == c and tuple(values.shape) == tuple(keys.shape) and H >= 1 and c % H == 0
+        V, (B, Q) = x.size(0), keys.shape[:2]
+        if mask is not None:
+            assert mask.dtype == torch.bool and mask.is_contiguous() and tuple(mask.shape) == (V, Q) and mask.device == x.device
+        if row_map is not None:
+            assert row_map.dtype == torch.int32 and row_map.is_contiguous() and row_map.numel() == V
+        if seg_of_row is not None:
+            assert seg_of_row.dtype == torch.int32 and seg_of_row.is_contiguous() and seg_of_row.numel() == V
+        return x, keys, values, V, B, Q, c // H
+
+    def vattn_forward(self, x, keys, values, mask, row_map, seg_of_row, H, scale):
+        """-> (out [V, C], lse [V, H]): per held row i, softmax over the queries of its sample seg_of_row[i]
+        (CoordinateManager.batch_segments) that mask [V, Q] (bool, caller's row order; None: none) does not block of scale *
+        <x[i, h], keys[b, q, h]>, applied to values.  x [V, C] as held, keys / values [B, Q, C]; row_map int32 [V] held row ->
+        caller's row, or None.  A row without an unblocked query: out = 0, lse = 0."""
+        x, keys, values, V, B, Q, d = self._vattn_check(x, keys, values, mask, row_map, seg_of_row, H)
+        out = torch.empty_like(x)
+        lse = torch.empty((V, H), dtype=torch.float32, device=x.device)
+        _lib.check(self.lib.ms3d_vattn_forward(_lib.ptr(x), _lib.ptr(keys), _lib.ptr(values), _lib.ptr(mask), _lib.ptr(row_map),
+                                               _lib.ptr(seg_of_row), C.c_long(V), int(B), int(Q), int(H), int(d),
+                                               C.c_float(scale), _lib.ptr(out), _lib.ptr(lse), _lib.stream_handle()),
+                   "ms3d_vattn_forward")
+        return out, lse
+
+    def vattn_backward_x(self, x, keys, values, mask, row_map, seg_of_row, out, lse, dout, H, scale, need_dx=True):
+        """-> (dx [V, C] or None, delta [V, H]); delta, the residual sum_q p <dout, values - out> per row and head, is what
+        vattn_backward_kv reads"""
+        x, keys, values, V, B, Q, d = self._vattn_check(x, keys, values, mask, row_map, seg_of_row, H)
+        dout = self._dev(dout)
+        assert tuple(dout.shape) == tuple(x.shape) == tuple(out.shape) and dout.dtype == torch.float32
+        dx = torch.empty_like(x) if need_dx else None
+        delta = torch.empty((V, H), dtype=torch.float32, device=x.device)
+        _lib.check(self.lib.ms3d_vattn_backward_x(_lib.ptr(x), _lib.ptr(keys), _lib.ptr(values), _lib.ptr(mask),
+                                                  _lib.ptr(row_map), _lib.ptr(seg_of_row), _lib.ptr(out), _lib.ptr(lse),
+                                                  _lib.ptr(dout), C.c_long(V), int(B), int(Q), int(H), int(d), C.c_float(scale),
+                                                  _lib.ptr(dx), _lib.ptr(delta), _lib.stream_handle()), "ms3d_vattn_backward_x")
+        return dx, delta
+
+    def vattn_backward_kv(self, x, keys, values, mask, row_map, group, out, lse, delta, dout, H, scale, need_dk=True,
+                          need_dv=True):
+        """-> (dkeys, dvalues) [B, Q, C] (None where not asked for): sums over the rows of a sample, one partial per chunk of
+        group = (order, seg_start, chunk_seg, chunk_first, chunks) (CoordinateManager.batch_rows and batch_chunks, the chunk
+        list of qattn_forward), added in chunk order"""
+        x, keys, values, V, B, Q, d = self._vattn_check(x, keys, values, mask, row_map, None, H)
+        order, seg_start, chunk_seg, chunk_first, chunks = self._qattn_group(group, V, B)
+        dout = self._dev(dout)
+        assert tuple(dout.shape) == tuple(x.shape) == tuple(out.shape) and (need_dk or need_dv)
+        dk = torch.empty_like(keys) if need_dk else None
+        dv = torch.empty_like(values) if need_dv else None
+        # (the scratch of the qattn calls: the calls of one stream run in order, so both directions of a decoder share it)
+        ws = self.ws.get("qattn", 4 * self.lib.ms3d_vattn_backward_kv_ws_floats(C.c_long(chunks), int(Q), int(H), int(d)),
+                         x.device)
+        _lib.check(self.lib.ms3d_vattn_backward_kv(_lib.ptr(x), _lib.ptr(keys), _lib.ptr(values), _lib.ptr(mask),
+                                                   _lib.ptr(row_map), _lib.ptr(order), _lib.ptr(seg_start), _lib.ptr(chunk_seg),
+                                                   _lib.ptr(chunk_first), _lib.ptr(out), _lib.ptr(lse), _lib.ptr(delta),
+                                                   _lib.ptr(dout), C.c_long(V), int(B), int(chunks), int(Q), int(H), int(d),
+                                                   C.c_float(scale), _lib.ptr(dk), _lib.ptr(dv), _lib.ptr(ws),
+                                                   C.c_size_t(ws.numel() // 4), _lib.stream_handle()),
+                   "ms3d_vattn_backward_kv")
+        return dk, dv
+
     # ---- instance normalisation over the batch grouping of a coordinate set (csrc/inorm.hip)
     def _inorm_check(self, x, order, seg_start, seg_of_row):
         assert x.dtype == torch.float32 and x.dim() == 2

@@ -1,5 +1,6 @@
-// What the fused attention kernels share (csrc/kattn.hip over a kernel map, csrc/qattn.hip over the rows of a sample): the lane
-// layout of a (row, head) item, the accumulation steps of the three sweeps and the four-row gather stages.  Each file keeps its
+// What the fused attention kernels share (csrc/kattn.hip over a kernel map, csrc/qattn.hip and csrc/vattn.hip between the rows
+// and the queries of a sample): the lane layout of a (row, head) item, the accumulation steps of the three sweeps and the
+// four-row gather stages; for the two per-sample families also their limits and the chunking of a sample.  Each file keeps its
 // kernels, its loops and where a row index comes from; a score is formed there too.  What lies here is the ONE copy of the
 // arithmetic after it, so every sweep of either family recomputes p and ds to the same bits.
 //
@@ -225,6 +226,45 @@ __device__ __forceinline__ void query_stage(const float *__restrict__ q, const f
         dot[u] = group_sum(dot_slice(qr[u], kv), it.G);
         dp[u] = group_sum(dot_diff(dr[u], vv, orow[u]), it.G);
     }
+}
+
+// ---- the per-sample families (csrc/qattn.hip, csrc/vattn.hip): one set of limits, one chunking of a sample's rows
+
+constexpr int SATTN_MAX_D = 128;           // head dimension at most: two scalar rounds of a 64-lane group
+constexpr int SATTN_MAX_Q = 1024;
+constexpr int SATTN_MAX_C = 1024;          // H * D
+constexpr int SATTN_MAX_B = 65535;
+constexpr int SATTN_THREADS = 256;
+constexpr int SATTN_ROWS_PER_CHUNK = 512;  // positions of `order` per chunk: a constant of the library, NOT derived from the
+                                           // grid or the CU count -- the order of every sum is the same on every machine
+
+// what every kernel is told about the call
+struct Shape {
+    int B, Q, H, D, G;
+    float scale;
+};
+
+// the positions [p0, p1) of `order` that chunk c covers, and its sample
+__device__ __forceinline__ void chunk_range(const int *__restrict__ seg_start, const int *__restrict__ chunk_seg,
+                                            const int *__restrict__ chunk_first, int c, int &b, long &p0, long &p1)
+{
+    b = chunk_seg[c];
+    p0 = (long)seg_start[b] + (long)(c - chunk_first[b]) * SATTN_ROWS_PER_CHUNK;
+    p1 = min(p0 + SATTN_ROWS_PER_CHUNK, (long)seg_start[b + 1]);
+}
+
+// the limits every call shares: whether the shape is served
+bool sample_shape_served(long V, int B, int Q, int H, int D)
+{
+    if (H < 1 || D < 1 || D > SATTN_MAX_D || (long)H * D > SATTN_MAX_C) return false;
+    return Q >= 0 && Q <= SATTN_MAX_Q && B >= 0 && B <= SATTN_MAX_B && V >= 0;
+}
+
+// the tiles of (query, head) items of a sweep or merge launch; 0 when they do not fit a grid
+unsigned item_tiles(int Q, int H, int G)
+{
+    const long per = SATTN_THREADS / G, tiles = ((long)Q * H + per - 1) / per;
+    return tiles > 65535 ? 0u : (unsigned)tiles;
 }
 
 }  // namespace

@@ -30,28 +30,10 @@
 
 namespace {
 
-constexpr int QATTN_MAX_D = 128;           // head dimension at most: two scalar rounds of a 64-lane group
-constexpr int QATTN_MAX_Q = 1024;
-constexpr int QATTN_MAX_C = 1024;          // H * D
-constexpr int QATTN_MAX_B = 65535;
-constexpr int QATTN_THREADS = 256;
-constexpr int QATTN_ROWS_PER_CHUNK = 512;  // positions of `order` per chunk: a constant of the library, NOT derived from the
-                                           // grid or the CU count -- the order of every sum is the same on every machine
-
-// what every kernel is told about the call
-struct Shape {
-    int B, Q, H, D, G;
-    float scale;
-};
-
-// the positions [p0, p1) of `order` that chunk c covers, and its sample
-__device__ __forceinline__ void chunk_range(const int *__restrict__ seg_start, const int *__restrict__ chunk_seg,
-                                            const int *__restrict__ chunk_first, int c, int &b, long &p0, long &p1)
-{
-    b = chunk_seg[c];
-    p0 = (long)seg_start[b] + (long)(c - chunk_first[b]) * QATTN_ROWS_PER_CHUNK;
-    p1 = min(p0 + QATTN_ROWS_PER_CHUNK, (long)seg_start[b + 1]);
-}
+// the limits, the chunk size, Shape and chunk_range are attn_core.h's, shared with csrc/vattn.hip
+constexpr int QATTN_MAX_B = SATTN_MAX_B;
+constexpr int QATTN_THREADS = SATTN_THREADS;
+constexpr int QATTN_ROWS_PER_CHUNK = SATTN_ROWS_PER_CHUNK;
 
 // the held rows at the positions r0 .. r0 + 3 of `order` that query q may attend to; -1 past p1, where the mask blocks, or off
 __device__ __forceinline__ void rows_of_query(const long long *__restrict__ order, const unsigned char *__restrict__ mask,
@@ -284,21 +266,6 @@ __global__ __launch_bounds__(QATTN_THREADS) void qattn_backward_kv_kernel(
     if (dv) store_slice<VEC>(dv + (size_t)i * C + hoff, l, G, D, on, av);
 }
 
-// the limits all three calls share; 0 when the shape is served
-int shape_check(long V, int B, int Q, int H, int D)
-{
-    if (H < 1 || D < 1 || D > QATTN_MAX_D || (long)H * D > QATTN_MAX_C) return MS3D_E_UNSUPPORTED;
-    if (Q < 0 || Q > QATTN_MAX_Q || B < 0 || B > QATTN_MAX_B || V < 0) return MS3D_E_UNSUPPORTED;
-    return 0;
-}
-
-// the tiles of (query, head) items of a sweep or merge launch; 0 when they do not fit a grid
-unsigned item_tiles(int Q, int H, int G)
-{
-    const long per = QATTN_THREADS / G, tiles = ((long)Q * H + per - 1) / per;
-    return tiles > 65535 ? 0u : (unsigned)tiles;
-}
-
 }  // namespace
 
 extern "C" {
@@ -350,7 +317,7 @@ int ms3d_qattn_forward(const float *queries, const float *k, const float *v, con
                        ms3d_stream_t stream_)
 {
     hipStream_t stream = (hipStream_t)stream_;
-    if (shape_check(V, B, Q, H, D) || chunks < 0) return MS3D_E_UNSUPPORTED;
+    if (!sample_shape_served(V, B, Q, H, D) || chunks < 0) return MS3D_E_UNSUPPORTED;
     if (V == 0 || B == 0 || Q == 0) return 0;
     if (!queries || !k || !v || !order || !seg_start || !chunk_first || !out || !lse) return MS3D_E_UNSUPPORTED;
     if (chunks > 0 && (!chunk_seg || !ws)) return MS3D_E_UNSUPPORTED;
@@ -377,7 +344,7 @@ int ms3d_qattn_backward_q(const float *queries, const float *k, const float *v, 
                           float scale, float *dq, float *delta, float *ws, size_t ws_floats, ms3d_stream_t stream_)
 {
     hipStream_t stream = (hipStream_t)stream_;
-    if (shape_check(V, B, Q, H, D) || chunks < 0) return MS3D_E_UNSUPPORTED;
+    if (!sample_shape_served(V, B, Q, H, D) || chunks < 0) return MS3D_E_UNSUPPORTED;
     if (V == 0 || B == 0 || Q == 0) return 0;
     if (!queries || !k || !v || !order || !seg_start || !chunk_first || !out || !lse || !dout || !delta)
         return MS3D_E_UNSUPPORTED;
@@ -405,7 +372,7 @@ int ms3d_qattn_backward_kv(const float *queries, const float *k, const float *v,
                            long V, int B, int Q, int H, int D, float scale, float *dk, float *dv, ms3d_stream_t stream_)
 {
     hipStream_t stream = (hipStream_t)stream_;
-    if (shape_check(V, B, Q, H, D)) return MS3D_E_UNSUPPORTED;
+    if (!sample_shape_served(V, B, Q, H, D)) return MS3D_E_UNSUPPORTED;
     if (V == 0 || B == 0 || Q == 0) return 0;                         // (dk / dv are not written: the caller's zero)
     if (!queries || !k || !v || !seg_of_row || !out || !lse || !delta || !dout || (!dk && !dv)) return MS3D_E_UNSUPPORTED;
     const bool v4 = D % 4 == 0 && aligned16(queries, k, v, out, dout, dk, dv);
