@@ -520,6 +520,42 @@ int ms3d_vattn_backward_kv(const float *x, const float *keys, const float *value
                            int Q, int H, int D, float scale, float *dkeys, float *dvalues, float *ws, size_t ws_floats,
                            ms3d_stream_t stream);
 
+/* ---- farthest point sampling per sample (csrc/fps.hip): M rows of every sample, the seeds of the queries the two blocks above
+ * take.  The rows of sample b are order[seg_start[b] .. seg_start[b + 1]) (order int64 [V], seg_start int32 [B + 1]:
+ * CoordinateManager.batch_rows, or a stable sort of a field's batch column), read by index where they lie in coords [V][4] int32
+ * (batch, x, y, z) / points [N][4] float32 (batch, x, y, z), N = V; the batch column is not looked at.  The CALLER's row of held
+ * row i is row_map[i] (int32 [V], the manager's held-to-caller index) or i when row_map is NULL.  out [B][M] int64 holds caller
+ * rows:
+ *   out[b][0] = start_held[b] (int64 [B], a HELD row of sample b), or the sample's lowest caller row when start_held is NULL
+ *   out[b][j] = the row of sample b whose distance to the nearest of out[b][0 .. j-1] is largest; among equal distances the
+ *               lowest caller row; rows already picked have distance 0 and take part like any other row
+ * so the result is a pure function of the coordinate set and does not depend on how the rows are held.  M > len_b is served by
+ * the same rule (once every distance is 0 the lowest caller row repeats); the Python layer refuses it.
+ * Distances.  i32: the exact integer dx^2 + dy^2 + dz^2 in unsigned 32-bit arithmetic; the coordinates are trusted to lie in the
+ * packable range [-16384, 16384), where it reaches 3 * 32767^2 = 3 221 028 867 (above 2^31, below 2^32).  f32: d = (dx*dx + dy*dy)
+ * + dz*dz with dx = p.x - c.x, every operation rounded to float32 on its own, never contracted into an FMA; the running minimum
+ * is fminf on finite values; finite coordinates are a precondition and are not checked; duplicate points are legal.
+ * One launch, one workgroup per sample, which loops over its own segment; no workgroup waits for another (no spin, no grid
+ * barrier, no atomics), every loop is counted: M * ceil(len_b / rows per step) steps.  A thread keeps its best row as one 64-bit
+ * key, (distance bits << 32) | ~caller row, reduced per wave by shuffles and across waves through LDS; two workgroup barriers a
+ * pick.  A sample of at most ms3d_fps_resident_rows() rows is held in registers for the whole loop (nothing is read from global
+ * memory after the first gather); a larger one is gathered once, in segment order, into ws (i32: 16 B a row, f32: 20 B a row)
+ * and swept with 16-byte accesses every pick.  ws: ms3d_fps_ws_bytes(V, B) bytes, 16-byte aligned, never assumed zero; the same
+ * size serves both entry points; it grows with V and with B.
+ * V < 0, B < 0, B > 65535, M < 1: MS3D_E_UNSUPPORTED.  V == 0 or B == 0 otherwise: 0, nothing is launched, no pointer is looked
+ * at.  Then a NULL coords / points, order, seg_start, out or ws, or a ws that is not 16-byte aligned: MS3D_E_UNSUPPORTED; a short
+ * workspace: MS3D_E_WORKSPACE; all decided on the host before the launch.  The index arrays are trusted to name what they
+ * should; an order entry outside [0, V) and a seg_start outside [0, V] are clamped, a start_held outside its sample is ignored
+ * (lowest caller row), so no index is followed outside its array. */
+int ms3d_fps_resident_rows(void);
+size_t ms3d_fps_ws_bytes(long V, int B);
+int ms3d_fps_i32(const int *coords /*[V][4] as held*/, const long long *order /*[V]*/, const int *seg_start /*[B + 1]*/,
+                 const int *row_map /*[V] held -> caller, or NULL*/, const long long *start_held /*[B] or NULL*/, int V, int B,
+                 int M, long long *out /*[B][M] caller rows*/, void *ws, size_t ws_bytes, ms3d_stream_t stream);
+int ms3d_fps_f32(const float *points /*[N][4], N = V*/, const long long *order /*[V]*/, const int *seg_start /*[B + 1]*/,
+                 const int *row_map /*[V] held -> caller, or NULL*/, const long long *start_held /*[B] or NULL*/, int V, int B,
+                 int M, long long *out /*[B][M] caller rows*/, void *ws, size_t ws_bytes, ms3d_stream_t stream);
+
 /* ---- instance normalisation: per batch index (segment) and channel (csrc/inorm.hip; float32 rows and parameters, any C >= 1;
  * every sum, the statistics mean / invstd (DOUBLE [B, C]) and the arithmetic of the row passes are float64, rounded once at the
  * store: with few rows in a segment dx is a difference of nearly equal terms that float32 statistics cannot resolve; a lane takes four

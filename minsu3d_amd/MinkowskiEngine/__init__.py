@@ -214,6 +214,40 @@ a two-way mask-transformer decoder (engine extras: MinkowskiEngine has no such l
     per-head masks, attention dropout, keys.shape != values.shape, float16 / bfloat16, CPU tensors (NotImplementedError naming
     ms3d_vattn_forward).  Outside prepare_conv_weights.
 
+Farthest point sampling per sample -- where the queries of the two blocks above come from, and the grouping stage of a point
+network (an engine extra: MinkowskiEngine has no such function, and nothing here is pinned to it):
+
+    farthest_point_sampling(x, num_samples, start=None) -> int64 [B, M]
+
+    x: a SparseTensor (any tensor stride its manager holds; a plain, Morton-sorted or rooted manager) or a TensorField; M =
+    num_samples, a Python int >= 1; B the number of batch indices PRESENT, row b for the b-th of them in ascending order (the
+    numbering of query_attention, CoordinateManager.batch_rows, origin_map and the global pooling layers; gaps and interleaved
+    rows are fine).  The values are rows of x.F / x.C as the caller sees them, on a Morton-sorted manager too: x.F[idx] is
+    [B, M, C], ready for MinkowskiQueryAttention, x.C[idx][..., 1:] are the positions.
+    The rule, all of it: pick 0 of a sample is start[b] (without `start`: its lowest caller row); pick j is the row whose
+    distance to the nearest of the picks 0 .. j-1 is largest; among equal distances the lowest caller row wins; rows already
+    picked have distance 0 and take part like any other row.  The result is a pure function of the coordinates: the same
+    bytes on every run, whatever order the manager holds its rows in.
+    Distances: on a SparseTensor the exact integer dx^2 + dy^2 + dz^2 at the tensor's stride, in unsigned 32-bit arithmetic (up
+    to 3 * 32767^2 = 3 221 028 867 over the packable range [-16384, 16384)); on a TensorField its float32 points (float64 is
+    taken to float32 first), d = (dx*dx + dy*dy) + dz*dz with dx = p.x - c.x, every operation rounded to float32 on its own, no
+    FMA, the running minimum by fminf; finite coordinates are a precondition and are not checked; duplicate points are legal
+    (once every remaining distance is 0 the lowest row repeats).
+    start: int64 [B] caller rows, one inside each sample (one host read, only when it is given).  ValueError: num_samples that
+    is not an int >= 1 or is larger than the smallest sample (naming the sample and its size; the segment lengths are read on
+    the host once per coordinate set: CoordinateManager.batch_lengths, or once per field), a start of the wrong shape or dtype,
+    for another B or with a row outside its sample, integer coordinates outside the packable range.  An empty tensor gives an
+    empty [0, M] result.
+    csrc/fps.hip: one launch, one workgroup per sample looping over its own segment of batch_rows, rows read where they are
+    held (cm.coords, batch_rows and caller_rows are passed as they are); no atomics and no waiting between workgroups; a
+    thread's best row is one 64-bit key, (distance bits << 32) | ~caller row, reduced by shuffles and through LDS, two
+    barriers a pick.  A sample of at most ms3d_fps_resident_rows() rows stays in registers for the whole loop; a larger one
+    is gathered once into a workspace and swept every pick.  CPU tensors take the same rule as a torch expression, a loop
+    of M steps.  The index is not differentiable: gradients reach x.F through x.F[idx] or gather_rows.
+    Out of scope: other metrics, feature-space sampling, a different M per sample, float16 or float64 distances, gradients
+    with respect to the coordinates, kNN or ball grouping around the picks; a backend without the kernels raises
+    NotImplementedError naming ms3d_fps_i32 for device tensors.
+
 Not supported (each raises NotImplementedError naming it): `axis_types` of a KernelGenerator, a region of more than 254
 offsets, a dense grid of more than 2^31 - 1 cells, to_sparse of a tensor
 that is not 5-D ([B, C, X, Y, Z]: dimension 3) or in a format other than "BCXXX" / "BXXXC", dense() on a per-axis tensor stride, strides other than 1 and 2, a generative layer at stride 2 on an odd
@@ -232,6 +266,7 @@ from .tensor import SparseTensor, CoordinateManager, CoordinateMapKey, cat, pref
 from .tensor import TensorField, SparseTensorQuantizationMode  # noqa: F401
 from .tensor import to_sparse, to_sparse_all  # noqa: F401
 from .tensor import RegionType, KernelGenerator  # noqa: F401
+from .tensor import farthest_point_sampling  # noqa: F401  (engine extra: the seeds of the attention blocks' queries)
 from .modules import (MinkowskiConvolution, MinkowskiConvolutionTranspose, MinkowskiBatchNorm,  # noqa: F401
                       MinkowskiReLU, prepare_conv_weights, release_conv_weights,
                       MinkowskiMaxPooling, MinkowskiAvgPooling, MinkowskiSumPooling, MinkowskiGlobalMaxPooling,

@@ -829,6 +829,17 @@ class CoordinateManager:
             hit = cache[ts] = (chunk_seg.to(offsets.device), chunk_first.to(offsets.device), chunk_seg.numel())
         return hit
 
+    def batch_lengths(self, ts):
+        """the number of rows of every segment of batch_rows(ts) as a tuple of Python ints: one host read, once per tensor
+        stride, kept beside batch_rows and batch_chunks (farthest_point_sampling refuses more picks than a sample has rows).
+        An engine extra."""
+        cache = self.__dict__.setdefault("_batch_lengths", {})
+        hit = cache.get(ts)
+        if hit is None:
+            off = self.batch_rows(ts)[2].tolist()
+            hit = cache[ts] = tuple(off[i + 1] - off[i] for i in range(len(off) - 1))
+        return hit
+
     def caller_rows(self, ts):
         """int32 [V]: for every row of the set as it is HELD, the row of .coordinates / .features the caller sees it at; None
         where the two orders are the same (no Morton permutation, or a coarser set).  Built once."""
@@ -1400,6 +1411,34 @@ class TensorField:
             p = self._shared["points"] = self._C.to(torch.float32)
         return p
 
+    def _points32(self):
+        """the coordinates as ONE contiguous float32 tensor [N, 4] (float64 points are taken to float32 once)"""
+        p = self._points()
+        if p.dtype == torch.float32 and p.is_contiguous():
+            return p
+        q = self._shared.get("points32")
+        if q is None:
+            q = self._shared["points32"] = p.to(torch.float32).contiguous()
+        return q
+
+    def _batch_group(self):
+        """the points grouped by batch index, as CoordinateManager.batch_rows groups rows -> (order int64 [N]: the points
+        sorted by batch index, stable; offsets int32 [B + 1] into `order`, one segment per batch index PRESENT, ascending; the
+        segment lengths as a tuple of Python ints; seg int32 [N]: the segment of every point).  One stable sort of the batch
+        column and one host read, once per field."""
+        g = self._shared.get("batch_group")
+        if g is None:
+            b = self._C[:, 0].long()
+            sb, order = torch.sort(b, stable=True)
+            _, counts = torch.unique_consecutive(sb, return_counts=True)
+            offsets = torch.zeros(counts.numel() + 1, dtype=torch.int32, device=b.device)
+            offsets[1:] = torch.cumsum(counts, 0)
+            seg = torch.empty(order.numel(), dtype=torch.int32, device=b.device)
+            seg[order] = torch.repeat_interleave(torch.arange(counts.numel(), dtype=torch.int32, device=b.device), counts,
+                                                 output_size=order.numel())
+            g = self._shared["batch_group"] = (order.contiguous(), offsets, tuple(counts.tolist()), seg)
+        return g
+
     def _quantized(self, ts):
         """int32 [N, 4]: the voxel of every point at tensor stride ts, floor(p / ts) * ts per axis (floor, not truncation:
         -0.5 -> -ts); the batch column is taken as an integer"""
@@ -1487,6 +1526,130 @@ class TensorField:
     def cat_slice(self, x):
         """.slice(x) with the field's own features concatenated in front"""
         return self._like(torch.cat([self._F, self.slice(x)._F], 1))
+
+
+_FPS_MAX_B = 65535                       # the limit of csrc/fps.hip
+_FPS_LO, _FPS_HI = -16384, 16384         # the packable range: squared distances inside it fit unsigned 32-bit arithmetic
+
+
+def _fps_torch(points, batch, lengths, M, start):
+    """the rule of farthest_point_sampling as a torch expression: a loop of M steps over all samples at once.  points [V, 3]
+    (int64: exact distances; float32: every operation rounded to float32) and batch [V] in the CALLER's row order, lengths:
+    the rows of every sample present (ascending batch index), start: int64 [B] caller rows or None -> int64 [B, M].  A sample
+    is laid out in ascending caller row and argmax returns the first of equal values, hence the lowest caller row."""
+    B, L, V, dev = len(lengths), max(lengths), points.size(0), points.device
+    rows = torch.sort(batch, stable=True).indices
+    n = torch.tensor(lengths, dtype=torch.int64, device=dev)
+    pos = torch.arange(L, device=dev)
+    valid = pos[None, :] < n[:, None]
+    idx = rows[((torch.cumsum(n, 0) - n)[:, None] + pos[None, :]).clamp(max=V - 1)]     # [B, L]; the padding is never chosen
+    P = points[idx]
+    ar = torch.arange(B, device=dev)
+    at = torch.zeros(B, dtype=torch.int64, device=dev) if start is None else ((idx == start[:, None]) & valid).int().argmax(1)
+    big = float("inf") if P.is_floating_point() else torch.iinfo(torch.int64).max
+    nearest = torch.full((B, L), big, dtype=P.dtype, device=dev)
+    out = torch.empty((B, M), dtype=torch.int64, device=dev)
+    for j in range(M):
+        if j:
+            d = P - P[ar, at].unsqueeze(1)
+            d = d * d
+            nearest = torch.minimum(nearest, (d[..., 0] + d[..., 1]) + d[..., 2])
+            at = torch.where(valid, nearest, -1).argmax(1)
+        out[:, j] = idx[ar, at]
+    return out
+
+
+def farthest_point_sampling(x, num_samples, start=None):
+    """Farthest point sampling per sample (an engine extra: MinkowskiEngine has no such function) -- the seeds of a mask
+    transformer's queries, the grouping stage of a point network.  x: a SparseTensor (any tensor stride its manager holds, any
+    manager: plain, Morton-sorted, rooted) or a TensorField.  -> int64 [B, M], M = num_samples (a Python int >= 1), B the number
+    of batch indices PRESENT; row b belongs to the b-th of them in ascending order -- the numbering of
+    CoordinateManager.batch_rows, of origin_map, of the global pooling layers and of query_attention; gaps in the batch indices
+    and interleaved rows are fine.  The values are rows of x.F / x.C as the caller sees them, on a Morton-sorted manager too:
+    x.F[idx] is [B, M, C], ready for MinkowskiQueryAttention; x.C[idx][..., 1:] are the positions.
+
+    The rule, all of it: pick 0 of a sample is start[b], without `start` the sample's lowest caller row; pick j is the row of the
+    sample whose distance to the nearest of the picks 0 .. j-1 is largest; among equal distances the lowest caller row wins;
+    rows already picked have distance 0 and take part like any other row.  So the result is a pure function of the coordinates
+    -- the same bytes on every run, whatever order the manager holds its rows in.
+
+    Distances.  SparseTensor: the exact integer dx^2 + dy^2 + dz^2 of the coordinates at the tensor's stride, in unsigned 32-bit
+    arithmetic (up to 3 * 32767^2 = 3 221 028 867 over the packable range [-16384, 16384); a coordinate outside that range is a
+    ValueError).  TensorField: its float32 points (float64 input is taken to float32 first), d = (dx*dx + dy*dy) + dz*dz with
+    dx = p.x - c.x, every operation rounded to float32 on its own and never contracted into an FMA, the running minimum by
+    fminf.  Finite coordinates are a precondition and are not checked.  Duplicate points are legal: once every remaining
+    distance is 0 the rule repeats the lowest row.
+
+    start: an int64 tensor [B] of caller rows, one inside each sample in the numbering above; a wrong shape or dtype, a row
+    outside its sample or another B is a ValueError.  Checking it is one host read, made only when start is given.
+    num_samples larger than the smallest sample is a ValueError naming the sample and its size (the segment lengths are read on
+    the host once per coordinate set or field).  An empty tensor gives an empty [0, M] result.
+
+    Device tensors: one launch of csrc/fps.hip, one workgroup per sample, no atomics, no waiting between workgroups; a sample of
+    at most ms3d_fps_resident_rows() rows stays in registers, a larger one is swept from a workspace every pick.  The rows are
+    read where the manager holds them; nothing is permuted or copied.  CPU tensors: the same rule as a torch expression, a loop
+    of M steps.  The index is not differentiable: gradients reach x.F through the caller's x.F[idx] or ME.gather_rows.
+    Out of scope: other metrics, feature-space sampling, a different M per sample, float16 or float64 distances, gradients
+    with respect to the coordinates, kNN or ball grouping around the picks."""
+    name = "farthest_point_sampling"
+    if isinstance(num_samples, bool) or not isinstance(num_samples, int) or num_samples < 1:
+        raise ValueError(f"{name}: num_samples must be a Python int >= 1, got {num_samples!r}")
+    M = num_samples
+    if isinstance(x, SparseTensor):
+        cm, ts = x.coordinate_manager, x.tensor_stride
+        data = cm.coords[ts]
+        V = data.size(0)
+        if V:
+            order, _, offsets, _ = cm.batch_rows(ts)
+            lengths, row_map, seg = cm.batch_lengths(ts), cm.caller_rows(ts), cm.batch_segments(ts)
+            held_of = cm.inv if row_map is not None else None
+            lo, hi, _ = cm.extent(ts)
+            if min(lo) < _FPS_LO or max(hi) >= _FPS_HI:
+                raise ValueError(f"{name}: coordinates from {min(lo)} to {max(hi)} leave the packable range [{_FPS_LO}, {_FPS_HI}), "
+                                 "outside which squared distances do not fit 32 bits")
+    elif isinstance(x, TensorField):
+        data = x._points32()
+        V = data.size(0)
+        if V:
+            order, offsets, lengths, seg = x._batch_group()
+            row_map = held_of = None
+    else:
+        raise TypeError(f"{name}: x must be a SparseTensor or a TensorField, got {type(x).__name__}")
+    dev = data.device
+    if V == 0:
+        if start is not None and (not torch.is_tensor(start) or start.dtype != torch.int64 or tuple(start.shape) != (0,)):
+            raise ValueError(f"{name}: start must be an int64 tensor [B] with B = 0, the samples of x")
+        return torch.empty((0, M), dtype=torch.int64, device=dev)
+    B = len(lengths)
+    small = min(range(B), key=lengths.__getitem__)
+    if M > lengths[small]:
+        raise ValueError(f"{name}: num_samples = {M} is larger than sample {small}, which has {lengths[small]} rows")
+    if B > _FPS_MAX_B:
+        raise ValueError(f"{name}: B = {B} is above the kernel's limit of {_FPS_MAX_B}")
+    start_held = None
+    if start is not None:
+        if not torch.is_tensor(start) or start.dtype != torch.int64:
+            raise ValueError(f"{name}: start must be an int64 tensor [B] of caller rows, got "
+                             f"{getattr(start, 'dtype', type(start).__name__)}")
+        if tuple(start.shape) != (B,):
+            raise ValueError(f"{name}: start must have shape [B] = [{B}], one row per sample of x, got {list(start.shape)}")
+        start = start.to(dev)
+        inside = (start >= 0) & (start < V)
+        start_held = start.clamp(0, V - 1)
+        if held_of is not None:
+            start_held = held_of[start_held]
+        inside &= seg[start_held] == torch.arange(B, dtype=torch.int32, device=dev)
+        if not bool(inside.all()):
+            bad = int((~inside).nonzero()[0])
+            raise ValueError(f"{name}: start[{bad}] = {int(start[bad])} is not a row of sample {bad}")
+    if not data.is_cuda:
+        batch = x.C[:, 0].long()
+        points = x.C[:, 1:].long() if isinstance(x, SparseTensor) else data[:, 1:]
+        return _fps_torch(points, batch, lengths, M, start)
+    be = get_backend()
+    if not hasattr(be, "fps"):
+        raise NotImplementedError(f"{name} on device tensors needs the HIP backend (ms3d_fps_i32)")
+    return be.fps(data, order, offsets, row_map, None if start_held is None else start_held.contiguous(), M)
 
 
 def _dense_input(x, format, device):

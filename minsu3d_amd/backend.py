@@ -1446,6 +1446,35 @@ class _HipEngine:
                    "ms3d_vattn_backward_kv")
         return dk, dv
 
+    # ---- farthest point sampling over the batch grouping of a coordinate set or a field (csrc/fps.hip)
+    def fps_resident_rows(self):
+        return int(self.lib.ms3d_fps_resident_rows())
+
+    def fps(self, data, order, seg_start, row_map, start_held, M):
+        """-> int64 [B, M] caller rows: M farthest-point picks per sample.  data [V, 4] on the device as held: int32
+        coordinates (exact integer distances) or float32 points (float32 distances, no FMA), batch column first; order int64
+        [V] / seg_start int32 [B + 1]: the rows of every sample (CoordinateManager.batch_rows); row_map int32 [V] held row ->
+        caller's row, or None; start_held int64 [B] held rows, or None (the lowest caller row of every sample)."""
+        if not hasattr(self.lib, "ms3d_fps_i32"):
+            raise NotImplementedError("farthest point sampling needs a library with ms3d_fps_i32")
+        assert data.is_cuda and data.is_contiguous() and data.dim() == 2 and data.size(1) == 4
+        assert data.dtype in (torch.int32, torch.float32)
+        V, B, dev = data.size(0), seg_start.numel() - 1, data.device
+        assert order.dtype == torch.int64 and order.is_contiguous() and order.numel() == V and order.device == dev
+        assert seg_start.dtype == torch.int32 and seg_start.is_contiguous() and seg_start.dim() == 1 and seg_start.device == dev
+        if row_map is not None:
+            assert row_map.dtype == torch.int32 and row_map.is_contiguous() and row_map.numel() == V and row_map.device == dev
+        if start_held is not None:
+            assert start_held.dtype == torch.int64 and start_held.is_contiguous() and tuple(start_held.shape) == (B,)
+            assert start_held.device == dev
+        out = torch.empty((B, int(M)), dtype=torch.int64, device=dev)
+        ws = self.ws.get("fps", self.lib.ms3d_fps_ws_bytes(C.c_long(V), int(B)), dev)
+        name = "ms3d_fps_i32" if data.dtype == torch.int32 else "ms3d_fps_f32"
+        _lib.check(getattr(self.lib, name)(_lib.ptr(data), _lib.ptr(order), _lib.ptr(seg_start), _lib.ptr(row_map),
+                                           _lib.ptr(start_held), int(V), int(B), int(M), _lib.ptr(out), _lib.ptr(ws),
+                                           C.c_size_t(ws.numel()), _lib.stream_handle()), name)
+        return out
+
     # ---- instance normalisation over the batch grouping of a coordinate set (csrc/inorm.hip)
     def _inorm_check(self, x, order, seg_start, seg_of_row):
         assert x.dtype == torch.float32 and x.dim() == 2
