@@ -556,6 +556,48 @@ int ms3d_fps_f32(const float *points /*[N][4], N = V*/, const long long *order /
                  const int *row_map /*[V] held -> caller, or NULL*/, const long long *start_held /*[B] or NULL*/, int V, int B,
                  int M, long long *out /*[B][M] caller rows*/, void *ws, size_t ws_bytes, ms3d_stream_t stream);
 
+/* ---- k nearest neighbours per sample (csrc/knn.hip): what follows the sampling above -- grouping rows around the picks,
+ * carrying features of the picks back to every row, kNN graphs.  The support set is given exactly as to ms3d_fps_*: coords
+ * [V][4] int32 / points [V][4] float32 (batch, x, y, z) as held, the rows of sample b are order[seg_start[b] .. seg_start[b + 1]),
+ * the CALLER's row of held row i is row_map[i], or i when row_map is NULL.  The queries come packed: 32-bit words [NQ][4] =
+ * (segment, x, y, z) -- int32 coordinates for i32, the bits of float32 points for f32 -- grouped by segment, the queries of
+ * segment b at q_start[b] .. q_start[b + 1] (int32 [B + 1]); max_queries: the largest number of queries any segment has (host
+ * arithmetic on the segment lengths; it sizes the grid, queries beyond it in a segment are not served).
+ *   out_idx[q][0 .. k) = the caller rows of the k rows of the query's segment with the smallest keys (distance bits << 32) | caller
+ *                        row, in ascending key order: nearer first, among equal distances the lower caller row; the query's own
+ *                        row, if it is one of the set, is found like any other (first, at distance 0)
+ *   out_d2[q][0 .. k)  = their distances (i32: unsigned 32-bit words; f32: float32)
+ * A row qualifies when its distance is <= max_d2 (the boundary included; max_d2 < 0: no cap; i32 caps above 2^32 - 1 are no
+ * cap).  Slots no row qualifies for -- a segment of fewer than k rows, a cap, a query whose segment word is not the segment it
+ * is filed under -- hold -1 and the distance word of "none" (i32: all ones; f32: +inf), after every qualifying slot.  Real keys
+ * are distinct, so the result is a pure function of the coordinates and does not depend on how the rows are held.
+ * Distances are ms3d_fps_*'s: i32 the exact integer dx^2 + dy^2 + dz^2 in unsigned 32-bit arithmetic over the packable range
+ * [-16384, 16384) of BOTH sets (up to 3 221 028 867); f32 d = (dx*dx + dy*dy) + dz*dz with dx = q.x - p.x, every operation rounded
+ * to float32 on its own, never contracted into an FMA; finite coordinates are a precondition and are not checked.
+ * Two launches: the support set is packed into ws in segment order, 16 B a row (every word read is written first: ws is never
+ * assumed zero; `order` is clamped there); then workgroup (g, b) of ms3d_knn_queries_per_group() threads takes that many queries
+ * of segment b, a thread a query, and streams the segment through LDS in tiles of ms3d_knn_rows_per_tile() rows; a thread's
+ * list of its k smallest keys lives in LDS and is put in order at the end.  No atomics, no spin, no grid barrier; every loop is counted.  ws: ms3d_knn_ws_bytes(V)
+ * bytes, 16-byte aligned.
+ * V < 0, B < 0, B > 65535, NQ < 0, max_queries < 0, k < 1, k > ms3d_knn_max_k(): MS3D_E_UNSUPPORTED.  Otherwise V == 0, B == 0,
+ * NQ == 0 or max_queries == 0: 0, nothing is launched, no pointer is looked at.  Then a NULL coords / points, order, seg_start,
+ * queries, q_start, out_idx, out_d2 or ws, or a ws that is not 16-byte aligned: MS3D_E_UNSUPPORTED; a short workspace:
+ * MS3D_E_WORKSPACE; all decided on the host before a launch.  seg_start and q_start values are clamped to their arrays. */
+int ms3d_knn_max_k(void);
+int ms3d_knn_queries_per_group(void);
+int ms3d_knn_rows_per_tile(void);
+size_t ms3d_knn_ws_bytes(long V);
+int ms3d_knn_i32(const int *coords /*[V][4] as held*/, const long long *order /*[V]*/, const int *seg_start /*[B + 1]*/,
+                 const int *row_map /*[V] held -> caller, or NULL*/, int V, int B, const int *queries /*[NQ][4]*/,
+                 const int *q_start /*[B + 1]*/, int NQ, int max_queries, int k, long long max_d2 /*< 0: none*/,
+                 long long *out_idx /*[NQ][k] caller rows*/, unsigned *out_d2 /*[NQ][k]*/, void *ws, size_t ws_bytes,
+                 ms3d_stream_t stream);
+int ms3d_knn_f32(const float *points /*[V][4] as held*/, const long long *order /*[V]*/, const int *seg_start /*[B + 1]*/,
+                 const int *row_map /*[V] held -> caller, or NULL*/, int V, int B, const int *queries /*[NQ][4] words*/,
+                 const int *q_start /*[B + 1]*/, int NQ, int max_queries, int k, float max_d2 /*< 0: none*/,
+                 long long *out_idx /*[NQ][k] caller rows*/, float *out_d2 /*[NQ][k]*/, void *ws, size_t ws_bytes,
+                 ms3d_stream_t stream);
+
 /* ---- instance normalisation: per batch index (segment) and channel (csrc/inorm.hip; float32 rows and parameters, any C >= 1;
  * every sum, the statistics mean / invstd (DOUBLE [B, C]) and the arithmetic of the row passes are float64, rounded once at the
  * store: with few rows in a segment dx is a difference of nearly equal terms that float32 statistics cannot resolve; a lane takes four

@@ -245,8 +245,48 @@ network (an engine extra: MinkowskiEngine has no such function, and nothing here
     is gathered once into a workspace and swept every pick.  CPU tensors take the same rule as a torch expression, a loop
     of M steps.  The index is not differentiable: gradients reach x.F through x.F[idx] or gather_rows.
     Out of scope: other metrics, feature-space sampling, a different M per sample, float16 or float64 distances, gradients
-    with respect to the coordinates, kNN or ball grouping around the picks; a backend without the kernels raises
-    NotImplementedError naming ms3d_fps_i32 for device tensors.
+    with respect to the coordinates; a backend without the kernels raises NotImplementedError naming ms3d_fps_i32 for device
+    tensors.  Grouping rows around the picks: knn_query(x, k, idx), below.
+
+k nearest neighbours per sample -- what follows the sampling: grouping rows around the picks, carrying features of M picks
+back to all V rows (three-nearest inverse-distance unpooling), kNN graphs for vector attention (an engine extra: MinkowskiEngine
+has no such function, and nothing here is pinned to it):
+
+    knn_query(x, k, queries=None, max_squared_distance=None) -> (idx int64 [..., k], d2 [..., k])
+
+    x, the support set: a SparseTensor (any tensor stride its manager holds; a plain, Morton-sorted or rooted manager) or a
+    TensorField; k a Python int, 1 <= k <= 64 (ms3d_knn_max_k()).  queries: None -- every row of x queries its own sample,
+    [V, k], row i answers caller row i; an int64 tensor [B, M] of caller rows of x, exactly what farthest_point_sampling
+    returns (row b inside the b-th batch index present; duplicates are legal; one host read to check it, only for this form) --
+    [B, M, k]; or another tensor y of the same kind (SparseTensor with SparseTensor, strides and managers may differ, or
+    TensorField with TensorField): every row of y queries the sample of x with the same batch index VALUE, [V_y, k] in y's
+    caller row order (a batch index of y that x lacks is a ValueError naming it, samples of x without queries are fine,
+    mixed kinds are a TypeError).
+    The rule, all of it: for a query at position p in sample b, the k rows of sample b of x with the smallest keys (distance
+    to p, caller row of x), in ascending key order; among equal distances the lowest caller row comes first; a query that is
+    itself a row of x finds itself first, at distance 0.  A pure function of the coordinates: the same bytes on every run,
+    whatever order the manager holds its rows in.  The values are rows of x.F / x.C as the caller sees them: x.F[idx] is
+    [..., k, C].
+    Distances are farthest_point_sampling's: on a SparseTensor the exact integer dx^2 + dy^2 + dz^2 in unsigned 32-bit
+    arithmetic over the packable range [-16384, 16384) of both sets, returned as int64 (it reaches 3 221 028 867); on a
+    TensorField float32, d = (dx*dx + dy*dy) + dz*dz with dx = q.x - p.x, every operation rounded on its own, no FMA, returned
+    as float32.  max_squared_distance: a Python int (SparseTensor) or float (TensorField, taken to float32) >= 0; a row
+    qualifies when d2 <= cap, the boundary included; slots nothing qualifies for hold idx = -1 and d2 = -1 / +inf, after all
+    the qualifying slots -- mask before indexing.  Without a cap the result never contains -1.
+    ValueError: k out of range or larger than the smallest sample of x that has queries (naming it; from the cached
+    batch_lengths), a cap of the wrong type or negative, a bad [B, M] tensor, coordinates outside the packable range, more
+    than 65535 samples.  Empty x or queries give empty [0, k] / [B, 0, k] results.
+    csrc/knn.hip: the support set is read where it is held (cm.coords, batch_rows and caller_rows as they are) and packed
+    once in segment order, 16 B a row; then one workgroup takes ms3d_knn_queries_per_group() queries of one sample, a thread a
+    query, and streams the sample through LDS in tiles of ms3d_knn_rows_per_tile() rows.  A thread's list of its k smallest 64-bit
+    keys, (distance bits << 32) | caller row, lives in LDS; candidates are held back and inserted by all lanes of a wave
+    together.  No atomics, no waiting between workgroups, every loop counted.  CPU tensors take the same rule as a torch
+    expression, at most 2^22 (query, row) pairs at a time.  The index is not differentiable; gradients reach x.F through
+    x.F[idx].
+    Out of scope: spatial acceleration (a grid or hash walk), a fused neighbour gather or interpolation layer, mixed voxel /
+    point queries, other metrics, a different k per query, k above 64, float16 or float64 distances, gradients with respect
+    to the coordinates, a ball query's first-k-inside-the-radius order; a backend without the kernels raises
+    NotImplementedError naming ms3d_knn_i32 for device tensors.
 
 Not supported (each raises NotImplementedError naming it): `axis_types` of a KernelGenerator, a region of more than 254
 offsets, a dense grid of more than 2^31 - 1 cells, to_sparse of a tensor
@@ -267,6 +307,7 @@ from .tensor import TensorField, SparseTensorQuantizationMode  # noqa: F401
 from .tensor import to_sparse, to_sparse_all  # noqa: F401
 from .tensor import RegionType, KernelGenerator  # noqa: F401
 from .tensor import farthest_point_sampling  # noqa: F401  (engine extra: the seeds of the attention blocks' queries)
+from .tensor import knn_query  # noqa: F401  (engine extra: the k nearest rows of a query's own sample)
 from .modules import (MinkowskiConvolution, MinkowskiConvolutionTranspose, MinkowskiBatchNorm,  # noqa: F401
                       MinkowskiReLU, prepare_conv_weights, release_conv_weights,
                       MinkowskiMaxPooling, MinkowskiAvgPooling, MinkowskiSumPooling, MinkowskiGlobalMaxPooling,

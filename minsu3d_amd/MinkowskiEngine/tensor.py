@@ -840,6 +840,18 @@ class CoordinateManager:
             hit = cache[ts] = tuple(off[i + 1] - off[i] for i in range(len(off) - 1))
         return hit
 
+    def batch_indices(self, ts):
+        """the batch indices present, ascending, as a tuple of Python ints -- the batch index of every segment of
+        batch_rows(ts): one host read, once per tensor stride, kept beside batch_lengths (knn_query pairs the samples of two
+        sets by batch index VALUE).  An engine extra."""
+        cache = self.__dict__.setdefault("_batch_indices", {})
+        hit = cache.get(ts)
+        if hit is None:
+            order, _, offsets, _ = self.batch_rows(ts)
+            first = order[offsets[:-1].long()] if order.numel() else order[:0]
+            hit = cache[ts] = tuple(int(v) for v in self.coords[ts][first, 0].tolist())
+        return hit
+
     def caller_rows(self, ts):
         """int32 [V]: for every row of the set as it is HELD, the row of .coordinates / .features the caller sees it at; None
         where the two orders are the same (no Morton permutation, or a coarser set).  Built once."""
@@ -1439,6 +1451,16 @@ class TensorField:
             g = self._shared["batch_group"] = (order.contiguous(), offsets, tuple(counts.tolist()), seg)
         return g
 
+    def _batch_indices(self):
+        """the batch indices present, ascending, as a tuple of Python ints -- the batch index of every segment of _batch_group;
+        one host read, once per field"""
+        hit = self._shared.get("batch_indices")
+        if hit is None:
+            order, offsets, _, _ = self._batch_group()
+            first = order[offsets[:-1].long()] if order.numel() else order[:0]
+            hit = self._shared["batch_indices"] = tuple(int(v) for v in self._C[first, 0].tolist())
+        return hit
+
     def _quantized(self, ts):
         """int32 [N, 4]: the voxel of every point at tensor stride ts, floor(p / ts) * ts per axis (floor, not truncation:
         -0.5 -> -ts); the batch column is taken as an integer"""
@@ -1590,7 +1612,7 @@ def farthest_point_sampling(x, num_samples, start=None):
     read where the manager holds them; nothing is permuted or copied.  CPU tensors: the same rule as a torch expression, a loop
     of M steps.  The index is not differentiable: gradients reach x.F through the caller's x.F[idx] or ME.gather_rows.
     Out of scope: other metrics, feature-space sampling, a different M per sample, float16 or float64 distances, gradients
-    with respect to the coordinates, kNN or ball grouping around the picks."""
+    with respect to the coordinates.  Grouping rows around the picks: knn_query(x, k, idx)."""
     name = "farthest_point_sampling"
     if isinstance(num_samples, bool) or not isinstance(num_samples, int) or num_samples < 1:
         raise ValueError(f"{name}: num_samples must be a Python int >= 1, got {num_samples!r}")
@@ -1650,6 +1672,237 @@ def farthest_point_sampling(x, num_samples, start=None):
     if not hasattr(be, "fps"):
         raise NotImplementedError(f"{name} on device tensors needs the HIP backend (ms3d_fps_i32)")
     return be.fps(data, order, offsets, row_map, None if start_held is None else start_held.contiguous(), M)
+
+
+_KNN_MAX_K = 64                          # ms3d_knn_max_k() of csrc/knn.hip
+_KNN_CHUNK = 1 << 22                     # the CPU path holds at most this many (query, row) pairs at a time
+
+
+class _KnnSet:
+    """one side of knn_query -- a SparseTensor or a TensorField as csrc/knn.hip takes it: data [V, 4] as HELD (int32
+    coordinates / float32 points), order and offsets of the batch grouping, the segment lengths (host), row_map held row ->
+    caller row (or None), seg: the segment of every held row, held_of: caller row -> held row (or None)"""
+
+    def __init__(self, x, name, what):
+        self.x, self.order, self.offsets, self.lengths, self.row_map, self.seg, self.held_of = x, None, None, (), None, None, None
+        if isinstance(x, SparseTensor):
+            cm, ts = x.coordinate_manager, x.tensor_stride
+            self.kind, self.data = SparseTensor, cm.coords[ts]
+            if self.data.size(0):
+                self.order, _, self.offsets, _ = cm.batch_rows(ts)
+                self.lengths, self.row_map, self.seg = cm.batch_lengths(ts), cm.caller_rows(ts), cm.batch_segments(ts)
+                self.held_of = cm.inv if self.row_map is not None else None
+                lo, hi, _ = cm.extent(ts)
+                if min(lo) < _FPS_LO or max(hi) >= _FPS_HI:
+                    raise ValueError(f"{name}: coordinates from {min(lo)} to {max(hi)} leave the packable range [{_FPS_LO}, "
+                                     f"{_FPS_HI}), outside which squared distances do not fit 32 bits")
+        elif isinstance(x, TensorField):
+            self.kind, self.data = TensorField, x._points32()
+            if self.data.size(0):
+                self.order, self.offsets, self.lengths, self.seg = x._batch_group()
+        else:
+            raise TypeError(f"{name}: {what} must be a SparseTensor or a TensorField, got {type(x).__name__}")
+        self.V = self.data.size(0)
+
+    def present(self):
+        """the batch index of every segment (host, cached with the set)"""
+        if not self.V:
+            return ()
+        if self.kind is SparseTensor:
+            return self.x.coordinate_manager.batch_indices(self.x.tensor_stride)
+        return self.x._batch_indices()
+
+    def words(self, held, segment):
+        """the rows `held` as packed queries: int32 words [n, 4] = (segment, x, y, z)"""
+        w = self.data[held]
+        w = w if w.dtype == torch.int32 else w.view(torch.int32)
+        w[:, 0] = segment
+        return w
+
+    def caller_of_order(self):
+        """the caller row of every position of `order`"""
+        return self.order if self.row_map is None else self.row_map[self.order].long()
+
+
+def _knn_torch(points, batch, lengths, qpoints, q_counts, k, cap):
+    """the rule of knn_query as a torch expression.  points [V, 3] (int64: exact distances; float32: every operation rounded
+    to float32) and batch [V] in the CALLER's row order, lengths: the rows of every sample present (ascending batch index);
+    qpoints [NQ, 3] the queries grouped by sample, q_counts of them for each -> (int64 [NQ, k] caller rows, int64 / float32
+    [NQ, k] distances).  Per sample the queries go in chunks of at most max(1, _KNN_CHUNK // V_b), so no more than _KNN_CHUNK
+    = 2^22 (query, row) pairs are held at a time; per chunk one int64 key (distance bits << 31) | caller row -- 3 221 028 867 *
+    2^31 < 2^63, and the bits of a non-negative float32 are below 2^31 -- and one torch.topk over the distinct keys."""
+    dev, integer, NQ = points.device, not points.is_floating_point(), qpoints.size(0)
+    rows = torch.sort(batch, stable=True).indices
+    idx = torch.full((NQ, k), -1, dtype=torch.int64, device=dev)
+    d2 = torch.full((NQ, k), -1 if integer else float("inf"), dtype=points.dtype, device=dev)
+    s = q = 0
+    for n, m in zip(lengths, q_counts):
+        r = rows[s:s + n]
+        P = points[r]
+        step, kk = max(1, _KNN_CHUNK // max(n, 1)), min(k, n)
+        for c in range(q, q + m if kk else q, step):
+            Q = qpoints[c:min(c + step, q + m)]
+            dx, dy, dz = (Q[:, a:a + 1] - P[:, a][None, :] for a in range(3))
+            d = (dx * dx + dy * dy) + dz * dz                     # three products, two sums, each rounded on its own
+            bits = d if integer else d.view(torch.int32).long()
+            top = torch.topk((bits << 31) | r[None, :], kk, dim=1, largest=False, sorted=True).values
+            idx[c:c + Q.size(0), :kk] = top & (2 ** 31 - 1)
+            top = top >> 31
+            d2[c:c + Q.size(0), :kk] = top if integer else top.to(torch.int32).view(torch.float32)
+        s, q = s + n, q + m
+    if cap is not None:
+        far = d2 > cap
+        idx[far] = -1
+        d2[far] = -1 if integer else float("inf")
+    return idx, d2
+
+
+def knn_query(x, k, queries=None, max_squared_distance=None):
+    """The k nearest rows of a query's own sample (an engine extra: MinkowskiEngine has no such function) -- grouping rows
+    around the picks of farthest_point_sampling, carrying features of M picks back to all V rows (three-nearest inverse
+    distance unpooling), kNN graphs for vector attention.  -> (idx int64 [..., k], d2 [..., k]).
+
+    x, the support set: a SparseTensor (any tensor stride its manager holds; a plain, Morton-sorted or rooted manager) or a
+    TensorField.  k: a Python int, 1 <= k <= 64 (ms3d_knn_max_k()).  queries:
+      None             every row of x queries its own sample -> [V, k]; row i answers caller row i of x.
+      int64 [B, M]     caller rows of x, the form farthest_point_sampling returns: row b lies inside the b-th batch index present
+                       (the numbering of batch_rows, origin_map and query_attention) -> [B, M, k].  Duplicates inside a row are
+                       legal.  A row outside its sample, another B, a wrong dtype or shape is a ValueError; that check is one
+                       host read, made only for this form.
+      y                another tensor of the same kind as x (SparseTensor with SparseTensor -- tensor strides and managers
+                       may differ -- or TensorField with TensorField): every row of y queries the sample of x with the same batch
+                       index VALUE -> [V_y, k] in y's caller row order.  A batch index present in y and absent from x is a
+                       ValueError naming it; samples of x without queries are fine.  Mixed kinds are a TypeError.
+
+    The rule, all of it: for a query at position p in sample b the answer is the k rows of sample b of x with the smallest keys
+    (distance to p, caller row of x), in ascending key order.  Among equal distances the lowest caller row comes first.  A query
+    that is itself a row of x finds itself first, at distance 0 (nothing is excluded).  The result is a pure function of the
+    coordinates: the same bytes on every run, whatever order the manager holds its rows in.  The values are rows of x.F / x.C
+    as the caller sees them: x.F[idx] is [..., k, C].
+
+    Distances are those of farthest_point_sampling.  SparseTensor: the exact integer dx^2 + dy^2 + dz^2 in unsigned 32-bit
+    arithmetic over the packable range [-16384, 16384) of both sets (outside it: ValueError), returned as int64 because it
+    reaches 3 * 32767^2 = 3 221 028 867.  TensorField: float32 points (float64 is taken to float32 first), d = (dx*dx + dy*dy)
+    + dz*dz with dx = q.x - p.x, every operation rounded to float32 on its own, never contracted into an FMA; returned as
+    float32; finite coordinates are a precondition and are not checked.
+
+    max_squared_distance: None, or the largest distance that qualifies -- a Python int >= 0 for a SparseTensor, a Python float
+    >= 0 (taken to float32) for a TensorField; the boundary is included (d2 <= cap, on the values above).  Slots for which no
+    row qualifies hold idx = -1 and d2 = -1 (int64) / +inf (float32), after all the qualifying slots: mask before indexing
+    (x.F[idx] with idx = -1 reads the LAST row).  Without a cap the result never contains -1.
+
+    ValueError: k that is not an int in range; k larger than the smallest sample of x that has queries (naming the sample and
+    its size -- with a cap too, one rule; the lengths are the cached batch_lengths, no new host read); a cap of the wrong type
+    for the kind, or negative; more than 65535 samples.  TypeError: an unsupported x.  An empty x or empty queries give empty
+    [0, k] / [B, 0, k] results.  Host reads, each cached with the coordinate set or field: the segment lengths, the batch
+    indices present (the third form only) and the extent.
+
+    Device tensors: csrc/knn.hip -- the support set is read where it is held and packed once in segment order, then one workgroup
+    takes ms3d_knn_queries_per_group() queries of one sample, a thread a query, and streams the sample through LDS in tiles of
+    ms3d_knn_rows_per_tile() rows; a thread's list of its k smallest 64-bit keys, (distance bits << 32) | caller row, lives in LDS; no
+    atomics, no waiting between workgroups.  The queries are packed and the results put back into the caller's order by torch
+    gathers.  CPU tensors: the same rule as a torch expression (_knn_torch), at most 2^22 (query, row) pairs at a time.  The
+    index is not differentiable: gradients reach x.F through x.F[idx].
+    Out of scope: spatial acceleration (a grid or hash walk), a fused neighbour gather, mixed voxel / point queries, other
+    metrics, a different k per query, k above 64, float16 or float64 distances, gradients with respect to the coordinates,
+    the first-k-inside-the-radius order of a ball query (the cap keeps the nearest-first order)."""
+    name = "knn_query"
+    if isinstance(k, bool) or not isinstance(k, int) or not 1 <= k <= _KNN_MAX_K:
+        raise ValueError(f"{name}: k must be a Python int with 1 <= k <= {_KNN_MAX_K}, got {k!r}")
+    sup = _KnnSet(x, name, "x")
+    integer = sup.kind is SparseTensor
+    cap = max_squared_distance
+    if cap is not None:
+        if integer and (isinstance(cap, bool) or not isinstance(cap, int)):
+            raise ValueError(f"{name}: max_squared_distance must be a Python int >= 0 for a SparseTensor (its distances are exact "
+                             f"integers), got {cap!r}")
+        if not integer and not isinstance(cap, float):
+            raise ValueError(f"{name}: max_squared_distance must be a Python float >= 0 for a TensorField, got {cap!r}")
+        if not cap >= 0:
+            raise ValueError(f"{name}: max_squared_distance must be >= 0, got {cap!r}")
+        cap = min(cap, 2 ** 32 - 1) if integer else float(np.float32(cap))       # no distance is above 2^32 - 1
+    dev, B = sup.data.device, len(sup.lengths)
+    d2_dtype = torch.int64 if integer else torch.float32
+    shape, pos = None, None              # the result's leading shape; the caller's position of every packed query, or None
+
+    if queries is None:
+        if sup.V == 0:
+            return torch.empty((0, k), dtype=torch.int64, device=dev), torch.empty((0, k), dtype=d2_dtype, device=dev)
+        q_words, q_start, q_counts = sup.words(sup.order, sup.seg[sup.order]), sup.offsets, sup.lengths
+        pos = sup.caller_of_order()
+    elif torch.is_tensor(queries):
+        if queries.dtype != torch.int64:
+            raise ValueError(f"{name}: queries must be an int64 tensor [B, M] of caller rows of x, got {queries.dtype}")
+        if queries.dim() != 2 or queries.size(0) != B:
+            raise ValueError(f"{name}: queries must have shape [B, M] with B = {B}, the samples of x, got {list(queries.shape)}")
+        M = queries.size(1)
+        shape = (B, M)
+        if B * M == 0:
+            return torch.empty((B, M, k), dtype=torch.int64, device=dev), torch.empty((B, M, k), dtype=d2_dtype, device=dev)
+        queries = queries.to(dev)
+        inside = (queries >= 0) & (queries < sup.V)
+        held = queries.clamp(0, sup.V - 1)
+        if sup.held_of is not None:
+            held = sup.held_of[held]
+        segment = torch.arange(B, dtype=torch.int32, device=dev)
+        inside &= sup.seg[held] == segment[:, None]
+        if not bool(inside.all()):                               # the one host read of this form
+            b, j = (int(v) for v in (~inside).nonzero()[0])
+            raise ValueError(f"{name}: queries[{b}, {j}] = {int(queries[b, j])} is not a row of sample {b}")
+        q_words = sup.words(held.reshape(-1), segment.repeat_interleave(M))
+        q_start, q_counts = torch.arange(B + 1, dtype=torch.int32, device=dev) * M, (M,) * B
+    elif isinstance(queries, (SparseTensor, TensorField)):
+        if not isinstance(queries, sup.kind):
+            raise TypeError(f"{name}: mixed kinds -- x is a {sup.kind.__name__} and queries a {type(queries).__name__}; voxels "
+                            "query voxels and points query points")
+        qs = _KnnSet(queries, name, "queries")
+        if qs.data.device != dev:
+            raise ValueError(f"{name}: x is on {dev} and queries on {qs.data.device}")
+        if qs.V == 0:
+            return torch.empty((0, k), dtype=torch.int64, device=dev), torch.empty((0, k), dtype=d2_dtype, device=dev)
+        segment_of = {bi: s for s, bi in enumerate(sup.present())}
+        absent = [bi for bi in qs.present() if bi not in segment_of]
+        if absent:
+            raise ValueError(f"{name}: batch index {absent[0]} is present in queries and absent from x")
+        target = [segment_of[bi] for bi in qs.present()]         # ascending, as both lists are
+        counts = [0] * B
+        for s, n in zip(target, qs.lengths):
+            counts[s] = n
+        starts = [0]
+        for n in counts:
+            starts.append(starts[-1] + n)
+        lut = torch.tensor(target, dtype=torch.int32, device=dev)
+        q_words = qs.words(qs.order, lut[qs.seg[qs.order].long()])
+        q_start, q_counts = torch.tensor(starts, dtype=torch.int32, device=dev), tuple(counts)
+        pos = qs.caller_of_order()
+    else:
+        raise ValueError(f"{name}: queries must be None, an int64 tensor [B, M] of caller rows of x or a {sup.kind.__name__} "
+                         f"like x, got {type(queries).__name__}")
+
+    asked = [s for s in range(B) if q_counts[s]]
+    small = min(asked, key=sup.lengths.__getitem__)
+    if k > sup.lengths[small]:
+        raise ValueError(f"{name}: k = {k} is larger than sample {small}, which has {sup.lengths[small]} rows")
+    if B > _FPS_MAX_B:
+        raise ValueError(f"{name}: B = {B} is above the kernel's limit of {_FPS_MAX_B}")
+
+    if not sup.data.is_cuda:
+        batch = x.C[:, 0].long()
+        points = x.C[:, 1:].long() if integer else sup.data[:, 1:]
+        qpoints = q_words[:, 1:].long() if integer else q_words.view(torch.float32)[:, 1:]
+        idx, d2 = _knn_torch(points, batch, sup.lengths, qpoints, q_counts, k, cap)
+    else:
+        be = get_backend()
+        if not hasattr(be, "knn"):
+            raise NotImplementedError(f"{name} on device tensors needs the HIP backend (ms3d_knn_i32)")
+        idx, d2 = be.knn(sup.data, sup.order, sup.offsets, sup.row_map, q_words, q_start.contiguous(), max(q_counts), k, cap)
+        if integer:
+            d2 = torch.where(idx < 0, -1, d2.long() & 0xffffffff)
+    if pos is not None:
+        idx, d2 = torch.empty_like(idx).index_copy_(0, pos, idx), torch.empty_like(d2).index_copy_(0, pos, d2)
+    if shape is not None:
+        idx, d2 = idx.view(*shape, k), d2.view(*shape, k)
+    return idx, d2
 
 
 def _dense_input(x, format, device):

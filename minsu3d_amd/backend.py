@@ -1475,6 +1475,53 @@ class _HipEngine:
                                            C.c_size_t(ws.numel()), _lib.stream_handle()), name)
         return out
 
+    # ---- k nearest neighbours over the batch grouping of a coordinate set or a field (csrc/knn.hip)
+    def knn_max_k(self):
+        return int(self.lib.ms3d_knn_max_k())
+
+    def knn_geometry(self):
+        """(queries a workgroup takes, rows of the support set in LDS at a time)"""
+        return int(self.lib.ms3d_knn_queries_per_group()), int(self.lib.ms3d_knn_rows_per_tile())
+
+    def knn(self, data, order, seg_start, row_map, queries, q_start, max_queries, k, cap):
+        """-> (int64 [NQ, k] caller rows, [NQ, k] distances: int32 WORDS (unsigned values) for coordinates, float32 for points):
+        the k nearest rows of every query's sample, nearest first, ties to the lower caller row; slots nothing qualified for
+        hold -1 and all-ones bits / +inf.  data [V, 4] on the device as held: int32 coordinates or float32 points, batch
+        column first; order int64 [V] / seg_start int32 [B + 1]: the rows of every sample (CoordinateManager.batch_rows);
+        row_map int32 [V] held row -> caller's row, or None; queries int32 [NQ, 4] words (segment, x, y, z: coordinates, or
+        the bits of float32 points) grouped by segment, q_start int32 [B + 1] their starts, max_queries the largest number
+        of queries a segment has; cap: None, or the largest distance that qualifies (an int >= 0 for coordinates, a float
+        >= 0 for points)."""
+        if not hasattr(self.lib, "ms3d_knn_i32"):
+            raise NotImplementedError("k nearest neighbours need a library with ms3d_knn_i32")
+        assert data.is_cuda and data.is_contiguous() and data.dim() == 2 and data.size(1) == 4
+        assert data.dtype in (torch.int32, torch.float32)
+        V, B, dev = data.size(0), seg_start.numel() - 1, data.device
+        assert order.dtype == torch.int64 and order.is_contiguous() and order.numel() == V and order.device == dev
+        assert seg_start.dtype == torch.int32 and seg_start.is_contiguous() and seg_start.dim() == 1 and seg_start.device == dev
+        if row_map is not None:
+            assert row_map.dtype == torch.int32 and row_map.is_contiguous() and row_map.numel() == V and row_map.device == dev
+        assert queries.dtype == torch.int32 and queries.is_contiguous() and queries.dim() == 2 and queries.size(1) == 4
+        assert queries.device == dev
+        assert q_start.dtype == torch.int32 and q_start.is_contiguous() and tuple(q_start.shape) == (B + 1,) and q_start.device == dev
+        NQ, k = queries.size(0), int(k)
+        assert 0 <= int(max_queries) <= NQ and 1 <= k <= self.knn_max_k()
+        integer = data.dtype == torch.int32
+        out = torch.empty((NQ, k), dtype=torch.int64, device=dev)
+        d2 = torch.empty((NQ, k), dtype=data.dtype, device=dev)
+        ws = self.ws.get("knn", self.lib.ms3d_knn_ws_bytes(C.c_long(V)), dev)
+        if integer:
+            assert cap is None or (isinstance(cap, int) and cap >= 0)
+            name, limit = "ms3d_knn_i32", C.c_longlong(-1 if cap is None else min(cap, 2 ** 32 - 1))
+        else:
+            assert cap is None or (isinstance(cap, float) and cap >= 0)
+            name, limit = "ms3d_knn_f32", C.c_float(-1.0 if cap is None else cap)
+        _lib.check(getattr(self.lib, name)(_lib.ptr(data), _lib.ptr(order), _lib.ptr(seg_start), _lib.ptr(row_map), int(V),
+                                           int(B), _lib.ptr(queries), _lib.ptr(q_start), int(NQ), int(max_queries), k, limit,
+                                           _lib.ptr(out), _lib.ptr(d2), _lib.ptr(ws), C.c_size_t(ws.numel()),
+                                           _lib.stream_handle()), name)
+        return out, d2
+
     # ---- instance normalisation over the batch grouping of a coordinate set (csrc/inorm.hip)
     def _inorm_check(self, x, order, seg_start, seg_of_row):
         assert x.dtype == torch.float32 and x.dim() == 2
