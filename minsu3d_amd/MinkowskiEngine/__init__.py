@@ -40,7 +40,9 @@ Normalisation per sample and the activations of the decoders, generators and reg
 
     MinkowskiInstanceNorm (eps 1e-8), MinkowskiStableInstanceNorm (eps 1e-6): `weight`, `bias` of shape (1, C), no running
     statistics; per batch index and channel, biased variance; segmented HIP reductions in a fixed order, shifted sums merged
-    by Chan's formula (csrc/inorm.hip); rows read where they are held  (+ CoordinateManager.batch_segments: engine extra)
+    by Chan's formula (csrc/inorm.hip); rows read where they are held  (+ CoordinateManager.batch_group, the grouping of the
+    rows by batch index as ONE record, backend.BatchGroup, that every per-sample op below reads; batch_rows, batch_segments,
+    batch_chunks, batch_lengths, batch_indices and caller_rows are views onto it: engine extras)
     MinkowskiELU, MinkowskiLeakyReLU, MinkowskiPReLU, MinkowskiSELU, MinkowskiCELU, MinkowskiGELU, MinkowskiSiLU,
     MinkowskiTanh, MinkowskiSoftplus, MinkowskiHardswish, MinkowskiHardtanh, MinkowskiReLU6, MinkowskiSoftmax,
     MinkowskiLogSoftmax: the torch operator as `self.module`, applied to the rows
@@ -177,7 +179,7 @@ Per-sample query attention -- the global block of a sparse transformer, the deco
     whose rows are all blocked is zero, contributes to no gradient and receives none (torch.nn.MultiheadAttention gives NaN
     there).  csrc/qattn.hip: the rows of a sample are batch_rows' segment, read by index where they are held (on a
     Morton-sorted manager the mask row is found through the held-to-caller index); a segment is cut into chunks of
-    ms3d_qattn_rows_per_chunk() positions (CoordinateManager.batch_chunks: one host read per coordinate set), one workgroup
+    ms3d_qattn_rows_per_chunk() positions (the record's `chunks`: one host read per coordinate set), one workgroup
     per chunk and tile of (query, head) items does an online-softmax sweep and leaves a partial, a second kernel merges the
     partials in chunk order and saves the log-sum-exp; the backward recomputes the probabilities -- a second sweep for the
     queries, a loop over the queries per voxel row for k and v.  Nothing of size V x Q is stored, no atomics, every sum in an
@@ -206,7 +208,7 @@ a two-way mask-transformer decoder (engine extras: MinkowskiEngine has no such l
     that no row may attend to gets a zero gradient.  csrc/vattn.hip: forward and the backward for x are one loop over the Q
     queries per (held row, head) item -- an online-softmax sweep that saves the log-sum-exp, then the probabilities recomputed
     -- without scratch; the backward for keys and values sweeps the chunks of query_attention (the same
-    CoordinateManager.batch_chunks list: no second host read), one partial per chunk, merged in chunk order.  The keys and
+    `chunks` of the same record: no second host read), one partial per chunk, merged in chunk order.  The keys and
     values of a sample are read through the cache.  Nothing of size V x Q is stored, no atomics, every sum in an order fixed
     by the shapes, the same bytes on every run.  D <= 128, Q <= 1024, C <= 1024, B <= 65535.  Frozen keys and values skip their
     pass; a frozen x skips its own when keys and values are frozen too (the kv pass reads a per-row residual the x pass leaves).
@@ -235,11 +237,11 @@ network (an engine extra: MinkowskiEngine has no such function, and nothing here
     (once every remaining distance is 0 the lowest row repeats).
     start: int64 [B] caller rows, one inside each sample (one host read, only when it is given).  ValueError: num_samples that
     is not an int >= 1 or is larger than the smallest sample (naming the sample and its size; the segment lengths are read on
-    the host once per coordinate set: CoordinateManager.batch_lengths, or once per field), a start of the wrong shape or dtype,
+    the host once per coordinate set or field: the record's `lengths`), a start of the wrong shape or dtype,
     for another B or with a row outside its sample, integer coordinates outside the packable range.  An empty tensor gives an
     empty [0, M] result.
     csrc/fps.hip: one launch, one workgroup per sample looping over its own segment of batch_rows, rows read where they are
-    held (cm.coords, batch_rows and caller_rows are passed as they are); no atomics and no waiting between workgroups; a
+    held (cm.coords and the record are passed as they are); no atomics and no waiting between workgroups; a
     thread's best row is one 64-bit key, (distance bits << 32) | ~caller row, reduced by shuffles and through LDS, two
     barriers a pick.  A sample of at most ms3d_fps_resident_rows() rows stays in registers for the whole loop; a larger one
     is gathered once into a workspace and swept every pick.  CPU tensors take the same rule as a torch expression, a loop
@@ -273,10 +275,10 @@ has no such function, and nothing here is pinned to it):
     as float32.  max_squared_distance: a Python int (SparseTensor) or float (TensorField, taken to float32) >= 0; a row
     qualifies when d2 <= cap, the boundary included; slots nothing qualifies for hold idx = -1 and d2 = -1 / +inf, after all
     the qualifying slots -- mask before indexing.  Without a cap the result never contains -1.
-    ValueError: k out of range or larger than the smallest sample of x that has queries (naming it; from the cached
-    batch_lengths), a cap of the wrong type or negative, a bad [B, M] tensor, coordinates outside the packable range, more
+    ValueError: k out of range or larger than the smallest sample of x that has queries (naming it; from the record's cached
+    `lengths`), a cap of the wrong type or negative, a bad [B, M] tensor, coordinates outside the packable range, more
     than 65535 samples.  Empty x or queries give empty [0, k] / [B, 0, k] results.
-    csrc/knn.hip: the support set is read where it is held (cm.coords, batch_rows and caller_rows as they are) and packed
+    csrc/knn.hip: the support set is read where it is held (cm.coords and the record as they are) and packed
     once in segment order, 16 B a row; then one workgroup takes ms3d_knn_queries_per_group() queries of one sample, a thread a
     query, and streams the sample through LDS in tiles of ms3d_knn_rows_per_tile() rows.  A thread's list of its k smallest 64-bit
     keys, (distance bits << 32) | caller row, lives in LDS; candidates are held back and inserted by all lanes of a wave

@@ -640,93 +640,92 @@ def kernel_attention_rows(q, k, v, rel_bias, nbr_fwd, nbr_inv, vin, vout, K, num
 class QueryAttentionFn(torch.autograd.Function):
     """out[b, q, h, :] = sum_i softmax_i(scale * <queries[b, q, h], k[i, h]>) * v[i, h, :] over the rows i of sample b that
     mask [V, Q] does not block (csrc/qattn.hip; float32, C = num_heads * D; a query with nothing to attend to is zero).  k / v:
-    rows as the manager holds them; mask: rows as the caller sees them, row_map the held -> caller index (None: the same);
-    group = (order, seg_start, chunk_seg, chunk_first, chunks) of CoordinateManager.batch_rows / batch_chunks, seg_of_row =
-    batch_segments.  Saves queries, k, v, out and the log-sum-exp lse [B, Q, H]; the backward recomputes the probabilities
-    from lse.  The q pass sweeps the chunks again (dq and delta [B, Q, H], the residual the kv pass subtracts; one partial per
+    rows as the manager holds them; mask: rows as the caller sees them; group: the backend.BatchGroup of the rows
+    (CoordinateManager.batch_group), which knows the held -> caller index, the chunk list and the segment of every row.
+    Saves queries, k, v, out and the log-sum-exp lse [B, Q, H]; the backward recomputes the probabilities from lse.  The q pass sweeps the chunks again (dq and delta [B, Q, H], the residual the kv pass subtracts; one partial per
     chunk, added in chunk order), the kv pass loops over the queries per row: no atomics, the same bytes on every run.
     Frozen queries skip the q pass unless the kv pass needs its delta (the pass then stores nothing else); frozen k and v
     skip the kv pass."""
 
     @staticmethod
-    def forward(ctx, queries, k, v, mask, row_map, group, seg_of_row, num_heads, scale):
+    def forward(ctx, queries, k, v, mask, group, num_heads, scale):
         be = get_backend()
         if not hasattr(be, "qattn_forward"):
             raise NotImplementedError("query attention needs the HIP backend (ms3d_qattn_forward)")
         queries, k, v = queries.contiguous(), k.contiguous(), v.contiguous()
-        out, lse = be.qattn_forward(queries, k, v, mask, row_map, group, num_heads, scale)
+        out, lse = be.qattn_forward(queries, k, v, mask, group, num_heads, scale)
         ctx.save_for_backward(queries, k, v, out, lse)
-        ctx.geom = (mask, row_map, group, seg_of_row, num_heads, scale)
+        ctx.geom = (mask, group, num_heads, scale)
         return out
 
     @staticmethod
     def backward(ctx, dout):
         queries, k, v, out, lse = ctx.saved_tensors
-        mask, row_map, group, seg_of_row, H, scale = ctx.geom
+        mask, group, H, scale = ctx.geom
         need_q, need_k, need_v = ctx.needs_input_grad[:3]
         be = get_backend()
         dout = dout.contiguous()
         dq = dk = dv = None
         if need_q or need_k or need_v:
-            dq, delta = be.qattn_backward_q(queries, k, v, mask, row_map, group, out, lse, dout, H, scale, need_dq=need_q)
+            dq, delta = be.qattn_backward_q(queries, k, v, mask, group, out, lse, dout, H, scale, need_dq=need_q)
             if need_k or need_v:
-                dk, dv = be.qattn_backward_kv(queries, k, v, mask, row_map, seg_of_row, out, lse, delta, dout, H, scale,
-                                              need_dk=need_k, need_dv=need_v)
-        return dq, dk, dv, None, None, None, None, None, None
+                dk, dv = be.qattn_backward_kv(queries, k, v, mask, group, out, lse, delta, dout, H, scale, need_dk=need_k,
+                                              need_dv=need_v)
+        return dq, dk, dv, None, None, None, None
 
 
-def query_attention_rows(queries, k, v, mask, row_map, group, seg_of_row, num_heads, scale):
+def query_attention_rows(queries, k, v, mask, group, num_heads, scale):
     """attention of queries [B, Q, C] over the rows k / v [V, C] of their own sample (rows as the manager holds them, the mask's
     as the caller sees them) -> out [B, Q, C]"""
-    return QueryAttentionFn.apply(queries, k, v, mask, row_map, group, seg_of_row, num_heads, scale)
+    return QueryAttentionFn.apply(queries, k, v, mask, group, num_heads, scale)
 
 
 class VoxelAttentionFn(torch.autograd.Function):
     """out[i, h, :] = sum_q softmax_q(scale * <x[i, h], keys[b, q, h]>) * values[b, q, h, :] over the queries q of the row's
-    sample b = seg_of_row[i] that mask [V, Q] does not block (csrc/vattn.hip; float32, C = num_heads * D; a row with nothing to
-    attend to is zero) -- QueryAttentionFn's reverse direction, on the same mask, row_map, group and seg_of_row.  Saves x, keys,
+    sample b = group.seg_of_row[i] that mask [V, Q] does not block (csrc/vattn.hip; float32, C = num_heads * D; a row with nothing to
+    attend to is zero) -- QueryAttentionFn's reverse direction, on the same mask and group.  Saves x, keys,
     values, out and the log-sum-exp lse [V, H]; the backward recomputes the probabilities from lse.  The x pass loops over the
     queries per row again (dx and delta [V, H], the residual the kv pass subtracts), the kv pass sweeps the chunks of every
     sample (one partial per chunk, added in chunk order): no atomics, the same bytes on every run.  Frozen keys and values
     skip the kv pass; a frozen x skips the x pass unless the kv pass needs its delta (the pass then stores nothing else)."""
 
     @staticmethod
-    def forward(ctx, x, keys, values, mask, row_map, group, seg_of_row, num_heads, scale):
+    def forward(ctx, x, keys, values, mask, group, num_heads, scale):
         be = get_backend()
         if not hasattr(be, "vattn_forward"):
             raise NotImplementedError("voxel attention needs the HIP backend (ms3d_vattn_forward)")
         x, keys, values = x.contiguous(), keys.contiguous(), values.contiguous()
-        out, lse = be.vattn_forward(x, keys, values, mask, row_map, seg_of_row, num_heads, scale)
+        out, lse = be.vattn_forward(x, keys, values, mask, group, num_heads, scale)
         ctx.save_for_backward(x, keys, values, out, lse)
-        ctx.geom = (mask, row_map, group, seg_of_row, num_heads, scale)
+        ctx.geom = (mask, group, num_heads, scale)
         return out
 
     @staticmethod
     def backward(ctx, dout):
         x, keys, values, out, lse = ctx.saved_tensors
-        mask, row_map, group, seg_of_row, H, scale = ctx.geom
+        mask, group, H, scale = ctx.geom
         need_x, need_k, need_v = ctx.needs_input_grad[:3]
         be = get_backend()
         dout = dout.contiguous()
         dx = dk = dv = None
         if need_x or need_k or need_v:
-            dx, delta = be.vattn_backward_x(x, keys, values, mask, row_map, seg_of_row, out, lse, dout, H, scale, need_dx=need_x)
+            dx, delta = be.vattn_backward_x(x, keys, values, mask, group, out, lse, dout, H, scale, need_dx=need_x)
             if need_k or need_v:
-                dk, dv = be.vattn_backward_kv(x, keys, values, mask, row_map, group, out, lse, delta, dout, H, scale,
-                                              need_dk=need_k, need_dv=need_v)
-        return dx, dk, dv, None, None, None, None, None, None
+                dk, dv = be.vattn_backward_kv(x, keys, values, mask, group, out, lse, delta, dout, H, scale, need_dk=need_k,
+                                              need_dv=need_v)
+        return dx, dk, dv, None, None, None, None
 
 
-def voxel_attention_rows(x, keys, values, mask, row_map, group, seg_of_row, num_heads, scale):
+def voxel_attention_rows(x, keys, values, mask, group, num_heads, scale):
     """attention of the rows x [V, C] (as the manager holds them, the mask's as the caller sees them) over the queries keys /
     values [B, Q, C] of their own sample -> out [V, C]"""
-    return VoxelAttentionFn.apply(x, keys, values, mask, row_map, group, seg_of_row, num_heads, scale)
+    return VoxelAttentionFn.apply(x, keys, values, mask, group, num_heads, scale)
 
 
 class InstanceNormFn(torch.autograd.Function):
     """y[r, c] = (x[r, c] - mean[s, c]) * invstd[s, c] * weight[c] + bias[c] with the statistics of the row's segment s (its
-    batch index) and the biased variance (csrc/inorm.hip).  group = (order, seg_start, seg_of_row): CoordinateManager.
-    batch_rows' grouping and batch_segments; the rows are read where they are held, nothing is permuted.  Every sum runs in one
+    batch index) and the biased variance (csrc/inorm.hip).  group: the backend.BatchGroup of the rows (CoordinateManager.
+    batch_group); the rows are read where they are held, nothing is permuted.  Every sum runs in one
     fixed order without atomics: the same bytes on every run; sums and statistics (mean, invstd: float64 [B, C]) are double, the
     rows float32.  A frozen affine skips dweight / dbias, an input without grad
     skips dx."""
@@ -736,9 +735,8 @@ class InstanceNormFn(torch.autograd.Function):
         be = get_backend()
         if not hasattr(be, "inorm_forward"):
             raise NotImplementedError("instance normalisation needs the HIP backend (ms3d_inorm_forward)")
-        order, seg_start, seg_of_row = group
         x = x.contiguous()
-        y, mean, invstd = be.inorm_forward(x, order, seg_start, seg_of_row, eps, weight, bias)
+        y, mean, invstd = be.inorm_forward(x, group, eps, weight, bias)
         ctx.save_for_backward(x, mean, invstd, weight)
         ctx.group = group
         ctx.shapes = (None if weight is None else tuple(weight.shape), None if bias is None else tuple(bias.shape))
@@ -747,13 +745,11 @@ class InstanceNormFn(torch.autograd.Function):
     @staticmethod
     def backward(ctx, dy):
         x, mean, invstd, weight = ctx.saved_tensors
-        order, seg_start, seg_of_row = ctx.group
         w_shape, b_shape = ctx.shapes
         need_x = ctx.needs_input_grad[0]
         need_w = w_shape is not None and ctx.needs_input_grad[1]
         need_b = b_shape is not None and ctx.needs_input_grad[2]
-        dx, dw, db = get_backend().inorm_backward(dy.contiguous(), x, order, seg_start, seg_of_row, mean, invstd, weight,
-                                                  need_x, need_w, need_b)
+        dx, dw, db = get_backend().inorm_backward(dy.contiguous(), x, ctx.group, mean, invstd, weight, need_x, need_w, need_b)
         return dx, dw.view(w_shape) if need_w else None, db.view(b_shape) if need_b else None, None, None
 
 

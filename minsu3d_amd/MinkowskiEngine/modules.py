@@ -566,8 +566,8 @@ def query_attention(queries, k, v, num_heads, attn_mask=None, scale=None, dropou
         raise ValueError(f"{name}: {C} channels do not divide into num_heads={num_heads}")
     if queries.device != k._F.device:
         raise ValueError(f"{name}: queries are on {queries.device}, k and v on {k._F.device}")
-    order, _, offsets, _ = cm.batch_rows(ts)
-    B, Q, D = offsets.numel() - 1, queries.size(1), C // num_heads
+    group = cm.batch_group(ts)
+    B, Q, D = group.B, queries.size(1), C // num_heads
     if queries.size(0) != B:
         raise ValueError(f"{name}: queries has B = {queries.size(0)} samples, the coordinate set holds {B} batch indices")
     if attn_mask is not None:
@@ -593,10 +593,8 @@ def query_attention(queries, k, v, num_heads, attn_mask=None, scale=None, dropou
                                   "(ms3d_qattn_forward)")
     if scale is None:
         scale = D ** -0.5
-    group = (order, offsets) + cm.batch_chunks(ts)
     mask = None if attn_mask is None else attn_mask.contiguous()
-    return Fn.query_attention_rows(queries, k._raw(), v._raw(), mask, cm.caller_rows(ts), group, cm.batch_segments(ts),
-                                   num_heads, float(scale))
+    return Fn.query_attention_rows(queries, k._raw(), v._raw(), mask, group, num_heads, float(scale))
 
 
 class MinkowskiQueryAttention(nn.Module):
@@ -685,8 +683,8 @@ def voxel_attention(x, keys, values, num_heads, attn_mask=None, scale=None, drop
         raise ValueError(f"{name}: {C} channels do not divide into num_heads={num_heads}")
     if keys.device != x._F.device or values.device != x._F.device:
         raise ValueError(f"{name}: keys and values are on {keys.device} and {values.device}, x on {x._F.device}")
-    order, _, offsets, _ = cm.batch_rows(ts)
-    B, Q, D = offsets.numel() - 1, keys.size(1), C // num_heads
+    group = cm.batch_group(ts)
+    B, Q, D = group.B, keys.size(1), C // num_heads
     if keys.size(0) != B:
         raise ValueError(f"{name}: keys has B = {keys.size(0)} samples, the coordinate set holds {B} batch indices")
     if attn_mask is not None:
@@ -712,10 +710,9 @@ def voxel_attention(x, keys, values, num_heads, attn_mask=None, scale=None, drop
                                   "(ms3d_vattn_forward)")
     if scale is None:
         scale = D ** -0.5
-    group = (order, offsets) + cm.batch_chunks(ts)
+    group.chunks                    # the kv pass sweeps them: their one host read is made here, not inside the backward
     mask = None if attn_mask is None else attn_mask.contiguous()
-    return x._like(Fn.voxel_attention_rows(x._raw(), keys, values, mask, cm.caller_rows(ts), group, cm.batch_segments(ts),
-                                           num_heads, float(scale)))
+    return x._like(Fn.voxel_attention_rows(x._raw(), keys, values, mask, group, num_heads, float(scale)))
 
 
 class MinkowskiVoxelAttention(nn.Module):
@@ -1041,14 +1038,15 @@ class _GlobalPoolBase(nn.Module):
         from ..common_ops.functions.common_ops import roipool
         from ..common_ops.functions.softgroup_ops import global_avg_pool
         cm, ts = x.coordinate_manager, x.tensor_stride
-        order, inv, offsets, counts = cm.batch_rows(ts)
-        rows = Fn.PermuteRowsFn.apply(x._raw(), order, inv)        # a permutation: the backward is the gather dy[inv]
+        group = cm.batch_group(ts)
+        order, offsets = group.order, group.seg_start
+        rows = Fn.PermuteRowsFn.apply(x._raw(), order, group.inverse)        # a permutation: the backward is the gather dy[inv]
         if self.MODE == 0:
             y = roipool(rows, offsets)
         else:
             y = global_avg_pool(rows, offsets)
             if self.MODE == 2:
-                y = y * counts
+                y = y * group.counts
         b = cm.coords[ts][order[offsets[:-1].long()], 0]
         coords = torch.zeros((b.numel(), 4), dtype=torch.int32, device=b.device)
         coords[:, 0] = b
@@ -1201,8 +1199,7 @@ class MinkowskiInstanceNorm(nn.Module):
         cm, ts = x.coordinate_manager, x.tensor_stride
         if not hasattr(get_backend(), "inorm_forward"):
             raise NotImplementedError(f"{type(self).__name__} needs the HIP backend (ms3d_inorm_forward)")
-        order, _, offsets, _ = cm.batch_rows(ts)
-        y = Fn.instance_norm(x._raw(), self.weight, self.bias, (order, offsets, cm.batch_segments(ts)), self.eps)
+        y = Fn.instance_norm(x._raw(), self.weight, self.bias, cm.batch_group(ts), self.eps)
         return x._like(y)
 
     def extra_repr(self):

@@ -15,7 +15,7 @@ import os
 import numpy as np
 import torch
 
-from ..backend import get_backend
+from ..backend import BatchGroup, get_backend
 from . import functional as Fn
 
 
@@ -307,7 +307,7 @@ class CoordinateManager:
         self._ident = {}
         self._kmaps = {}    # (ts, kernel_size, stride, dilation) -> kernel_map() tuple of the general geometries
         self._kinv = {}     # the same key -> inverse table (pooling backward over a submanifold map)
-        self._batch_rows = {}
+        self._batch_groups = {}     # ts -> BatchGroup: the rows grouped by batch index, what every per-sample op reads
 
     @classmethod
     def rooted(cls, coordinates, tensor_stride):
@@ -319,7 +319,7 @@ class CoordinateManager:
         cm.perm = cm.inv = None
         cm.root = int(tensor_stride)
         cm.coords = {cm.root: coordinates.contiguous()}
-        cm._k3, cm._k2, cm._ident, cm._kmaps, cm._kinv, cm._batch_rows = {}, {}, {}, {}, {}, {}
+        cm._k3, cm._k2, cm._ident, cm._kmaps, cm._kinv, cm._batch_groups = {}, {}, {}, {}, {}, {}
         return cm
 
     def generate(self, ts, kernel_size, stride=1, dilation=1, region=None):
@@ -480,13 +480,12 @@ class CoordinateManager:
                 gcm._batch_index[gts] = gb
             if isinstance(gb, ValueError):
                 raise gb
-            order, _, offsets, _ = self.batch_rows(ts)
+            group = self.batch_group(ts)
+            order, offsets, present = group.order, group.seg_start, group.indices   # batch index of every segment, ascending
             dev = self.coords[ts].device
-            first = order[offsets[:-1].long()] if order.numel() else order[:0]
-            present = self.coords[ts][first, 0].cpu().numpy()          # batch index of every segment, ascending
             seg = {int(b): s for s, b in enumerate(present)}
             seg_of_g = torch.tensor([seg.get(int(b), -1) for b in gb], dtype=torch.int32, device=dev)
-            lut = torch.full((int(max([-1] + gb.tolist() + present.tolist())) + 2,), -1, dtype=torch.int32, device=dev)
+            lut = torch.full((int(max([-1] + gb.tolist() + list(present))) + 2,), -1, dtype=torch.int32, device=dev)
             lut[torch.as_tensor(gb, device=dev).long()] = torch.arange(len(gb), dtype=torch.int32, device=dev)
             grow = lut[self.coords[ts][:, 0].long()].contiguous()
             hit = cache[key] = (grow, (order.contiguous(), offsets.contiguous(), seg_of_g), gcm)
@@ -696,7 +695,7 @@ class CoordinateManager:
             raise ValueError(f"origin_map: the key's manager holds no coordinate set of tensor stride {ts}")
         cache = cm.__dict__.setdefault("_origin_maps", {})
         if ts not in cache:
-            seg = cm.batch_segments(ts).long()
+            seg = cm.batch_group(ts).seg_of_row.long()
             if ts == 1 and cm.inv is not None:
                 seg = seg[cm.inv]
             cache[ts] = {0: torch.stack([torch.arange(seg.numel(), dtype=torch.int64, device=seg.device), seg])}
@@ -783,83 +782,50 @@ class CoordinateManager:
             self._kinv[key] = get_backend().kmap_invert(nbr_fwd.contiguous(), K, vout, vin)
         return self._kinv[key]
 
+    def batch_group(self, ts):
+        """the backend.BatchGroup of the coordinate set of tensor stride ts: its rows, as they are HELD, grouped by batch index
+        -- order, seg_start, seg_of_row, the held <-> caller row maps of a Morton-sorted manager, and on first use the inverse
+        order, the counts, and (one host read each) the segment lengths, the batch indices present and the attention chunk
+        list.  Rows are batch-contiguous already only for some inputs, so nothing relies on it.  One stable sort, once per
+        tensor stride; every per-sample op reads this record, the accessors below are views onto it.  An engine extra."""
+        g = self._batch_groups.get(ts)
+        if g is None:
+            held = ts == 1 and self.perm is not None
+            g = self._batch_groups[ts] = BatchGroup(self.coords[ts][:, 0], self.perm.to(torch.int32).contiguous() if held else None,
+                                                    self.inv if held else None)
+        return g
+
     def batch_rows(self, ts):
-        """rows of the coordinate set grouped by batch index -> (order int64 [V]: rows sorted by batch, stable; its inverse
-        permutation; offsets int32 [B + 1] into `order`, one segment per batch index PRESENT, ascending; counts float32
-        [B, 1]).  Rows are batch-contiguous already only for some inputs, so nothing relies on it; one host sync, once."""
-        br = self._batch_rows.get(ts)
-        if br is None:
-            b = self.coords[ts][:, 0].long()
-            sb, order = torch.sort(b, stable=True)
-            inv = torch.empty_like(order)
-            inv[order] = torch.arange(order.numel(), device=order.device)
-            _, counts = torch.unique_consecutive(sb, return_counts=True)
-            offsets = torch.zeros(counts.numel() + 1, dtype=torch.int32, device=b.device)
-            offsets[1:] = torch.cumsum(counts, 0)
-            br = self._batch_rows[ts] = (order, inv, offsets, counts.to(torch.float32).view(-1, 1))
-        return br
+        """-> (order int64 [V]: rows sorted by batch, stable; its inverse permutation; offsets int32 [B + 1] into `order`, one
+        segment per batch index PRESENT, ascending; counts float32 [B, 1]) of batch_group(ts)"""
+        return self.batch_group(ts).rows
 
     def batch_segments(self, ts):
         """int32 [V]: for every row of the coordinate set, as it is HELD, the index of its segment in batch_rows(ts) (the rank
-        of its batch index among the batch indices present) -- what a per-sample layer needs to find a row's statistics
-        without a permuted copy of the rows.  Derived from batch_rows, built once per tensor stride.  An engine extra."""
-        cache = self.__dict__.setdefault("_batch_segments", {})
-        seg = cache.get(ts)
-        if seg is None:
-            order, _, offsets, _ = self.batch_rows(ts)
-            lengths = (offsets[1:] - offsets[:-1]).long()
-            of_position = torch.repeat_interleave(torch.arange(lengths.numel(), dtype=torch.int32, device=order.device),
-                                                  lengths, output_size=order.numel())
-            seg = torch.empty(order.numel(), dtype=torch.int32, device=order.device)
-            seg[order] = of_position
-            cache[ts] = seg
-        return seg
+        of its batch index among the batch indices present): seg_of_row of batch_group(ts)"""
+        return self.batch_group(ts).seg_of_row
 
     def batch_chunks(self, ts):
         """the chunk list of query_attention over batch_rows(ts) -> (chunk_seg int32 [chunks]: the sample of every chunk,
         chunk_first int32 [B + 1]: the first chunk of every sample, chunks): every segment cut into runs of
-        ms3d_qattn_rows_per_chunk() positions of `order`, sorted by sample, then by run -- a pure function of the segment
-        lengths (backend.qattn_chunk_list).  Its size needs the segment lengths on the host: one host read, once per tensor
-        stride, kept beside batch_rows.  An engine extra."""
-        cache = self.__dict__.setdefault("_batch_chunks", {})
-        hit = cache.get(ts)
-        if hit is None:
-            offsets = self.batch_rows(ts)[2]
-            chunk_seg, chunk_first = get_backend().qattn_chunk_list(offsets.cpu())
-            hit = cache[ts] = (chunk_seg.to(offsets.device), chunk_first.to(offsets.device), chunk_seg.numel())
-        return hit
+        ms3d_qattn_rows_per_chunk() positions of `order`, sorted by sample, then by run (backend.qattn_chunk_list): chunks of
+        batch_group(ts), one host read"""
+        return self.batch_group(ts).chunks
 
     def batch_lengths(self, ts):
-        """the number of rows of every segment of batch_rows(ts) as a tuple of Python ints: one host read, once per tensor
-        stride, kept beside batch_rows and batch_chunks (farthest_point_sampling refuses more picks than a sample has rows).
-        An engine extra."""
-        cache = self.__dict__.setdefault("_batch_lengths", {})
-        hit = cache.get(ts)
-        if hit is None:
-            off = self.batch_rows(ts)[2].tolist()
-            hit = cache[ts] = tuple(off[i + 1] - off[i] for i in range(len(off) - 1))
-        return hit
+        """the number of rows of every segment of batch_rows(ts) as a tuple of Python ints: lengths of batch_group(ts), one
+        host read"""
+        return self.batch_group(ts).lengths
 
     def batch_indices(self, ts):
         """the batch indices present, ascending, as a tuple of Python ints -- the batch index of every segment of
-        batch_rows(ts): one host read, once per tensor stride, kept beside batch_lengths (knn_query pairs the samples of two
-        sets by batch index VALUE).  An engine extra."""
-        cache = self.__dict__.setdefault("_batch_indices", {})
-        hit = cache.get(ts)
-        if hit is None:
-            order, _, offsets, _ = self.batch_rows(ts)
-            first = order[offsets[:-1].long()] if order.numel() else order[:0]
-            hit = cache[ts] = tuple(int(v) for v in self.coords[ts][first, 0].tolist())
-        return hit
+        batch_rows(ts): indices of batch_group(ts), one host read"""
+        return self.batch_group(ts).indices
 
     def caller_rows(self, ts):
         """int32 [V]: for every row of the set as it is HELD, the row of .coordinates / .features the caller sees it at; None
-        where the two orders are the same (no Morton permutation, or a coarser set).  Built once."""
-        if ts != 1 or self.perm is None:
-            return None
-        if "_caller_rows" not in self.__dict__:
-            self.__dict__["_caller_rows"] = self.perm.to(torch.int32).contiguous()
-        return self.__dict__["_caller_rows"]
+        where the two orders are the same (no Morton permutation, or a coarser set): row_map of batch_group(ts)"""
+        return self.batch_group(ts).row_map
 
     def extent(self, ts):
         """(per-axis minimum [3], per-axis maximum [3], largest batch index) of the coordinate set as Python ints, None for an
@@ -908,10 +874,8 @@ class CoordinateManager:
                 present, counts = torch.unique_consecutive(sb, return_counts=True)
                 present, counts = present.tolist(), counts.tolist()
             else:
-                order, _, offsets, _ = self.batch_rows(ts)
-                off = offsets.tolist()
-                counts = [off[i + 1] - off[i] for i in range(len(off) - 1)]
-                present = b[order[offsets[:-1].long()]].tolist() if counts else []
+                group = self.batch_group(ts)
+                order, counts, present = group.order, list(group.lengths), list(group.indices)
             parts = dict(zip(present, torch.split(order, counts))) if counts else {}
             perms = cache[ts] = [parts.get(i, order[:0]) for i in range((present[-1] + 1) if present else 0)]
         return perms
@@ -1434,32 +1398,17 @@ class TensorField:
         return q
 
     def _batch_group(self):
-        """the points grouped by batch index, as CoordinateManager.batch_rows groups rows -> (order int64 [N]: the points
-        sorted by batch index, stable; offsets int32 [B + 1] into `order`, one segment per batch index PRESENT, ascending; the
-        segment lengths as a tuple of Python ints; seg int32 [N]: the segment of every point).  One stable sort of the batch
-        column and one host read, once per field."""
+        """the backend.BatchGroup of the points: grouped by batch index as CoordinateManager.batch_group groups rows (a field's
+        points are held in the caller's order: no row_map).  One stable sort of the batch column, once per field; fields made
+        by _like() share the record."""
         g = self._shared.get("batch_group")
         if g is None:
-            b = self._C[:, 0].long()
-            sb, order = torch.sort(b, stable=True)
-            _, counts = torch.unique_consecutive(sb, return_counts=True)
-            offsets = torch.zeros(counts.numel() + 1, dtype=torch.int32, device=b.device)
-            offsets[1:] = torch.cumsum(counts, 0)
-            seg = torch.empty(order.numel(), dtype=torch.int32, device=b.device)
-            seg[order] = torch.repeat_interleave(torch.arange(counts.numel(), dtype=torch.int32, device=b.device), counts,
-                                                 output_size=order.numel())
-            g = self._shared["batch_group"] = (order.contiguous(), offsets, tuple(counts.tolist()), seg)
+            g = self._shared["batch_group"] = BatchGroup(self._C[:, 0])
         return g
 
     def _batch_indices(self):
-        """the batch indices present, ascending, as a tuple of Python ints -- the batch index of every segment of _batch_group;
-        one host read, once per field"""
-        hit = self._shared.get("batch_indices")
-        if hit is None:
-            order, offsets, _, _ = self._batch_group()
-            first = order[offsets[:-1].long()] if order.numel() else order[:0]
-            hit = self._shared["batch_indices"] = tuple(int(v) for v in self._C[first, 0].tolist())
-        return hit
+        """the batch indices present, ascending, as a tuple of Python ints: indices of _batch_group(), one host read"""
+        return self._batch_group().indices
 
     def _quantized(self, ts):
         """int32 [N, 4]: the voxel of every point at tensor stride ts, floor(p / ts) * ts per axis (floor, not truncation:
@@ -1581,6 +1530,40 @@ def _fps_torch(points, batch, lengths, M, start):
     return out
 
 
+class _SupportSet:
+    """the set a per-sample point op searches -- a SparseTensor or a TensorField as csrc/fps.hip and csrc/knn.hip take it: its
+    kind, data [V, 4] as HELD (int32 coordinates / float32 points) and group, the BatchGroup of its rows.  Integer coordinates
+    outside the packable range are refused here."""
+
+    def __init__(self, x, name, what):
+        self.x = x
+        if isinstance(x, SparseTensor):
+            cm, ts = x.coordinate_manager, x.tensor_stride
+            self.kind, self.data, self.group = SparseTensor, cm.coords[ts], cm.batch_group(ts)
+            if self.data.size(0):
+                lo, hi, _ = cm.extent(ts)
+                if min(lo) < _FPS_LO or max(hi) >= _FPS_HI:
+                    raise ValueError(f"{name}: coordinates from {min(lo)} to {max(hi)} leave the packable range [{_FPS_LO}, "
+                                     f"{_FPS_HI}), outside which squared distances do not fit 32 bits")
+        elif isinstance(x, TensorField):
+            self.kind, self.data, self.group = TensorField, x._points32(), x._batch_group()
+        else:
+            raise TypeError(f"{name}: {what} must be a SparseTensor or a TensorField, got {type(x).__name__}")
+        self.V = self.data.size(0)
+
+    def words(self, held, segment):
+        """the rows `held` as packed queries: int32 words [n, 4] = (segment, x, y, z)"""
+        w = self.data[held]
+        w = w if w.dtype == torch.int32 else w.view(torch.int32)
+        w[:, 0] = segment
+        return w
+
+    def caller_of_order(self):
+        """the caller row of every position of `order`"""
+        g = self.group
+        return g.order if g.row_map is None else g.row_map[g.order].long()
+
+
 def farthest_point_sampling(x, num_samples, start=None):
     """Farthest point sampling per sample (an engine extra: MinkowskiEngine has no such function) -- the seeds of a mask
     transformer's queries, the grouping stage of a point network.  x: a SparseTensor (any tensor stride its manager holds, any
@@ -1617,32 +1600,13 @@ def farthest_point_sampling(x, num_samples, start=None):
     if isinstance(num_samples, bool) or not isinstance(num_samples, int) or num_samples < 1:
         raise ValueError(f"{name}: num_samples must be a Python int >= 1, got {num_samples!r}")
     M = num_samples
-    if isinstance(x, SparseTensor):
-        cm, ts = x.coordinate_manager, x.tensor_stride
-        data = cm.coords[ts]
-        V = data.size(0)
-        if V:
-            order, _, offsets, _ = cm.batch_rows(ts)
-            lengths, row_map, seg = cm.batch_lengths(ts), cm.caller_rows(ts), cm.batch_segments(ts)
-            held_of = cm.inv if row_map is not None else None
-            lo, hi, _ = cm.extent(ts)
-            if min(lo) < _FPS_LO or max(hi) >= _FPS_HI:
-                raise ValueError(f"{name}: coordinates from {min(lo)} to {max(hi)} leave the packable range [{_FPS_LO}, {_FPS_HI}), "
-                                 "outside which squared distances do not fit 32 bits")
-    elif isinstance(x, TensorField):
-        data = x._points32()
-        V = data.size(0)
-        if V:
-            order, offsets, lengths, seg = x._batch_group()
-            row_map = held_of = None
-    else:
-        raise TypeError(f"{name}: x must be a SparseTensor or a TensorField, got {type(x).__name__}")
-    dev = data.device
+    sup = _SupportSet(x, name, "x")
+    data, group, V, dev = sup.data, sup.group, sup.V, sup.data.device
     if V == 0:
         if start is not None and (not torch.is_tensor(start) or start.dtype != torch.int64 or tuple(start.shape) != (0,)):
             raise ValueError(f"{name}: start must be an int64 tensor [B] with B = 0, the samples of x")
         return torch.empty((0, M), dtype=torch.int64, device=dev)
-    B = len(lengths)
+    B, lengths = group.B, group.lengths
     small = min(range(B), key=lengths.__getitem__)
     if M > lengths[small]:
         raise ValueError(f"{name}: num_samples = {M} is larger than sample {small}, which has {lengths[small]} rows")
@@ -1656,11 +1620,7 @@ def farthest_point_sampling(x, num_samples, start=None):
         if tuple(start.shape) != (B,):
             raise ValueError(f"{name}: start must have shape [B] = [{B}], one row per sample of x, got {list(start.shape)}")
         start = start.to(dev)
-        inside = (start >= 0) & (start < V)
-        start_held = start.clamp(0, V - 1)
-        if held_of is not None:
-            start_held = held_of[start_held]
-        inside &= seg[start_held] == torch.arange(B, dtype=torch.int32, device=dev)
+        start_held, inside = group.held_rows(start)
         if not bool(inside.all()):
             bad = int((~inside).nonzero()[0])
             raise ValueError(f"{name}: start[{bad}] = {int(start[bad])} is not a row of sample {bad}")
@@ -1671,57 +1631,11 @@ def farthest_point_sampling(x, num_samples, start=None):
     be = get_backend()
     if not hasattr(be, "fps"):
         raise NotImplementedError(f"{name} on device tensors needs the HIP backend (ms3d_fps_i32)")
-    return be.fps(data, order, offsets, row_map, None if start_held is None else start_held.contiguous(), M)
+    return be.fps(data, group, None if start_held is None else start_held.contiguous(), M)
 
 
 _KNN_MAX_K = 64                          # ms3d_knn_max_k() of csrc/knn.hip
 _KNN_CHUNK = 1 << 22                     # the CPU path holds at most this many (query, row) pairs at a time
-
-
-class _KnnSet:
-    """one side of knn_query -- a SparseTensor or a TensorField as csrc/knn.hip takes it: data [V, 4] as HELD (int32
-    coordinates / float32 points), order and offsets of the batch grouping, the segment lengths (host), row_map held row ->
-    caller row (or None), seg: the segment of every held row, held_of: caller row -> held row (or None)"""
-
-    def __init__(self, x, name, what):
-        self.x, self.order, self.offsets, self.lengths, self.row_map, self.seg, self.held_of = x, None, None, (), None, None, None
-        if isinstance(x, SparseTensor):
-            cm, ts = x.coordinate_manager, x.tensor_stride
-            self.kind, self.data = SparseTensor, cm.coords[ts]
-            if self.data.size(0):
-                self.order, _, self.offsets, _ = cm.batch_rows(ts)
-                self.lengths, self.row_map, self.seg = cm.batch_lengths(ts), cm.caller_rows(ts), cm.batch_segments(ts)
-                self.held_of = cm.inv if self.row_map is not None else None
-                lo, hi, _ = cm.extent(ts)
-                if min(lo) < _FPS_LO or max(hi) >= _FPS_HI:
-                    raise ValueError(f"{name}: coordinates from {min(lo)} to {max(hi)} leave the packable range [{_FPS_LO}, "
-                                     f"{_FPS_HI}), outside which squared distances do not fit 32 bits")
-        elif isinstance(x, TensorField):
-            self.kind, self.data = TensorField, x._points32()
-            if self.data.size(0):
-                self.order, self.offsets, self.lengths, self.seg = x._batch_group()
-        else:
-            raise TypeError(f"{name}: {what} must be a SparseTensor or a TensorField, got {type(x).__name__}")
-        self.V = self.data.size(0)
-
-    def present(self):
-        """the batch index of every segment (host, cached with the set)"""
-        if not self.V:
-            return ()
-        if self.kind is SparseTensor:
-            return self.x.coordinate_manager.batch_indices(self.x.tensor_stride)
-        return self.x._batch_indices()
-
-    def words(self, held, segment):
-        """the rows `held` as packed queries: int32 words [n, 4] = (segment, x, y, z)"""
-        w = self.data[held]
-        w = w if w.dtype == torch.int32 else w.view(torch.int32)
-        w[:, 0] = segment
-        return w
-
-    def caller_of_order(self):
-        """the caller row of every position of `order`"""
-        return self.order if self.row_map is None else self.row_map[self.order].long()
 
 
 def _knn_torch(points, batch, lengths, qpoints, q_counts, k, cap):
@@ -1809,7 +1723,8 @@ def knn_query(x, k, queries=None, max_squared_distance=None):
     name = "knn_query"
     if isinstance(k, bool) or not isinstance(k, int) or not 1 <= k <= _KNN_MAX_K:
         raise ValueError(f"{name}: k must be a Python int with 1 <= k <= {_KNN_MAX_K}, got {k!r}")
-    sup = _KnnSet(x, name, "x")
+    sup = _SupportSet(x, name, "x")
+    group = sup.group
     integer = sup.kind is SparseTensor
     cap = max_squared_distance
     if cap is not None:
@@ -1821,14 +1736,14 @@ def knn_query(x, k, queries=None, max_squared_distance=None):
         if not cap >= 0:
             raise ValueError(f"{name}: max_squared_distance must be >= 0, got {cap!r}")
         cap = min(cap, 2 ** 32 - 1) if integer else float(np.float32(cap))       # no distance is above 2^32 - 1
-    dev, B = sup.data.device, len(sup.lengths)
+    dev, B = sup.data.device, group.B
     d2_dtype = torch.int64 if integer else torch.float32
     shape, pos = None, None              # the result's leading shape; the caller's position of every packed query, or None
 
     if queries is None:
         if sup.V == 0:
             return torch.empty((0, k), dtype=torch.int64, device=dev), torch.empty((0, k), dtype=d2_dtype, device=dev)
-        q_words, q_start, q_counts = sup.words(sup.order, sup.seg[sup.order]), sup.offsets, sup.lengths
+        q_words, q_start, q_counts = sup.words(group.order, group.seg_of_row[group.order]), group.seg_start, group.lengths
         pos = sup.caller_of_order()
     elif torch.is_tensor(queries):
         if queries.dtype != torch.int64:
@@ -1840,39 +1755,34 @@ def knn_query(x, k, queries=None, max_squared_distance=None):
         if B * M == 0:
             return torch.empty((B, M, k), dtype=torch.int64, device=dev), torch.empty((B, M, k), dtype=d2_dtype, device=dev)
         queries = queries.to(dev)
-        inside = (queries >= 0) & (queries < sup.V)
-        held = queries.clamp(0, sup.V - 1)
-        if sup.held_of is not None:
-            held = sup.held_of[held]
-        segment = torch.arange(B, dtype=torch.int32, device=dev)
-        inside &= sup.seg[held] == segment[:, None]
+        held, inside = group.held_rows(queries)
         if not bool(inside.all()):                               # the one host read of this form
             b, j = (int(v) for v in (~inside).nonzero()[0])
             raise ValueError(f"{name}: queries[{b}, {j}] = {int(queries[b, j])} is not a row of sample {b}")
-        q_words = sup.words(held.reshape(-1), segment.repeat_interleave(M))
+        q_words = sup.words(held.reshape(-1), torch.arange(B, dtype=torch.int32, device=dev).repeat_interleave(M))
         q_start, q_counts = torch.arange(B + 1, dtype=torch.int32, device=dev) * M, (M,) * B
     elif isinstance(queries, (SparseTensor, TensorField)):
         if not isinstance(queries, sup.kind):
             raise TypeError(f"{name}: mixed kinds -- x is a {sup.kind.__name__} and queries a {type(queries).__name__}; voxels "
                             "query voxels and points query points")
-        qs = _KnnSet(queries, name, "queries")
+        qs = _SupportSet(queries, name, "queries")
         if qs.data.device != dev:
             raise ValueError(f"{name}: x is on {dev} and queries on {qs.data.device}")
         if qs.V == 0:
             return torch.empty((0, k), dtype=torch.int64, device=dev), torch.empty((0, k), dtype=d2_dtype, device=dev)
-        segment_of = {bi: s for s, bi in enumerate(sup.present())}
-        absent = [bi for bi in qs.present() if bi not in segment_of]
+        segment_of = {bi: s for s, bi in enumerate(group.indices)}
+        absent = [bi for bi in qs.group.indices if bi not in segment_of]
         if absent:
             raise ValueError(f"{name}: batch index {absent[0]} is present in queries and absent from x")
-        target = [segment_of[bi] for bi in qs.present()]         # ascending, as both lists are
+        target = [segment_of[bi] for bi in qs.group.indices]         # ascending, as both lists are
         counts = [0] * B
-        for s, n in zip(target, qs.lengths):
+        for s, n in zip(target, qs.group.lengths):
             counts[s] = n
         starts = [0]
         for n in counts:
             starts.append(starts[-1] + n)
         lut = torch.tensor(target, dtype=torch.int32, device=dev)
-        q_words = qs.words(qs.order, lut[qs.seg[qs.order].long()])
+        q_words = qs.words(qs.group.order, lut[qs.group.seg_of_row[qs.group.order].long()])
         q_start, q_counts = torch.tensor(starts, dtype=torch.int32, device=dev), tuple(counts)
         pos = qs.caller_of_order()
     else:
@@ -1880,9 +1790,9 @@ def knn_query(x, k, queries=None, max_squared_distance=None):
                          f"like x, got {type(queries).__name__}")
 
     asked = [s for s in range(B) if q_counts[s]]
-    small = min(asked, key=sup.lengths.__getitem__)
-    if k > sup.lengths[small]:
-        raise ValueError(f"{name}: k = {k} is larger than sample {small}, which has {sup.lengths[small]} rows")
+    small = min(asked, key=group.lengths.__getitem__)
+    if k > group.lengths[small]:
+        raise ValueError(f"{name}: k = {k} is larger than sample {small}, which has {group.lengths[small]} rows")
     if B > _FPS_MAX_B:
         raise ValueError(f"{name}: B = {B} is above the kernel's limit of {_FPS_MAX_B}")
 
@@ -1890,12 +1800,12 @@ def knn_query(x, k, queries=None, max_squared_distance=None):
         batch = x.C[:, 0].long()
         points = x.C[:, 1:].long() if integer else sup.data[:, 1:]
         qpoints = q_words[:, 1:].long() if integer else q_words.view(torch.float32)[:, 1:]
-        idx, d2 = _knn_torch(points, batch, sup.lengths, qpoints, q_counts, k, cap)
+        idx, d2 = _knn_torch(points, batch, group.lengths, qpoints, q_counts, k, cap)
     else:
         be = get_backend()
         if not hasattr(be, "knn"):
             raise NotImplementedError(f"{name} on device tensors needs the HIP backend (ms3d_knn_i32)")
-        idx, d2 = be.knn(sup.data, sup.order, sup.offsets, sup.row_map, q_words, q_start.contiguous(), max(q_counts), k, cap)
+        idx, d2 = be.knn(sup.data, group, q_words, q_start.contiguous(), max(q_counts), k, cap)
         if integer:
             d2 = torch.where(idx < 0, -1, d2.long() & 0xffffffff)
     if pos is not None:

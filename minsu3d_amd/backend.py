@@ -7,6 +7,7 @@ the same method surface via `set_backend` (e.g. the oracle-backed one in oracle/
 nothing in this package imports the oracle.
 """
 import ctypes as C
+import functools
 import os
 import weakref
 
@@ -167,6 +168,101 @@ class SortedIndex:
                 cur.wait_event(self.event)
                 self.keys.record_stream(cur); self.order.record_stream(cur)
         return self.keys, self.order
+
+
+class BatchGroup:
+    """The rows of one coordinate set or field grouped by batch index -- what every per-sample op reads.  Built from the batch
+    column of the rows as they are HELD by one stable sort:
+      order       int64 [V]      the rows sorted by batch index
+      seg_start   int32 [B + 1]  offsets into `order`, one segment per batch index PRESENT, ascending
+      seg_of_row  int32 [V]      the segment of every held row (the rank of its batch index)
+      row_map     int32 [V]      held row -> the row the caller sees, or None where the two orders are the same
+      held_of     int64 [V]      caller row -> held row, or None with row_map
+    all validated here, once: the backend calls check a record against their rows (V, B, device) and nothing else.  The other
+    fields are made on first use and kept: inverse (of order), counts (float32 [B, 1]) and rows (the tuple of CoordinateManager.
+    batch_rows) stay on the device; lengths, indices and chunks are ONE host read each, so an op that needs none of them
+    (instance norm, global pooling, broadcast, origin_map) causes none."""
+
+    def __init__(self, batch, row_map=None, held_of=None):
+        sb, order = torch.sort(batch.long(), stable=True)
+        _, counts = torch.unique_consecutive(sb, return_counts=True)
+        seg_start = torch.zeros(counts.numel() + 1, dtype=torch.int32, device=batch.device)
+        seg_start[1:] = torch.cumsum(counts, 0)
+        seg_of_row = torch.empty(order.numel(), dtype=torch.int32, device=batch.device)
+        seg_of_row[order] = torch.repeat_interleave(torch.arange(counts.numel(), dtype=torch.int32, device=batch.device), counts,
+                                                    output_size=order.numel())
+        self._set(order, seg_start, seg_of_row, row_map, held_of, batch)
+
+    @classmethod
+    def from_tensors(cls, order, seg_start, seg_of_row, row_map=None):
+        """a record over a grouping made elsewhere (a test's hand-made one); it has no batch column, so no `indices`"""
+        self = cls.__new__(cls)
+        self._set(order, seg_start, seg_of_row, row_map, None, None)
+        return self
+
+    def _set(self, order, seg_start, seg_of_row, row_map, held_of, batch):
+        V, dev = order.numel(), order.device
+        assert order.dtype == torch.int64 and order.dim() == 1 and order.is_contiguous()
+        assert seg_start.dtype == torch.int32 and seg_start.dim() == 1 and seg_start.is_contiguous() and seg_start.numel() >= 1
+        assert seg_of_row.dtype == torch.int32 and seg_of_row.is_contiguous() and tuple(seg_of_row.shape) == (V,)
+        assert seg_start.device == dev and seg_of_row.device == dev
+        if row_map is not None:
+            assert row_map.dtype == torch.int32 and row_map.is_contiguous() and tuple(row_map.shape) == (V,)
+            assert row_map.device == dev
+        if held_of is not None:
+            assert row_map is not None and held_of.dtype == torch.int64 and tuple(held_of.shape) == (V,) and held_of.device == dev
+        self.order, self.seg_start, self.seg_of_row, self.row_map, self.held_of = order, seg_start, seg_of_row, row_map, held_of
+        self.V, self.B, self.device, self._batch = V, seg_start.numel() - 1, dev, batch
+
+    def check(self, V, device, B=None):
+        """refuses rows (and per-sample tensors of B samples) this record was not made for, on the host: a stale record never
+        reaches a kernel"""
+        assert self.V == V and self.device == device and B in (None, self.B), \
+            f"a BatchGroup of {self.V} rows in {self.B} samples on {self.device} for {V} rows in {B} samples on {device}"
+
+    @functools.cached_property
+    def inverse(self):
+        inv = torch.empty_like(self.order)
+        inv[self.order] = torch.arange(self.V, device=self.device)
+        return inv
+
+    @functools.cached_property
+    def counts(self):
+        return (self.seg_start[1:] - self.seg_start[:-1]).to(torch.float32).view(-1, 1)
+
+    @functools.cached_property
+    def rows(self):
+        return self.order, self.inverse, self.seg_start, self.counts
+
+    @functools.cached_property
+    def lengths(self):
+        """the rows of every segment as a tuple of Python ints"""
+        off = self.seg_start.tolist()
+        return tuple(off[i + 1] - off[i] for i in range(len(off) - 1))
+
+    @functools.cached_property
+    def indices(self):
+        """the batch index of every segment, ascending, as a tuple of Python ints"""
+        first = self.order[self.seg_start[:-1].long()] if self.V else self.order[:0]
+        return tuple(int(v) for v in self._batch[first].tolist())
+
+    @functools.cached_property
+    def chunks(self):
+        """(chunk_seg int32 [chunks], chunk_first int32 [B + 1], chunks): the chunk list of the per-sample attention kernels
+        (qattn_chunk_list), a pure function of the segment lengths"""
+        chunk_seg, chunk_first = get_backend().qattn_chunk_list(self.seg_start.cpu())
+        return chunk_seg.to(self.device), chunk_first.to(self.device), chunk_seg.numel()
+
+    def held_rows(self, rows):
+        """rows: caller rows int64 [B] or [B, M], row b naming rows of segment b -> (the held rows, clamped into [0, V); bool of
+        the same shape: the row exists and lies inside its segment).  Device arithmetic only."""
+        inside = (rows >= 0) & (rows < self.V)
+        held = rows.clamp(0, self.V - 1)
+        if self.held_of is not None:
+            held = self.held_of[held]
+        segment = torch.arange(self.B, dtype=torch.int32, device=rows.device)
+        inside &= self.seg_of_row[held] == segment.view((-1,) + (1,) * (rows.dim() - 1))
+        return held, inside
 
 
 class _Workspace:
@@ -1303,35 +1399,26 @@ class _HipEngine:
                    "ms3d_qattn_chunk_list")
         return chunk_seg, chunk_first
 
-    def _qattn_check(self, queries, k, v, mask, row_map, H):
-        """-> (queries, k, v) contiguous on the device and (V, B, Q, D)"""
-        queries, k, v = self._dev(queries), self._dev(k), self._dev(v)
-        assert queries.dtype == k.dtype == v.dtype == torch.float32 and queries.dim() == 3 and k.dim() == v.dim() == 2
-        c = k.size(1)
-        assert queries.size(2) == c and tuple(v.shape) == tuple(k.shape) and H >= 1 and c % H == 0
-        V, (B, Q) = k.size(0), queries.shape[:2]
+    def _sample_attn_check(self, rows, per_sample, mask, group, H):
+        """rows: the [V, C] tensors of a call, per_sample: its [B, Q, C] ones -> all of them contiguous on the device, in that
+        order, and (V, B, Q, D); group: the BatchGroup of the rows, checked against V, B and the device"""
+        rows, per_sample = [self._dev(t) for t in rows], [self._dev(t) for t in per_sample]
+        x, q = rows[0], per_sample[0]
+        assert x.dim() == 2 and q.dim() == 3 and H >= 1 and x.size(1) % H == 0 and q.size(2) == x.size(1)
+        assert all(t.dtype == torch.float32 and t.shape == x.shape for t in rows)
+        assert all(t.dtype == torch.float32 and t.shape == q.shape for t in per_sample)
+        V, (B, Q) = x.size(0), q.shape[:2]
+        group.check(V, x.device, B)
         if mask is not None:
-            assert mask.dtype == torch.bool and mask.is_contiguous() and tuple(mask.shape) == (V, Q) and mask.device == k.device
-        if row_map is not None:
-            assert row_map.dtype == torch.int32 and row_map.is_contiguous() and row_map.numel() == V
-        return queries, k, v, V, B, Q, c // H
+            assert mask.dtype == torch.bool and mask.is_contiguous() and tuple(mask.shape) == (V, Q) and mask.device == x.device
+        return (*rows, *per_sample, V, B, Q, x.size(1) // H)
 
-    @staticmethod
-    def _qattn_group(group, V, B):
-        order, seg_start, chunk_seg, chunk_first, chunks = group
-        assert order.dtype == torch.int64 and order.is_contiguous() and order.numel() == V
-        assert seg_start.dtype == torch.int32 and seg_start.is_contiguous() and seg_start.numel() == B + 1
-        assert chunk_seg.dtype == torch.int32 and chunk_seg.is_contiguous() and chunk_seg.numel() == chunks
-        assert chunk_first.dtype == torch.int32 and chunk_first.is_contiguous() and chunk_first.numel() == B + 1
-        return order, seg_start, chunk_seg, chunk_first, int(chunks)
-
-    def qattn_forward(self, queries, k, v, mask, row_map, group, H, scale):
+    def qattn_forward(self, queries, k, v, mask, group, H, scale):
         """-> (out [B, Q, C], lse [B, Q, H]): per sample, softmax over the sample's rows that mask [V, Q] (bool, caller's row
-        order; None: none) does not block of scale * <queries[b, q, h], k[i, h]>, applied to v.  k / v [V, C] as held; row_map
-        int32 [V] held row -> caller's row, or None; group = (order, seg_start, chunk_seg, chunk_first, chunks):
-        CoordinateManager.batch_rows and batch_chunks.  A (b, q) without an unblocked row: out = 0, lse = 0."""
-        queries, k, v, V, B, Q, d = self._qattn_check(queries, k, v, mask, row_map, H)
-        order, seg_start, chunk_seg, chunk_first, chunks = self._qattn_group(group, V, B)
+        order; None: none) does not block of scale * <queries[b, q, h], k[i, h]>, applied to v.  k / v [V, C] as held; group:
+        the BatchGroup of the rows.  A (b, q) without an unblocked row: out = 0, lse = 0."""
+        k, v, queries, V, B, Q, d = self._sample_attn_check((k, v), (queries,), mask, group, H)
+        order, seg_start, row_map, (chunk_seg, chunk_first, chunks) = group.order, group.seg_start, group.row_map, group.chunks
         dev = k.device
         out = torch.empty((B, Q, k.size(1)), dtype=torch.float32, device=dev)
         lse = torch.empty((B, Q, H), dtype=torch.float32, device=dev)
@@ -1343,11 +1430,11 @@ class _HipEngine:
                                                _lib.stream_handle()), "ms3d_qattn_forward")
         return out, lse
 
-    def qattn_backward_q(self, queries, k, v, mask, row_map, group, out, lse, dout, H, scale, need_dq=True):
+    def qattn_backward_q(self, queries, k, v, mask, group, out, lse, dout, H, scale, need_dq=True):
         """-> (dq [B, Q, C] or None, delta [B, Q, H]); delta, the residual sum_i p <dout, v - out> per query and head, is what
         qattn_backward_kv reads.  One partial per chunk, added in chunk order."""
-        queries, k, v, V, B, Q, d = self._qattn_check(queries, k, v, mask, row_map, H)
-        order, seg_start, chunk_seg, chunk_first, chunks = self._qattn_group(group, V, B)
+        k, v, queries, V, B, Q, d = self._sample_attn_check((k, v), (queries,), mask, group, H)
+        order, seg_start, row_map, (chunk_seg, chunk_first, chunks) = group.order, group.seg_start, group.row_map, group.chunks
         dout = self._dev(dout)
         assert tuple(dout.shape) == tuple(queries.shape) == tuple(out.shape) and dout.dtype == torch.float32
         dev = k.device
@@ -1362,14 +1449,13 @@ class _HipEngine:
                                                   _lib.stream_handle()), "ms3d_qattn_backward_q")
         return dq, delta
 
-    def qattn_backward_kv(self, queries, k, v, mask, row_map, seg_of_row, out, lse, delta, dout, H, scale, need_dk=True,
-                          need_dv=True):
-        """-> (dk, dv) [V, C] (None where not asked for): every row loops over the queries of its sample seg_of_row[i]
-        (CoordinateManager.batch_segments) in ascending order"""
-        queries, k, v, V, B, Q, d = self._qattn_check(queries, k, v, mask, row_map, H)
+    def qattn_backward_kv(self, queries, k, v, mask, group, out, lse, delta, dout, H, scale, need_dk=True, need_dv=True):
+        """-> (dk, dv) [V, C] (None where not asked for): every row loops over the queries of its sample group.seg_of_row[i]
+        in ascending order"""
+        k, v, queries, V, B, Q, d = self._sample_attn_check((k, v), (queries,), mask, group, H)
+        row_map, seg_of_row = group.row_map, group.seg_of_row
         dout = self._dev(dout)
         assert tuple(dout.shape) == tuple(queries.shape) == tuple(out.shape) and (need_dk or need_dv)
-        assert seg_of_row.dtype == torch.int32 and seg_of_row.is_contiguous() and seg_of_row.numel() == V
         dk = torch.empty_like(k) if need_dk else None
         dv = torch.empty_like(v) if need_dv else None
         _lib.check(self.lib.ms3d_qattn_backward_kv(_lib.ptr(queries), _lib.ptr(k), _lib.ptr(v), _lib.ptr(mask), _lib.ptr(row_map),
@@ -1380,27 +1466,13 @@ class _HipEngine:
         return dk, dv
 
     # ---- per-sample voxel attention, the reverse direction: rows attend to the queries of their sample (csrc/vattn.hip)
-    def _vattn_check(self, x, keys, values, mask, row_map, seg_of_row, H):
-        """-> (x, keys, values) contiguous on the device and (V, B, Q, D); the checks of _qattn_check with the roles swapped"""
-        x, keys, values = self._dev(x), self._dev(keys), self._dev(values)
-        assert x.dtype == keys.dtype == values.dtype == torch.float32 and x.dim() == 2 and keys.dim() == values.dim() == 3
-        c = x.size(1)
-        assert keys.size(2) == c and tuple(values.shape) == tuple(keys.shape) and H >= 1 and c % H == 0
-        V, (B, Q) = x.size(0), keys.shape[:2]
-        if mask is not None:
-            assert mask.dtype == torch.bool and mask.is_contiguous() and tuple(mask.shape) == (V, Q) and mask.device == x.device
-        if row_map is not None:
-            assert row_map.dtype == torch.int32 and row_map.is_contiguous() and row_map.numel() == V
-        if seg_of_row is not None:
-            assert seg_of_row.dtype == torch.int32 and seg_of_row.is_contiguous() and seg_of_row.numel() == V
-        return x, keys, values, V, B, Q, c // H
-
-    def vattn_forward(self, x, keys, values, mask, row_map, seg_of_row, H, scale):
-        """-> (out [V, C], lse [V, H]): per held row i, softmax over the queries of its sample seg_of_row[i]
-        (CoordinateManager.batch_segments) that mask [V, Q] (bool, caller's row order; None: none) does not block of scale *
-        <x[i, h], keys[b, q, h]>, applied to values.  x [V, C] as held, keys / values [B, Q, C]; row_map int32 [V] held row ->
-        caller's row, or None.  A row without an unblocked query: out = 0, lse = 0."""
-        x, keys, values, V, B, Q, d = self._vattn_check(x, keys, values, mask, row_map, seg_of_row, H)
+    def vattn_forward(self, x, keys, values, mask, group, H, scale):
+        """-> (out [V, C], lse [V, H]): per held row i, softmax over the queries of its sample group.seg_of_row[i] that mask
+        [V, Q] (bool, caller's row order; None: none) does not block of scale * <x[i, h], keys[b, q, h]>, applied to values.
+        x [V, C] as held, keys / values [B, Q, C]; group: the BatchGroup of the rows.  A row without an unblocked query: out
+        = 0, lse = 0."""
+        x, keys, values, V, B, Q, d = self._sample_attn_check((x,), (keys, values), mask, group, H)
+        row_map, seg_of_row = group.row_map, group.seg_of_row
         out = torch.empty_like(x)
         lse = torch.empty((V, H), dtype=torch.float32, device=x.device)
         _lib.check(self.lib.ms3d_vattn_forward(_lib.ptr(x), _lib.ptr(keys), _lib.ptr(values), _lib.ptr(mask), _lib.ptr(row_map),
@@ -1409,10 +1481,11 @@ class _HipEngine:
                    "ms3d_vattn_forward")
         return out, lse
 
-    def vattn_backward_x(self, x, keys, values, mask, row_map, seg_of_row, out, lse, dout, H, scale, need_dx=True):
+    def vattn_backward_x(self, x, keys, values, mask, group, out, lse, dout, H, scale, need_dx=True):
         """-> (dx [V, C] or None, delta [V, H]); delta, the residual sum_q p <dout, values - out> per row and head, is what
         vattn_backward_kv reads"""
-        x, keys, values, V, B, Q, d = self._vattn_check(x, keys, values, mask, row_map, seg_of_row, H)
+        x, keys, values, V, B, Q, d = self._sample_attn_check((x,), (keys, values), mask, group, H)
+        row_map, seg_of_row = group.row_map, group.seg_of_row
         dout = self._dev(dout)
         assert tuple(dout.shape) == tuple(x.shape) == tuple(out.shape) and dout.dtype == torch.float32
         dx = torch.empty_like(x) if need_dx else None
@@ -1423,13 +1496,11 @@ class _HipEngine:
                                                   _lib.ptr(dx), _lib.ptr(delta), _lib.stream_handle()), "ms3d_vattn_backward_x")
         return dx, delta
 
-    def vattn_backward_kv(self, x, keys, values, mask, row_map, group, out, lse, delta, dout, H, scale, need_dk=True,
-                          need_dv=True):
+    def vattn_backward_kv(self, x, keys, values, mask, group, out, lse, delta, dout, H, scale, need_dk=True, need_dv=True):
         """-> (dkeys, dvalues) [B, Q, C] (None where not asked for): sums over the rows of a sample, one partial per chunk of
-        group = (order, seg_start, chunk_seg, chunk_first, chunks) (CoordinateManager.batch_rows and batch_chunks, the chunk
-        list of qattn_forward), added in chunk order"""
-        x, keys, values, V, B, Q, d = self._vattn_check(x, keys, values, mask, row_map, None, H)
-        order, seg_start, chunk_seg, chunk_first, chunks = self._qattn_group(group, V, B)
+        group.chunks (the chunk list of qattn_forward), added in chunk order"""
+        x, keys, values, V, B, Q, d = self._sample_attn_check((x,), (keys, values), mask, group, H)
+        order, seg_start, row_map, (chunk_seg, chunk_first, chunks) = group.order, group.seg_start, group.row_map, group.chunks
         dout = self._dev(dout)
         assert tuple(dout.shape) == tuple(x.shape) == tuple(out.shape) and (need_dk or need_dv)
         dk = torch.empty_like(keys) if need_dk else None
@@ -1450,20 +1521,17 @@ class _HipEngine:
     def fps_resident_rows(self):
         return int(self.lib.ms3d_fps_resident_rows())
 
-    def fps(self, data, order, seg_start, row_map, start_held, M):
+    def fps(self, data, group, start_held, M):
         """-> int64 [B, M] caller rows: M farthest-point picks per sample.  data [V, 4] on the device as held: int32
-        coordinates (exact integer distances) or float32 points (float32 distances, no FMA), batch column first; order int64
-        [V] / seg_start int32 [B + 1]: the rows of every sample (CoordinateManager.batch_rows); row_map int32 [V] held row ->
-        caller's row, or None; start_held int64 [B] held rows, or None (the lowest caller row of every sample)."""
+        coordinates (exact integer distances) or float32 points (float32 distances, no FMA), batch column first; group: the
+        BatchGroup of the rows; start_held int64 [B] held rows, or None (the lowest caller row of every sample)."""
         if not hasattr(self.lib, "ms3d_fps_i32"):
             raise NotImplementedError("farthest point sampling needs a library with ms3d_fps_i32")
         assert data.is_cuda and data.is_contiguous() and data.dim() == 2 and data.size(1) == 4
         assert data.dtype in (torch.int32, torch.float32)
-        V, B, dev = data.size(0), seg_start.numel() - 1, data.device
-        assert order.dtype == torch.int64 and order.is_contiguous() and order.numel() == V and order.device == dev
-        assert seg_start.dtype == torch.int32 and seg_start.is_contiguous() and seg_start.dim() == 1 and seg_start.device == dev
-        if row_map is not None:
-            assert row_map.dtype == torch.int32 and row_map.is_contiguous() and row_map.numel() == V and row_map.device == dev
+        V, B, dev = data.size(0), group.B, data.device
+        group.check(V, dev)
+        order, seg_start, row_map = group.order, group.seg_start, group.row_map
         if start_held is not None:
             assert start_held.dtype == torch.int64 and start_held.is_contiguous() and tuple(start_held.shape) == (B,)
             assert start_held.device == dev
@@ -1483,12 +1551,11 @@ class _HipEngine:
         """(queries a workgroup takes, rows of the support set in LDS at a time)"""
         return int(self.lib.ms3d_knn_queries_per_group()), int(self.lib.ms3d_knn_rows_per_tile())
 
-    def knn(self, data, order, seg_start, row_map, queries, q_start, max_queries, k, cap):
+    def knn(self, data, group, queries, q_start, max_queries, k, cap):
         """-> (int64 [NQ, k] caller rows, [NQ, k] distances: int32 WORDS (unsigned values) for coordinates, float32 for points):
         the k nearest rows of every query's sample, nearest first, ties to the lower caller row; slots nothing qualified for
         hold -1 and all-ones bits / +inf.  data [V, 4] on the device as held: int32 coordinates or float32 points, batch
-        column first; order int64 [V] / seg_start int32 [B + 1]: the rows of every sample (CoordinateManager.batch_rows);
-        row_map int32 [V] held row -> caller's row, or None; queries int32 [NQ, 4] words (segment, x, y, z: coordinates, or
+        column first; group: the BatchGroup of the rows; queries int32 [NQ, 4] words (segment, x, y, z: coordinates, or
         the bits of float32 points) grouped by segment, q_start int32 [B + 1] their starts, max_queries the largest number
         of queries a segment has; cap: None, or the largest distance that qualifies (an int >= 0 for coordinates, a float
         >= 0 for points)."""
@@ -1496,11 +1563,9 @@ class _HipEngine:
             raise NotImplementedError("k nearest neighbours need a library with ms3d_knn_i32")
         assert data.is_cuda and data.is_contiguous() and data.dim() == 2 and data.size(1) == 4
         assert data.dtype in (torch.int32, torch.float32)
-        V, B, dev = data.size(0), seg_start.numel() - 1, data.device
-        assert order.dtype == torch.int64 and order.is_contiguous() and order.numel() == V and order.device == dev
-        assert seg_start.dtype == torch.int32 and seg_start.is_contiguous() and seg_start.dim() == 1 and seg_start.device == dev
-        if row_map is not None:
-            assert row_map.dtype == torch.int32 and row_map.is_contiguous() and row_map.numel() == V and row_map.device == dev
+        V, B, dev = data.size(0), group.B, data.device
+        group.check(V, dev)
+        order, seg_start, row_map = group.order, group.seg_start, group.row_map
         assert queries.dtype == torch.int32 and queries.is_contiguous() and queries.dim() == 2 and queries.size(1) == 4
         assert queries.device == dev
         assert q_start.dtype == torch.int32 and q_start.is_contiguous() and tuple(q_start.shape) == (B + 1,) and q_start.device == dev
@@ -1523,19 +1588,15 @@ class _HipEngine:
         return out, d2
 
     # ---- instance normalisation over the batch grouping of a coordinate set (csrc/inorm.hip)
-    def _inorm_check(self, x, order, seg_start, seg_of_row):
+    def inorm_forward(self, x, group, eps, weight, bias):
+        """-> (y [V, C], mean float64 [B, C], invstd float64 [B, C]): x normalised per segment of group (the BatchGroup of the
+        rows) and channel with the biased variance, times weight plus bias ([C] / [1, C] or None: 1 / 0).  Rows are read where
+        they lie."""
+        x = self._dev(x)
         assert x.dtype == torch.float32 and x.dim() == 2
-        assert order.dtype == torch.int64 and order.is_contiguous() and order.numel() == x.size(0)
-        assert seg_start.dtype == torch.int32 and seg_start.is_contiguous() and seg_start.numel() >= 1
-        assert seg_of_row.dtype == torch.int32 and seg_of_row.is_contiguous() and seg_of_row.numel() == x.size(0)
-        return x.size(0), x.size(1), seg_start.numel() - 1
-
-    def inorm_forward(self, x, order, seg_start, seg_of_row, eps, weight, bias):
-        """-> (y [V, C], mean float64 [B, C], invstd float64 [B, C]): x normalised per segment (order / seg_start: CoordinateManager.batch_rows;
-        seg_of_row: batch_segments) and channel with the biased variance, times weight plus bias ([C] / [1, C] or None: 1 / 0).
-        Rows are read where they lie."""
-        x = self._dev(x).contiguous()
-        v, c, B = self._inorm_check(x, order, seg_start, seg_of_row)
+        v, c, B = x.size(0), x.size(1), group.B
+        group.check(v, x.device)
+        order, seg_start, seg_of_row = group.order, group.seg_start, group.seg_of_row
         if weight is not None:
             weight = self._dev(weight).contiguous()
             assert weight.dtype == torch.float32 and weight.numel() == c
@@ -1553,13 +1614,14 @@ class _HipEngine:
                                                C.c_size_t(ws.numel()), _lib.stream_handle()), "ms3d_inorm_forward")
         return y, mean, invstd
 
-    def inorm_backward(self, dy, x, order, seg_start, seg_of_row, mean, invstd, weight, want_dx=True, want_dweight=True,
-                       want_dbias=True):
+    def inorm_backward(self, dy, x, group, mean, invstd, weight, want_dx=True, want_dweight=True, want_dbias=True):
         """-> (dx [V, C], dweight [C], dbias [C]), each None when not wanted; the segment sums in a fixed order, dweight and
         dbias over ascending segments"""
-        x = self._dev(x).contiguous()
-        dy = self._dev(dy).contiguous()
-        v, c, B = self._inorm_check(x, order, seg_start, seg_of_row)
+        x, dy = self._dev(x), self._dev(dy)
+        assert x.dtype == torch.float32 and x.dim() == 2
+        v, c, B = x.size(0), x.size(1), group.B
+        group.check(v, x.device)
+        order, seg_start, seg_of_row = group.order, group.seg_start, group.seg_of_row
         assert dy.dtype == torch.float32 and tuple(dy.shape) == (v, c)
         assert mean.dtype == torch.float64 and invstd.dtype == torch.float64 and mean.is_contiguous() and invstd.is_contiguous()
         assert tuple(mean.shape) == (B, c) and tuple(invstd.shape) == (B, c)

@@ -31,7 +31,7 @@
 //              them with 16-byte accesses, a thread four consecutive rows a step.  A thread meets the same rows in every sweep,
 //              so the minima need no barrier.  The workspace is never assumed zero: the gather writes every word the sweeps
 //              read, the padding up to a multiple of four rows included (minimum 0, caller row ~0: key 0, for ever).
-#include "common.h"
+#include "points.h"
 #include "../../include/minsu3d_hip.h"
 
 namespace {
@@ -44,17 +44,8 @@ constexpr int FPS_MAX_B = 65535;
 constexpr int FPS_SEG_PAD = 8;   // workspace rows between the starts of two samples beyond their rows: ws_rows_of
 constexpr unsigned FPS_F32_INF = 0x7f800000u;
 
-// (dx*dx + dy*dy) + dz*dz, seven float32 roundings.  hipcc contracts a * b + c into an FMA by default -- HIP's __fmul_rn and
-// __fadd_rn are the plain operators and are contracted like them -- so contraction is switched off for this body alone.
-__device__ __forceinline__ float dist_f32(float x, float y, float z, float cx, float cy, float cz)
-{
-#pragma clang fp contract(off)
-    const float dx = x - cx, dy = y - cy, dz = z - cz;
-    const float xx = dx * dx, yy = dy * dy, zz = dz * dz;
-    const float xy = xx + yy;
-    return xy + zz;
-}
-
+// F32: dist_f32 of points.h.  Integers: plain 32-bit products here, 24-bit ones in csrc/knn.hip -- the same bits over the
+// packable range; the two are kept apart because which is faster here has not been measured.
 template <bool F32> __device__ __forceinline__ unsigned dist(unsigned x, unsigned y, unsigned z, unsigned cx, unsigned cy,
                                                              unsigned cz)
 {
@@ -113,13 +104,6 @@ __device__ __forceinline__ void choose(const Pick &mine, Shared &sh, long long *
     cx = sh.pick[0], cy = sh.pick[1], cz = sh.pick[2];
 }
 
-// the held row at position p of `order`, kept inside [0, V): an index outside its array is never followed
-__device__ __forceinline__ long held_row(const long long *__restrict__ order, long p, int V)
-{
-    const long long h = order[p];
-    return h < 0 ? 0 : (h >= V ? V - 1 : (long)h);
-}
-
 // data [V][4]: int32 (batch, x, y, z) for F32 == false, float (batch, x, y, z) for F32 == true -- both read as 32-bit words
 template <bool F32>
 __global__ __launch_bounds__(FPS_THREADS) void fps_kernel(const unsigned *__restrict__ data, const long long *__restrict__ order,
@@ -129,7 +113,7 @@ __global__ __launch_bounds__(FPS_THREADS) void fps_kernel(const unsigned *__rest
 {
     __shared__ Shared sh;
     const int b = blockIdx.x, t = threadIdx.x;
-    const int s = min(max(seg_start[b], 0), V), e = min(max(seg_start[b + 1], 0), V);
+    const int s = clamp_to(seg_start[b], V), e = clamp_to(seg_start[b + 1], V);
     const int n = e - s;
     if (n <= 0) return;      // the whole workgroup: no barrier is left waiting
     long long *const dst = out + (size_t)b * M;

@@ -35,7 +35,7 @@
 //           lives in LDS in column layout list[j][thread], unsorted while rows stream by: a candidate takes the place of the
 //           largest key and k independent reads find the new largest; at the end a key's slot is the number of keys below it.
 #include <string.h>
-#include "common.h"
+#include "points.h"
 #include "../../include/minsu3d_hip.h"
 
 namespace {
@@ -53,17 +53,8 @@ constexpr unsigned KNN_F32_INF = 0x7f800000u;
 
 static_assert(KNN_TILE % KNN_QUERIES == 0 && KNN_TILE % KNN_UNROLL == 0 && KNN_STASH > KNN_UNROLL, "tile geometry");
 
-// (dx*dx + dy*dy) + dz*dz, seven float32 roundings; hipcc contracts a * b + c into an FMA by default, so contraction is switched
-// off for this body alone (as in csrc/fps.hip)
-__device__ __forceinline__ float dist_f32(float qx, float qy, float qz, float px, float py, float pz)
-{
-#pragma clang fp contract(off)
-    const float dx = qx - px, dy = qy - py, dz = qz - pz;
-    const float xx = dx * dx, yy = dy * dy, zz = dz * dz;
-    const float xy = xx + yy;
-    return xy + zz;
-}
-
+// F32: dist_f32 of points.h, the distance of csrc/fps.hip.  Integers: 24-bit products here, plain 32-bit ones in csrc/fps.hip --
+// the same bits over the packable range; the two are kept apart because which is faster there has not been measured.
 template <bool F32> __device__ __forceinline__ unsigned dist(unsigned qx, unsigned qy, unsigned qz, unsigned px, unsigned py,
                                                              unsigned pz)
 {
@@ -83,12 +74,9 @@ __global__ __launch_bounds__(KNN_PACK_THREADS) void knn_pack_kernel(const unsign
 {
     const long p = (long)blockIdx.x * KNN_PACK_THREADS + threadIdx.x;
     if (p >= V) return;
-    const long long o = order[p];
-    const long h = o < 0 ? 0 : (o >= V ? V - 1 : (long)o);      // kept inside [0, V): an index outside its array is never followed
+    const long h = held_row(order, p, V);
     ws[p] = make_uint4(data[4 * h + 1], data[4 * h + 2], data[4 * h + 3], row_map ? (unsigned)row_map[h] : (unsigned)h);
 }
-
-__device__ __forceinline__ int clamp_to(int v, int hi) { return min(max(v, 0), hi); }
 
 template <bool F32>
 __global__ __launch_bounds__(KNN_QUERIES) void knn_kernel(const uint4 *__restrict__ sup, const int *__restrict__ seg_start,

@@ -62,9 +62,9 @@ class _Recorder:
     def __init__(self):
         self.calls = []
 
-    def inorm_forward(self, x, order, seg_start, seg_of_row, eps, weight, bias):
-        self.calls.append((order, seg_start, seg_of_row, eps))
-        B = seg_start.numel() - 1
+    def inorm_forward(self, x, group, eps, weight, bias):
+        self.calls.append((group.order, group.seg_start, group.seg_of_row, eps))
+        B = group.seg_start.numel() - 1
         return x.clone(), x.new_zeros((B, x.size(1))), x.new_ones((B, x.size(1)))
 
 
@@ -127,9 +127,8 @@ def test_backend_without_the_kernel_is_an_error(name, eps):
     cm, x = _cpu_tensor()
     with pytest.raises(NotImplementedError, match=r"needs the HIP backend \(ms3d_inorm_forward\)"):
         getattr(ME, name)(4)(x)
-    order, _, offsets, _ = cm.batch_rows(1)
     with pytest.raises(NotImplementedError, match=r"needs the HIP backend \(ms3d_inorm_forward\)"):
-        Fn.instance_norm(x.F, None, None, (order, offsets, cm.batch_segments(1)), 1e-5)
+        Fn.instance_norm(x.F, None, None, cm.batch_group(1), 1e-5)
 
 
 @pytest.mark.parametrize("name,module,kw", ACTIVATIONS)

@@ -190,11 +190,6 @@ def test_three_batches_unequal_interleaved(ME, S, C):
 
 
 # ---------------------------------------------------------------------------------------------- 2. unaligned rows
-def _grouping(cm):
-    order, _, offsets, _ = cm.batch_rows(1)
-    return order, offsets, cm.batch_segments(1)
-
-
 def test_unaligned_rows_take_the_scalar_route(ME, be, S):
     """C = 4 rows carved 8 bytes into a buffer are contiguous but not 16-byte aligned: the guarded 4-byte route runs and gives
     the bits of the 16-byte one, forward and backward"""
@@ -202,7 +197,7 @@ def test_unaligned_rows_take_the_scalar_route(ME, be, S):
     coords = cloud(rng, [S + 1, 1, 700], [0, 2, 5])
     V = coords.shape[0]
     cm = manager_of(ME, coords)
-    order, offsets, seg = _grouping(cm)
+    group = cm.batch_group(1)
     x = torch.from_numpy(features(rng, V, 4)).cuda()
     dy = torch.from_numpy(features(rng, V, 4)).cuda()
     w = torch.from_numpy(features(rng, 1, 4)).cuda()
@@ -211,11 +206,11 @@ def test_unaligned_rows_take_the_scalar_route(ME, be, S):
     xu = flat[2:].view(V, 4)
     xu.copy_(x)
     assert x.data_ptr() % 16 == 0 and xu.data_ptr() % 16 == 8 and xu.is_contiguous()
-    ya, ma, ia = be.inorm_forward(x, order, offsets, seg, 1e-5, w, b)
-    yu, mu, iu = be.inorm_forward(xu, order, offsets, seg, 1e-5, w, b)
+    ya, ma, ia = be.inorm_forward(x, group, 1e-5, w, b)
+    yu, mu, iu = be.inorm_forward(xu, group, 1e-5, w, b)
     assert torch.equal(ya, yu) and torch.equal(ma, mu) and torch.equal(ia, iu)
-    ga = be.inorm_backward(dy, x, order, offsets, seg, ma, ia, w)
-    gu = be.inorm_backward(dy, xu, order, offsets, seg, mu, iu, w)
+    ga = be.inorm_backward(dy, x, group, ma, ia, w)
+    gu = be.inorm_backward(dy, xu, group, mu, iu, w)
     for a, u in zip(ga, gu):
         assert torch.equal(a, u)
     x64 = x.double().cpu().requires_grad_(True)
@@ -355,6 +350,7 @@ def test_bit_reproducible(ME, S):
 def test_long_segments_through_the_backend(be, S, C):
     """20000 and 9000 rows in two interleaved segments, straight through the backend (no coordinates are needed for the
     grouping): on 132 channels a thread walks more rows than it keeps in flight, so the row loop comes round again"""
+    from minsu3d_amd.backend import BatchGroup
     rng = np.random.default_rng(59 + C)
     batch = np.concatenate([np.zeros(20000, np.int64), np.ones(9000, np.int64)])
     rng.shuffle(batch)
@@ -362,13 +358,13 @@ def test_long_segments_through_the_backend(be, S, C):
     bt = torch.from_numpy(batch).cuda()
     order = torch.sort(bt, stable=True).indices
     offsets = torch.tensor([0, 20000, V], dtype=torch.int32, device="cuda")
-    seg = bt.to(torch.int32)
+    group = BatchGroup.from_tensors(order, offsets, bt.to(torch.int32))
     x = torch.from_numpy(features(rng, V, C)).cuda()
     dy = torch.from_numpy(features(rng, V, C)).cuda()
     w = torch.from_numpy(features(rng, 1, C)).cuda()
     b = torch.from_numpy(features(rng, 1, C)).cuda()
-    y, mean, invstd = be.inorm_forward(x, order, offsets, seg, 1e-5, w, b)
-    dx, dw, db = be.inorm_backward(dy, x, order, offsets, seg, mean, invstd, w)
+    y, mean, invstd = be.inorm_forward(x, group, 1e-5, w, b)
+    dx, dw, db = be.inorm_backward(dy, x, group, mean, invstd, w)
     x64 = x.double().cpu().requires_grad_(True)
     w64, b64 = w.double().cpu().requires_grad_(True), b.double().cpu().requires_grad_(True)
     want = reference(x64, batch, 1e-5, w64, b64)
@@ -379,7 +375,7 @@ def test_long_segments_through_the_backend(be, S, C):
     check(tag + " dweight", dw.view(1, -1), w64.grad)
     check(tag + " dbias", db.view(1, -1), b64.grad)
     # no affine: weight 1, bias 0
-    y1, _, _ = be.inorm_forward(x, order, offsets, seg, 1e-5, None, None)
+    y1, _, _ = be.inorm_forward(x, group, 1e-5, None, None)
     one, zero = torch.ones(1, C, dtype=torch.float64), torch.zeros(1, C, dtype=torch.float64)
     check(tag + " forward without affine", y1, reference(x.double().cpu(), batch, 1e-5, one, zero))
 
@@ -477,13 +473,14 @@ def test_conv_instancenorm_elu_conv_block(ME):
 # ---------------------------------------------------------------------------------------------- 11. argument contracts
 def test_argument_contracts(be):
     from minsu3d_amd._lib import HipLibraryError, E_UNSUPPORTED
+    from minsu3d_amd.backend import BatchGroup
     dev = "cuda"
     order = torch.arange(5, dtype=torch.int64, device=dev)
     offsets = torch.tensor([0, 5], dtype=torch.int32, device=dev)
     seg = torch.zeros(5, dtype=torch.int32, device=dev)
     x0 = torch.zeros((5, 0), dtype=torch.float32, device=dev)
     with pytest.raises(HipLibraryError, match=str(E_UNSUPPORTED)):
-        be.inorm_forward(x0, order, offsets, seg, 1e-5, None, None)
+        be.inorm_forward(x0, BatchGroup.from_tensors(order, offsets, seg), 1e-5, None, None)
     # 65536 segments are refused before any pointer is looked at (asked of the library itself: nothing is allocated for it)
     import ctypes as C
     null = C.c_void_p(0)
@@ -504,8 +501,9 @@ def test_argument_contracts(be):
     e64, e32 = order[:0], seg[:0]
     none = torch.zeros(1, dtype=torch.int32, device=dev)
     xe = torch.zeros((0, 4), dtype=torch.float32, device=dev)
-    y, mean, invstd = be.inorm_forward(xe, e64, none, e32, 1e-5, None, None)
+    empty = BatchGroup.from_tensors(e64, none, e32)
+    y, mean, invstd = be.inorm_forward(xe, empty, 1e-5, None, None)
     assert tuple(y.shape) == (0, 4) and tuple(mean.shape) == (0, 4) and tuple(invstd.shape) == (0, 4)
-    dx, dw, db = be.inorm_backward(xe, xe, e64, none, e32, mean, invstd, None)
+    dx, dw, db = be.inorm_backward(xe, xe, empty, mean, invstd, None)
     assert tuple(dx.shape) == (0, 4) and not dw.any() and not db.any()
     torch.cuda.synchronize()

@@ -169,7 +169,7 @@ def test_backend_without_the_kernels_is_an_error():
     k, v = _tensors()
     x = torch.randn(V, 8)
     with pytest.raises(NotImplementedError, match=r"needs the HIP backend \(ms3d_qattn_forward\)"):
-        Fn.query_attention_rows(torch.randn(B, 4, 8), x, x, None, None, None, None, 2, 0.5)
+        Fn.query_attention_rows(torch.randn(B, 4, 8), x, x, None, None, 2, 0.5)
     with pytest.raises(NotImplementedError, match="ms3d_qattn_forward"):
         ME.query_attention(torch.randn(B, 4, 8), k, v, 2)
 

@@ -175,7 +175,7 @@ def test_backend_without_the_kernels_is_an_error():
     backend.set_backend(Bare())                        # (tests/conftest.py restores the backend)
     rows, k = torch.randn(V, 8), torch.randn(B, 4, 8)
     with pytest.raises(NotImplementedError, match=r"needs the HIP backend \(ms3d_vattn_forward\)"):
-        Fn.voxel_attention_rows(rows, k, k, None, None, None, None, 2, 0.5)
+        Fn.voxel_attention_rows(rows, k, k, None, None, 2, 0.5)
     with pytest.raises(NotImplementedError, match="ms3d_vattn_forward"):
         ME.voxel_attention(_x(), k, k, 2)
 

@@ -87,8 +87,7 @@ def main():
             coords[:, 0] = torch.arange(coords.size(0), device=dev, dtype=coords.dtype) % B
             coords = coords[:V].contiguous()
         cm = ME.CoordinateManager(coords, spatial_sort=True)
-        cm.batch_rows(1)
-        cm.batch_segments(1)
+        cm.batch_group(1)
         for C in CHANNELS:
             torch.manual_seed(1)
             layer = ME.MinkowskiInstanceNorm(C).to(dev)

@@ -55,7 +55,7 @@ def main():
     def torch_side(x, points, q_points, q_counts, k):
         """the torch expression over x's rows; q_points: the queries grouped by sample, q_counts of them for each"""
         batch = x.C[:, 0].long()
-        lengths = x.coordinate_manager.batch_lengths(1) if isinstance(x, ME.SparseTensor) else x._batch_group()[2]
+        lengths = x.coordinate_manager.batch_lengths(1) if isinstance(x, ME.SparseTensor) else x._batch_group().lengths
         return lambda: _knn_torch(points, batch, lengths, q_points, q_counts, k, None)
 
     def report(name, what, cands, same):
