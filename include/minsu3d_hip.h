@@ -674,6 +674,53 @@ int ms3d_field_reduce(int mode, const float *feats, const long long *order, cons
 int ms3d_field_reduce_backward(int mode, const float *dvox, const int *inverse, const int *seg_start, const int *arg, long N,
                                int C, float *dfeat, ms3d_stream_t stream);
 
+/* ---- pooling and weighted sums over a neighbour index, with gradients (csrc/neighbor.hip): what a kNN index is used for --
+ * max over the k neighbours of a pick, inverse-distance interpolation of M picks onto all rows, scalar attention over a kNN
+ * graph.  float32, any C; the row layout and the contracts of the field.hip block above: every direction is a gather with one
+ * writer per output element, no float atomics, the same bytes on every run; an unknown mode, a NULL pointer that would be read
+ * or written, k < 1, k > 254 (a slot number fits a byte with 255 free), C < 1, V or N beyond 2^31 - 1 or N * k beyond 2^31 - 1
+ * (an entry number fits an int32) return MS3D_E_UNSUPPORTED; zero output rows return 0 and launch nothing; nothing is allocated
+ * inside a call.  x [V][C]: the support rows as held.  idx int64 [N][k]: per query k rows of x, or < 0 = no neighbour, in any
+ * slot; a negative index is skipped.  Values >= V are a precondition (the caller's record validated them; the kernels do not
+ * re-check).  Modes: 0 max, 1 avg, 2 sum, 3 weighted (backward only).
+ *
+ * ms3d_nbr_pool_forward (modes 0 .. 2), over the slots with idx >= 0 in ascending slot:
+ *   sum  the chain of float32 additions from 0 (ms3d_field_reduce's rule);  avg  that sum divided once by float(valid slots), a
+ *   query without one exact zeros;  max  per channel the first valid slot, then every strictly greater one: the lowest slot wins
+ *   ties, a NaN wins only from the first slot; the winning slot goes to arg uint8 [N][C] (read and written for max only), a
+ *   query without a valid slot stores 255 and yields zeros.
+ * ms3d_nbr_wsum_forward: out[n] = sum_j w[n][j] * x[idx[n][j]] over the valid slots, ascending j, one fmaf per slot and element
+ *   from 0 (ms3d_interp_forward's rule); the weight of an invalid slot is never read; a query whose single neighbour has weight 1
+ *   returns that row bit for bit.
+ * ms3d_nbr_backward: dx [V][C], written in full (no memset in front), dx[v] = the sum over the entries e = n * k + j of row v in
+ *   ascending e of  dout[n][c] where arg[n][c] == j (max) | dout[n] / float(valid[n]) (avg, valid int32 [N]: the valid slots of
+ *   every query) | dout[n] (sum) | w[e] * dout[n], one fmaf (weighted).  entry_sorted int64 [E] holds the entries with idx >= 0
+ *   grouped by row -- row v owns entry_sorted[seg_start[v] .. seg_start[v + 1]), seg_start int32 [V + 1] -- and a row is summed
+ *   in the order of its list: ascending e (one stable sort of the index by row, built once per map by the caller; where the
+ *   caller numbers the queries otherwise than they are held, ascending in ITS numbering, so that the sums do not depend on how
+ *   the rows are held); an entry outside [0, N * k) is skipped.  A row
+ *   of more than T = ms3d_nbr_chunk_entries() entries is cut into ceil(entries / T) chunks of T consecutive entries; each chunk
+ *   is summed the same way by its own thread group into a partial in ws, and the row adds its partials from 0 in chunk order.
+ *   chunk_start int32 [V + 1]: chunk_start[v + 1] - chunk_start[v] = the chunks of row v when it has more than one, else 0
+ *   (chunk_start[0] = 0); n_chunks = chunk_start[V].  A row of at most T entries is the plain chain.  ws: ms3d_nbr_ws_bytes(
+ *   n_chunks, C) = 4 * n_chunks * C bytes, 16-byte aligned, never assumed zero (0 and NULL are fine without long rows); less:
+ *   MS3D_E_WORKSPACE.  w, arg, valid: read for their mode only, NULL otherwise.  At most two launches.
+ * ms3d_nbr_wsum_backward_w: dw[n][j] = <dout[n], x[idx[n][j]]>, 0 for an invalid slot.  One wave per query: lane l takes the
+ *   channels l, l + 64, ... in ascending order (one fmaf each, from 0), then the 64 lane sums are folded by xor shuffles over
+ *   32, 16, .. 1 -- an order fixed by C alone.
+ * No atomics, no spin, no grid barrier; every loop is counted. */
+int ms3d_nbr_chunk_entries(void);
+size_t ms3d_nbr_ws_bytes(long n_chunks, int C);
+int ms3d_nbr_pool_forward(int mode, const float *x, long V, const long long *idx /*[N][k] held rows or < 0*/, long N, int k, int C,
+                          float *out, unsigned char *arg /*[N][C], max only*/, ms3d_stream_t stream);
+int ms3d_nbr_wsum_forward(const float *x, long V, const long long *idx, const float *w /*[N][k]*/, long N, int k, int C,
+                          float *out, ms3d_stream_t stream);
+int ms3d_nbr_backward(int mode, const float *dout, const float *w, const unsigned char *arg, const int *valid,
+                      const long long *entry_sorted, const int *seg_start, const int *chunk_start, long n_chunks, long V, long N,
+                      int k, int C, float *dx, void *ws, size_t ws_bytes, ms3d_stream_t stream);
+int ms3d_nbr_wsum_backward_w(const float *dout, const float *x, const long long *idx, long N, int k, int C, float *dw,
+                             ms3d_stream_t stream);
+
 /* Pair list = tile-compacted form of an offset-major table, built once per table and shared by every convolution of
  * the level (forward, backward-data, backward-weight).  Output rows are cut into tiles of 64; per tile and offset the
  * valid (input row, output row) pairs are stored contiguously, padded to a multiple of 16 ("batch" = one MFMA group).

@@ -285,10 +285,54 @@ has no such function, and nothing here is pinned to it):
     together.  No atomics, no waiting between workgroups, every loop counted.  CPU tensors take the same rule as a torch
     expression, at most 2^22 (query, row) pairs at a time.  The index is not differentiable; gradients reach x.F through
     x.F[idx].
-    Out of scope: spatial acceleration (a grid or hash walk), a fused neighbour gather or interpolation layer, mixed voxel /
-    point queries, other metrics, a different k per query, k above 64, float16 or float64 distances, gradients with respect
+    Out of scope: spatial acceleration (a grid or hash walk), mixed voxel / point queries (pooling, weighted
+    sums and interpolation over the index: knn_map and neighbor_pool / neighbor_sum / knn_interpolate, below), other metrics, a different k per query, k above 64, float16 or float64 distances, gradients with respect
     to the coordinates, a ball query's first-k-inside-the-radius order; a backend without the kernels raises
     NotImplementedError naming ms3d_knn_i32 for device tensors.
+
+Pooling and weighted sums over a neighbour index -- what a kNN index is used for: max over the k neighbours of a pick (the
+"down" block of an FPS + kNN network), inverse-distance interpolation of M picks back onto all rows (the "up" block), scalar
+attention over a kNN graph once the caller has taken a softmax over [N, k] (an engine extra, nothing of MinkowskiEngine's):
+
+    knn_map(x, k, queries=None, max_squared_distance=None) -> NeighborMap
+    NeighborMap.from_index(idx, num_rows, d2=None) -> NeighborMap
+    neighbor_pool(x, nmap, mode="max")          mode: "max" | "avg" | "sum"
+    neighbor_sum(x, nmap, weights)              weights float32 [..., k]
+    knn_interpolate(x, nmap, eps=1e-8)
+
+    A NeighborMap (backend.NeighbourGroup) is the record of one index, built once and shared by every op and layer over the
+    same graph: idx and d2 as given, N, k (1 <= k <= 254: a slot number fits a byte), V, idx_held int64 [N, k] -- the index in
+    the rows as the support and the target set HOLD them, translated once by torch gathers, so features are read and written
+    where they lie (no permuted copy of x.F) --, valid int32 [N], and on first use the transposed table (entry_sorted,
+    seg_start: the entries e = n * k + j grouped by support row, ascending e in the caller's numbering of the queries, one
+    stable sort) and -- only when a feature
+    gradient runs on the device -- the chunk list (chunk_start, n_chunks; one host read).  knn_map runs knn_query with the
+    same arguments and remembers the support (x's coordinate set or field) and the target: x itself (queries=None), y, or
+    none for an int64 [B, M] tensor of picks (results are then plain [B, M, C]).  from_index wraps a hand-made int64 index
+    [..., k] over plain rows [num_rows, C]; a negative value means no neighbour and may sit in any slot; another dtype, a
+    value >= num_rows or k > 254 is a ValueError (one host read, once).  An op given a map and an x of another set or
+    another number of rows refuses on the host (ValueError); x is the SparseTensor / TensorField the map was made for or, for
+    from_index maps, a float32 tensor [V, C]; the result is a SparseTensor / TensorField on the target's set, or a tensor.
+    The rules, all of them, over the slots with idx >= 0 in ascending slot: sum -- the chain of float32 additions from 0;
+    avg -- that sum divided once by float(valid[n]), a query without a valid slot exact zeros; max -- per channel the first
+    valid slot, then every strictly greater one (the lowest slot wins ties, a NaN wins only from the first slot), a query
+    without a valid slot zeros; neighbor_sum -- one fmaf per slot and element from 0, the weight of an invalid slot is never
+    read, a single neighbour of weight 1 returns that row bit for bit; knn_interpolate -- r = 1 / (float32(d2) + eps),
+    w = r / sum_j r over the valid slots, a torch expression on [N, k] that is not differentiable, then neighbor_sum (a map
+    without d2: ValueError).  Gradients: to the features, per support row the sum over its entries in ascending e of dout[n]
+    (sum), dout[n] / float(valid[n]) (avg), w[n, j] * dout[n] (one fmaf), dout[n, c] where the saved slot is j (max) -- a row
+    of more than ms3d_nbr_chunk_entries() entries is cut into chunks of that many, each summed the same way into a partial,
+    the partials added in chunk order; to the weights (neighbor_sum) dw[n, j] = <dout[n], x[idx[n, j]]>, 0 for an invalid
+    slot; none to idx, d2 or the coordinates.  A frozen x skips the feature pass (the chunk list is then never built), frozen
+    weights the weight pass.  csrc/neighbor.hip: gathers with one writer per element, no atomics, the same bytes on every run;
+    nothing of size [N, k, C] is ever made.  CPU tensors take the same rules as torch expressions (x[idx.clamp(min=0)]
+    masked, then reduced in slot order).  Modules without parameters: MinkowskiKNNPooling(k, mode="max") -- forward(x,
+    queries=None, nmap=None) -- and MinkowskiKNNInterpolation(k=3, eps=1e-8) -- forward(x, y, nmap=None).
+    Out of scope (each raises where it can be asked for): per-head or per-channel weights [N, k, H], a fused softmax over the
+    slots or vector attention itself, a fused x_j - x_i / relative-position edge feature, a materialising differentiable
+    [N, k, C] gather with masked slots, float16 / bfloat16 rows, k above 254, gradients with respect to coordinates or
+    distances, mixed voxel / point maps (knn_query refuses them); a backend without the kernels raises NotImplementedError
+    naming ms3d_nbr_pool_forward for device tensors.
 
 Not supported (each raises NotImplementedError naming it): `axis_types` of a KernelGenerator, a region of more than 254
 offsets, a dense grid of more than 2^31 - 1 cells, to_sparse of a tensor
@@ -310,6 +354,8 @@ from .tensor import to_sparse, to_sparse_all  # noqa: F401
 from .tensor import RegionType, KernelGenerator  # noqa: F401
 from .tensor import farthest_point_sampling  # noqa: F401  (engine extra: the seeds of the attention blocks' queries)
 from .tensor import knn_query  # noqa: F401  (engine extra: the k nearest rows of a query's own sample)
+from .tensor import knn_map, NeighborMap  # noqa: F401  (engine extra: a neighbour index as a record the ops below read)
+from .functional import neighbor_pool, neighbor_sum, knn_interpolate  # noqa: F401  (engine extra: csrc/neighbor.hip)
 from .modules import (MinkowskiConvolution, MinkowskiConvolutionTranspose, MinkowskiBatchNorm,  # noqa: F401
                       MinkowskiReLU, prepare_conv_weights, release_conv_weights,
                       MinkowskiMaxPooling, MinkowskiAvgPooling, MinkowskiSumPooling, MinkowskiGlobalMaxPooling,
@@ -320,7 +366,7 @@ from .modules import (MinkowskiConvolution, MinkowskiConvolutionTranspose, Minko
                       MinkowskiPoolingTranspose, MinkowskiInterpolation, MinkowskiChannelwiseConvolution,
                       MinkowskiInstanceNorm, MinkowskiStableInstanceNorm,
                       MinkowskiKernelAttention, kernel_attention, MinkowskiQueryAttention, query_attention,
-                      MinkowskiVoxelAttention, voxel_attention,
+                      MinkowskiVoxelAttention, voxel_attention, MinkowskiKNNPooling, MinkowskiKNNInterpolation,
                       MinkowskiToSparseTensor, MinkowskiToDenseTensor, MinkowskiToFeature,
                       MinkowskiELU, MinkowskiLeakyReLU, MinkowskiPReLU, MinkowskiSELU, MinkowskiCELU, MinkowskiGELU,
                       MinkowskiSiLU, MinkowskiTanh, MinkowskiSoftplus, MinkowskiHardswish, MinkowskiHardtanh,

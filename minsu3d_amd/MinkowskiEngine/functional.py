@@ -10,7 +10,7 @@ import threading
 
 import torch
 
-from ..backend import get_backend
+from ..backend import NBR_MODES, NBR_WEIGHTED, NeighbourGroup, get_backend
 
 # ---- matmul precision of the convolutions (torch.set_float32_matmul_precision)
 # "highest" = float32 grade everywhere; "high" / "medium" let the wide layers' bf16 kernels keep two / one of the three
@@ -895,6 +895,155 @@ class InterpolateFn(torch.autograd.Function):
 
 def interpolate(x, rows, weights, group):
     return InterpolateFn.apply(x, rows, weights, group)
+
+
+class NeighborPoolFn(torch.autograd.Function):
+    """out [N, C] = max | avg | sum of the rows x [V, C] (as held) over the valid slots of every query of a NeighbourGroup, in
+    ascending slot (csrc/neighbor.hip).  The backward is a gather through the record's table grouped by support row: one
+    writer per element, no float atomics; max keeps the winning slot as uint8 [N, C]."""
+
+    @staticmethod
+    def forward(ctx, x, nmap, mode):
+        out, arg = get_backend().nbr_pool_forward(mode, x.contiguous(), nmap)
+        ctx.geom = (nmap, mode, arg)
+        return out
+
+    @staticmethod
+    def backward(ctx, dout):
+        nmap, mode, arg = ctx.geom
+        return get_backend().nbr_backward(mode, dout.contiguous(), nmap, arg=arg), None, None
+
+
+class NeighborSumFn(torch.autograd.Function):
+    """out [N, C] = sum_j w[n, j] * x[idx[n, j]] over the valid slots (rows as held, w [N, k] in the row order of the record's
+    idx_held), one fmaf per slot.  Gradients: to x through the record's table (skipped for a frozen x, the chunk list is then
+    never built), to w one dot product per slot (skipped for frozen weights)."""
+
+    @staticmethod
+    def forward(ctx, x, w, nmap):
+        x, w = x.contiguous(), w.contiguous()
+        ctx.nmap = nmap
+        ctx.save_for_backward(x if ctx.needs_input_grad[1] else None, w if ctx.needs_input_grad[0] else None)
+        return get_backend().nbr_wsum_forward(x, nmap, w)
+
+    @staticmethod
+    def backward(ctx, dout):
+        x, w = ctx.saved_tensors
+        be, nmap, dout = get_backend(), ctx.nmap, dout.contiguous()
+        dx = be.nbr_backward(NBR_WEIGHTED, dout, nmap, w=w) if ctx.needs_input_grad[0] else None
+        dw = be.nbr_wsum_backward_w(dout, x, nmap) if ctx.needs_input_grad[1] else None
+        return dx, dw, None
+
+
+def _nbr_input(x, nmap, name):
+    """-> the rows of x as held [V, C], after the record has refused an x it was not made for"""
+    if not isinstance(nmap, NeighbourGroup):
+        raise TypeError(f"{name}: nmap must be a NeighborMap (knn_map or NeighborMap.from_index), got {type(nmap).__name__}")
+    if torch.is_tensor(x):
+        support, rows = (None, None), x
+        if x.dim() != 2:
+            raise ValueError(f"{name}: plain features must be [V, C], got {list(x.shape)}")
+    elif hasattr(x, "coordinate_manager"):
+        support, rows = (x.coordinate_manager, x.tensor_stride), x._raw()
+    elif hasattr(x, "_shared"):
+        support, rows = (x._shared, None), x._F
+    else:
+        raise TypeError(f"{name}: x must be a SparseTensor, a TensorField or a float tensor [V, C], got {type(x).__name__}")
+    nmap.check(support, rows.size(0), rows.device)
+    if rows.dtype in (torch.float16, torch.bfloat16) or not rows.is_floating_point():
+        raise NotImplementedError(f"{name}: {rows.dtype} rows (float32; float64 on the CPU path)")
+    if rows.is_cuda:
+        if rows.dtype != torch.float32:
+            raise NotImplementedError(f"{name}: {rows.dtype} rows on the device (float32)")
+        if not hasattr(get_backend(), "nbr_pool_forward"):
+            raise NotImplementedError(f"{name} on device tensors needs the HIP backend (ms3d_nbr_pool_forward)")
+    return rows
+
+
+def _nbr_result(out, nmap):
+    return out.view(*nmap.lead, out.size(1)) if nmap.wrap is None else nmap.wrap(out)
+
+
+def _nbr_gathered(rows, nmap):
+    """the CPU path's [N, k, C] gather with the invalid slots zeroed, and the mask [N, k]"""
+    ok = nmap.idx_held >= 0
+    if nmap.V == 0:
+        return (rows.sum() * 0).expand(nmap.N, nmap.k, rows.size(1)), ok
+    g = rows[nmap.idx_held.clamp(min=0)]
+    return torch.where(ok.unsqueeze(-1), g, torch.zeros((), dtype=g.dtype, device=g.device)), ok
+
+
+def neighbor_pool(x, nmap, mode="max"):
+    """max | avg | sum of x's rows over the neighbours of every query of nmap: the rules are in the package docstring."""
+    name = "neighbor_pool"
+    if mode not in NBR_MODES:
+        raise ValueError(f"{name}: mode must be 'max', 'avg' or 'sum', got {mode!r}")
+    rows = _nbr_input(x, nmap, name)
+    if rows.is_cuda:
+        if nmap.N == 0 or nmap.V == 0:           # no launch on an empty grid; x stays in the graph, its gradient is zeros
+            return _nbr_result((rows.sum() * 0).expand(nmap.N, rows.size(1)), nmap)
+        return _nbr_result(NeighborPoolFn.apply(rows, nmap, NBR_MODES[mode]), nmap)
+    g, ok = _nbr_gathered(rows, nmap)
+    acc = rows.new_zeros((nmap.N, rows.size(1)))
+    seen = torch.zeros((nmap.N, 1), dtype=torch.bool)
+    for j in range(nmap.k):                      # the chain in ascending slot; an invalid slot adds +0, which changes nothing
+        if mode == "max":
+            take = ok[:, j:j + 1] & (~seen | (g[:, j] > acc))
+            acc = torch.where(take, g[:, j], acc)
+            seen = seen | ok[:, j:j + 1]
+        else:
+            acc = acc + g[:, j]
+    if mode == "avg":
+        cnt = nmap.valid.to(rows.dtype).view(-1, 1)
+        acc = torch.where(cnt > 0, acc / cnt.clamp(min=1), acc)
+    return _nbr_result(acc, nmap)
+
+
+def neighbor_sum(x, nmap, weights):
+    """sum_j weights[n, j] * x[idx[n, j]] over the valid slots; weights float32 [..., k], differentiable."""
+    name = "neighbor_sum"
+    rows = _nbr_input(x, nmap, name)
+    if not torch.is_tensor(weights) or not weights.is_floating_point():
+        raise ValueError(f"{name}: weights must be a float tensor {list(nmap.lead) + [nmap.k]}")
+    if tuple(weights.shape) != nmap.lead + (nmap.k,):
+        if weights.dim() == len(nmap.lead) + 2 and tuple(weights.shape[:-1]) == nmap.lead + (nmap.k,):
+            raise NotImplementedError(f"{name}: per-head or per-channel weights {list(weights.shape)}: one weight per slot, "
+                                      f"{list(nmap.lead) + [nmap.k]}")
+        raise ValueError(f"{name}: weights must have the shape of the index, {list(nmap.lead) + [nmap.k]}, got "
+                         f"{list(weights.shape)}")
+    if weights.dtype != rows.dtype or weights.device != rows.device:
+        raise ValueError(f"{name}: weights are {weights.dtype} on {weights.device}, the rows {rows.dtype} on {rows.device}")
+    w = weights.reshape(nmap.N, nmap.k)
+    if nmap.row_perm is not None:                # the caller's query rows -> the order the target set holds them in
+        w = PermuteRowsFn.apply(w, *nmap.row_perm)
+    if rows.is_cuda:
+        if nmap.N == 0 or nmap.V == 0:
+            zero = (rows.sum() + w.sum()) * 0    # keeps both inputs in the graph: their gradients are zeros of the right shape
+            return _nbr_result(zero.expand(nmap.N, rows.size(1)), nmap)
+        return _nbr_result(NeighborSumFn.apply(rows, w, nmap), nmap)
+    g, ok = _nbr_gathered(rows, nmap)
+    w = torch.where(ok, w, torch.zeros((), dtype=w.dtype))             # the weight of an invalid slot is never read
+    acc = rows.new_zeros((nmap.N, rows.size(1)))
+    for j in range(nmap.k):
+        acc = acc + w[:, j:j + 1] * g[:, j]
+    return _nbr_result(acc, nmap)
+
+
+def knn_interpolate(x, nmap, eps=1e-8):
+    """inverse-distance interpolation: r = 1 / (float32(d2) + eps), w = r / sum_j r over the valid slots, then neighbor_sum.
+    The weights are plumbing: not differentiable."""
+    name = "knn_interpolate"
+    if not isinstance(nmap, NeighbourGroup):
+        raise TypeError(f"{name}: nmap must be a NeighborMap, got {type(nmap).__name__}")
+    if nmap.d2 is None:
+        raise ValueError(f"{name}: the map holds no distances (d2)")
+    rows = _nbr_input(x, nmap, name)
+    with torch.no_grad():
+        ok = nmap.idx >= 0
+        r = 1.0 / (nmap.d2.to(torch.float32) + eps)
+        r = torch.where(ok, r, torch.zeros((), dtype=torch.float32, device=r.device))
+        w = torch.where(ok, r / r.sum(-1, keepdim=True), r).to(rows.dtype)
+    return neighbor_sum(x, nmap, w)
 
 
 class DenseScatterFn(torch.autograd.Function):

@@ -18,7 +18,7 @@ import torch.nn as nn
 from ..backend import get_backend
 from . import functional as Fn
 from .tensor import SparseTensor, CoordinateMapKey, check_geometry, union_op, to_sparse, to_sparse_all, target_key
-from .tensor import KernelGenerator
+from .tensor import KernelGenerator, knn_map
 
 
 def _layer_geometry(layer, kernel_size, stride, dilation, kernel_generator, expand_coordinates=False):
@@ -1027,6 +1027,50 @@ class MinkowskiInterpolation(nn.Module):
         if self.return_weights:
             out.append(weights)
         return out[0] if len(out) == 1 else tuple(out)
+
+
+class MinkowskiKNNPooling(nn.Module):
+    """forward(x, queries=None, nmap=None): max | avg | sum of x's rows over the k nearest rows of every query's sample
+    (ME.neighbor_pool over ME.knn_map(x, k, queries)) -- the "down" block of an FPS + kNN network.  queries as knn_query takes
+    them; the result lives on the target of the map: x's own set, y's set, or a plain [B, M, C] tensor for picks.  nmap: a
+    NeighborMap made for the same x and queries, shared by every layer over one graph (its k wins).  No parameters.  An engine
+    extra."""
+
+    def __init__(self, k, mode="max"):
+        super().__init__()
+        if isinstance(k, bool) or not isinstance(k, int) or k < 1:
+            raise ValueError(f"{type(self).__name__}: k must be a Python int >= 1, got {k!r}")
+        if mode not in ("max", "avg", "sum"):
+            raise ValueError(f"{type(self).__name__}: mode must be 'max', 'avg' or 'sum', got {mode!r}")
+        self.k, self.mode = k, mode
+
+    def forward(self, x, queries=None, nmap=None):
+        if nmap is None:
+            nmap = knn_map(x, self.k, queries)
+        return Fn.neighbor_pool(x, nmap, self.mode)
+
+    def extra_repr(self):
+        return f"k={self.k}, mode={self.mode!r}"
+
+
+class MinkowskiKNNInterpolation(nn.Module):
+    """forward(x, y, nmap=None): x's features carried onto y's coordinate set or points by inverse-distance weights over the k
+    nearest rows of x in every row's sample (ME.knn_interpolate over ME.knn_map(x, k, y)) -- the "up" block of an FPS + kNN
+    network.  nmap must be knn_map(x, k, y) when given.  No parameters.  An engine extra."""
+
+    def __init__(self, k=3, eps=1e-8):
+        super().__init__()
+        if isinstance(k, bool) or not isinstance(k, int) or k < 1:
+            raise ValueError(f"{type(self).__name__}: k must be a Python int >= 1, got {k!r}")
+        self.k, self.eps = k, float(eps)
+
+    def forward(self, x, y, nmap=None):
+        if nmap is None:
+            nmap = knn_map(x, self.k, y)
+        return Fn.knn_interpolate(x, nmap, self.eps)
+
+    def extra_repr(self):
+        return f"k={self.k}, eps={self.eps}"
 
 
 class _GlobalPoolBase(nn.Module):

@@ -15,7 +15,7 @@ import os
 import numpy as np
 import torch
 
-from ..backend import BatchGroup, get_backend
+from ..backend import BatchGroup, NeighbourGroup, get_backend
 from . import functional as Fn
 
 
@@ -1717,8 +1717,8 @@ def knn_query(x, k, queries=None, max_squared_distance=None):
     atomics, no waiting between workgroups.  The queries are packed and the results put back into the caller's order by torch
     gathers.  CPU tensors: the same rule as a torch expression (_knn_torch), at most 2^22 (query, row) pairs at a time.  The
     index is not differentiable: gradients reach x.F through x.F[idx].
-    Out of scope: spatial acceleration (a grid or hash walk), a fused neighbour gather, mixed voxel / point queries, other
-    metrics, a different k per query, k above 64, float16 or float64 distances, gradients with respect to the coordinates,
+    Out of scope: spatial acceleration (a grid or hash walk), mixed voxel / point queries, other metrics (pooling, weighted sums
+    and interpolation over the index: knn_map with neighbor_pool / neighbor_sum / knn_interpolate), a different k per query, k above 64, float16 or float64 distances, gradients with respect to the coordinates,
     the first-k-inside-the-radius order of a ball query (the cap keeps the nearest-first order)."""
     name = "knn_query"
     if isinstance(k, bool) or not isinstance(k, int) or not 1 <= k <= _KNN_MAX_K:
@@ -1813,6 +1813,46 @@ def knn_query(x, k, queries=None, max_squared_distance=None):
     if shape is not None:
         idx, d2 = idx.view(*shape, k), d2.view(*shape, k)
     return idx, d2
+
+
+NeighborMap = NeighbourGroup             # the public name of the record (backend.NeighbourGroup)
+
+
+def _nbr_set(t):
+    """what a NeighborMap remembers of a SparseTensor / TensorField: (the token its check compares, features as held -> a
+    tensor of that set, its BatchGroup)"""
+    if isinstance(t, SparseTensor):
+        cm, ts = t.coordinate_manager, t.tensor_stride
+        return (cm, ts), lambda feats: SparseTensor(feats, coordinate_manager=cm, tensor_stride=ts), cm.batch_group(ts)
+    points, mode, shared = t._C, t.quantization_mode, t._shared
+
+    def like(feats):                     # TensorField._like without keeping t's features alive
+        f = TensorField.__new__(TensorField)
+        f._F, f._C, f.quantization_mode, f._shared = feats, points, mode, shared
+        return f
+    return (shared, None), like, t._batch_group()
+
+
+def knn_map(x, k, queries=None, max_squared_distance=None):
+    """knn_query(x, k, queries, max_squared_distance) wrapped as a NeighborMap: the record ME.neighbor_pool, neighbor_sum and
+    knn_interpolate read.  It remembers the support set (x's coordinate set or field) and the target the results live on:
+    x's own set (queries=None), y's set (a SparseTensor / TensorField y), or none -- plain [B, M, C] results -- for an int64
+    [B, M] tensor of picks.  The index is translated into the rows as both sets HOLD them here, once, by torch gathers; the
+    transposed table of the backward is made on first use and kept, so every layer over one graph shares it.  Arguments,
+    refusals and host reads are knn_query's."""
+    idx, d2 = knn_query(x, k, queries, max_squared_distance)
+    support, wrap, group = _nbr_set(x)
+    row_map = row_held_of = None
+    if queries is None:
+        target = group
+    elif torch.is_tensor(queries):
+        target, wrap = None, None
+    else:
+        _, wrap, target = _nbr_set(queries)
+    if target is not None and target.row_map is not None:
+        row_map, row_held_of = target.row_map, target.held_of
+    return NeighbourGroup(idx, group.V, d2, held_of=group.held_of, row_map=row_map, row_held_of=row_held_of, support=support,
+                          wrap=wrap)
 
 
 def _dense_input(x, format, device):

@@ -265,6 +265,121 @@ class BatchGroup:
         return held, inside
 
 
+NBR_MAX_K = 254                          # a slot number fits a byte with 255 free (the arg of a neighbour max)
+NBR_MODES = {"max": 0, "avg": 1, "sum": 2}
+NBR_WEIGHTED = 3
+
+
+class NeighbourGroup:
+    """A neighbour index -- what knn_query returns, or a hand-made one -- as every neighbour op reads it (ME.NeighborMap).
+    Built once, validated once, shared by every op and every layer that uses the same graph:
+      idx, d2       as the caller gave them, in caller numbering, [..., k]; d2 may be None
+      N, k, V       queries (the product of the leading shape), slots (1 <= k <= 254), support rows
+      idx_held      int64 [N, k]  the same index in the numbering the kernels use: its VALUES are held rows of the support set
+                                  (through the support's BatchGroup.held_of where the two orders differ), its ROWS are in the
+                                  held order of the target set; translated once, by torch gathers; any negative value = no
+                                  neighbour
+      valid         int32 [N]     the slots >= 0 of every query
+      support       what the index points into, compared by check(); wrap: features [N, C] in the target's held order -> the
+                    op's result (None: a plain tensor [..., C]); row_perm: (held -> caller, caller -> held) rows of the target
+                    where the two orders differ, else None
+    Made on first use and kept: the transposed table (entry_sorted int64 [E], seg_start int32 [V + 1]: the entries e = n * k + j
+    with idx_held >= 0 grouped by support row, ascending e inside a row -- in the caller's numbering of the queries where the
+    target holds them in another order -- one stable sort, as CoordinateManager.interpolation_map builds its group) and, only when a feature backward runs on the device, the chunk list (chunk_start int32
+    [V + 1], n_chunks: the cut of the rows that have more than ms3d_nbr_chunk_entries() entries -- one host read)."""
+
+    def __init__(self, idx, V, d2=None, held_of=None, row_map=None, row_held_of=None, support=(None, None), wrap=None):
+        assert idx.dtype == torch.int64 and idx.dim() >= 1 and 1 <= idx.size(-1) <= NBR_MAX_K
+        assert d2 is None or tuple(d2.shape) == tuple(idx.shape)
+        self.idx, self.d2, self.V, self.k, self.device = idx, d2, int(V), idx.size(-1), idx.device
+        self.lead = tuple(idx.shape[:-1])
+        self.N = int(np.prod(self.lead, dtype=np.int64))
+        flat = idx.reshape(self.N, self.k)
+        if held_of is not None and self.V > 0:
+            flat = torch.where(flat >= 0, held_of[flat.clamp(min=0)], flat)
+        self.row_perm = None
+        if row_map is not None:
+            assert row_map.numel() == self.N and row_held_of is not None
+            self.row_perm = (row_map.long(), row_held_of)
+            flat = flat[self.row_perm[0]]
+        self.idx_held = flat.contiguous()
+        self.valid = (self.idx_held >= 0).sum(1).to(torch.int32)
+        self.support, self.wrap = support, wrap
+
+    @classmethod
+    def from_index(cls, idx, num_rows, d2=None):
+        """a hand-made index over plain feature rows [num_rows, C]: idx int64 [..., k], a negative value = no neighbour, in
+        any slot.  Any other dtype, a value >= num_rows or k > 254 is a ValueError (one host read, here, once)."""
+        if not torch.is_tensor(idx) or idx.dtype != torch.int64 or idx.dim() < 1:
+            raise ValueError(f"NeighborMap.from_index: idx must be an int64 tensor [..., k], got "
+                             f"{getattr(idx, 'dtype', type(idx).__name__)}")
+        if isinstance(num_rows, bool) or not isinstance(num_rows, int) or num_rows < 0:
+            raise ValueError(f"NeighborMap.from_index: num_rows must be a Python int >= 0, got {num_rows!r}")
+        k = idx.size(-1)
+        if not 1 <= k <= NBR_MAX_K:
+            raise ValueError(f"NeighborMap.from_index: k = {k} is outside 1 .. {NBR_MAX_K} (a slot number must fit a byte)")
+        if d2 is not None and (not torch.is_tensor(d2) or tuple(d2.shape) != tuple(idx.shape)):
+            raise ValueError(f"NeighborMap.from_index: d2 must have the shape of idx, {list(idx.shape)}")
+        if idx.numel() and int(idx.max()) >= num_rows:
+            raise ValueError(f"NeighborMap.from_index: idx holds {int(idx.max())}, which is no row of {num_rows}")
+        return cls(idx, num_rows, None if d2 is None else d2.to(idx.device))
+
+    def check(self, support, V, device):
+        """refuses features of another set, another number of rows or another device, on the host: a stale record never
+        reaches a kernel"""
+        mine = self.support
+        if mine[0] is not support[0] or mine[1] != support[1]:
+            raise ValueError("this NeighborMap was made for another set than x: a map made by knn_map(x, ...) serves that x's "
+                             "coordinate set or field, a map made by from_index plain feature rows [num_rows, C]")
+        if V != self.V or device != self.device:
+            raise ValueError(f"a NeighborMap over {self.V} rows on {self.device} for {V} rows on {device}")
+
+    @functools.cached_property
+    def table(self):
+        """(entry_sorted, seg_start).  The order inside a row is ascending in the CALLER's numbering of the queries, so the
+        sums of the backward do not depend on how a sorted manager holds the target's rows; the values are entry numbers into
+        idx_held.  Without row_perm the two numberings are one."""
+        rows = self.idx_held if self.row_perm is None else self.idx_held[self.row_perm[1]]     # query rows in caller order
+        flat = rows.reshape(-1)
+        entries = torch.nonzero(flat >= 0).view(-1)
+        of_row = flat[entries]
+        entry_sorted = entries[torch.sort(of_row, stable=True).indices]
+        if self.row_perm is not None:
+            n = torch.div(entry_sorted, self.k, rounding_mode="floor")
+            entry_sorted = self.row_perm[1][n] * self.k + (entry_sorted - n * self.k)
+        seg_start = torch.zeros(self.V + 1, dtype=torch.int32, device=self.device)
+        seg_start[1:] = torch.cumsum(torch.bincount(of_row, minlength=self.V), 0)
+        return entry_sorted.contiguous(), seg_start
+
+    @property
+    def entry_sorted(self):
+        return self.table[0]
+
+    @property
+    def seg_start(self):
+        return self.table[1]
+
+    @functools.cached_property
+    def chunks(self):
+        """(chunk_start int32 [V + 1], n_chunks): per row its ceil(entries / T) chunks when it has more than one, else 0, as
+        running sums; T = ms3d_nbr_chunk_entries().  One host read."""
+        T = get_backend().nbr_chunk_entries()
+        seg = self.seg_start.long()
+        per_row = (seg[1:] - seg[:-1] + (T - 1)) // T
+        per_row = torch.where(per_row > 1, per_row, torch.zeros_like(per_row))
+        chunk_start = torch.zeros(self.V + 1, dtype=torch.int32, device=self.device)
+        chunk_start[1:] = torch.cumsum(per_row, 0)
+        return chunk_start, int(chunk_start[-1])
+
+    @property
+    def chunk_start(self):
+        return self.chunks[0]
+
+    @property
+    def n_chunks(self):
+        return self.chunks[1]
+
+
 class _Workspace:
     """grow-only device scratch, one per purpose (avoids hipMalloc on the hot path)"""
 
@@ -1586,6 +1701,76 @@ class _HipEngine:
                                            _lib.ptr(out), _lib.ptr(d2), _lib.ptr(ws), C.c_size_t(ws.numel()),
                                            _lib.stream_handle()), name)
         return out, d2
+
+    # ---- pooling and weighted sums over a neighbour index (csrc/neighbor.hip); group: the NeighbourGroup of the index
+    def nbr_chunk_entries(self):
+        return int(self.lib.ms3d_nbr_chunk_entries())
+
+    @staticmethod
+    def _nbr_rows(t, rows, what):
+        assert t.is_cuda and t.dtype == torch.float32 and t.dim() == 2 and t.size(0) == rows and t.is_contiguous(), what
+
+    def nbr_pool_forward(self, mode, x, group):
+        """-> (out [N, C], arg uint8 [N, C] for max, else None): mode 0 max, 1 avg, 2 sum over the valid slots of every query,
+        ascending slot; x [V, C] as held"""
+        self._nbr_rows(x, group.V, "x")
+        group.check(group.support, x.size(0), x.device)
+        n, c = group.N, x.size(1)
+        out = torch.empty((n, c), dtype=torch.float32, device=x.device)
+        arg = torch.empty((n, c), dtype=torch.uint8, device=x.device) if mode == 0 else None
+        _lib.check(self.lib.ms3d_nbr_pool_forward(int(mode), _lib.ptr(x), C.c_long(group.V), _lib.ptr(group.idx_held), C.c_long(n),
+                                                  int(group.k), int(c), _lib.ptr(out), _lib.ptr(arg), _lib.stream_handle()),
+                   "ms3d_nbr_pool_forward")
+        return out, arg
+
+    def nbr_wsum_forward(self, x, group, w):
+        """out [N, C] = sum over the valid slots of w[n, j] * x[idx[n, j]], one fmaf each, ascending slot; w float32 [N, k] in
+        the row order of idx_held"""
+        self._nbr_rows(x, group.V, "x")
+        self._nbr_rows(w, group.N, "w")
+        assert w.size(1) == group.k
+        group.check(group.support, x.size(0), x.device)
+        out = torch.empty((group.N, x.size(1)), dtype=torch.float32, device=x.device)
+        _lib.check(self.lib.ms3d_nbr_wsum_forward(_lib.ptr(x), C.c_long(group.V), _lib.ptr(group.idx_held), _lib.ptr(w),
+                                                  C.c_long(group.N), int(group.k), int(x.size(1)), _lib.ptr(out),
+                                                  _lib.stream_handle()), "ms3d_nbr_wsum_forward")
+        return out
+
+    def nbr_backward(self, mode, dout, group, w=None, arg=None):
+        """dx [V, C]: per support row the sum over its entries, ascending entry, of dout (2 sum), dout / valid (1 avg), w * dout
+        (3 weighted) or dout where arg names the entry's slot (0 max); rows of more than nbr_chunk_entries() entries through
+        chunk partials (group.chunks)"""
+        self._nbr_rows(dout, group.N, "dout")
+        c, dev = dout.size(1), dout.device
+        assert group.device == dev
+        if mode == NBR_WEIGHTED:
+            self._nbr_rows(w, group.N, "w")
+            assert w.size(1) == group.k
+        if mode == 0:
+            assert arg.dtype == torch.uint8 and arg.is_contiguous() and tuple(arg.shape) == (group.N, c) and arg.device == dev
+        entry_sorted, seg_start = group.table
+        chunk_start, n_chunks = group.chunks
+        dx = torch.empty((group.V, c), dtype=torch.float32, device=dev)
+        need = self.lib.ms3d_nbr_ws_bytes(C.c_long(n_chunks), int(c))
+        ws = self.ws.get("nbr", need, dev) if need else None
+        _lib.check(self.lib.ms3d_nbr_backward(int(mode), _lib.ptr(dout), _lib.ptr(w if mode == NBR_WEIGHTED else None),
+                                              _lib.ptr(arg if mode == 0 else None), _lib.ptr(group.valid if mode == 1 else None),
+                                              _lib.ptr(entry_sorted), _lib.ptr(seg_start), _lib.ptr(chunk_start),
+                                              C.c_long(n_chunks), C.c_long(group.V), C.c_long(group.N), int(group.k), int(c),
+                                              _lib.ptr(dx), _lib.ptr(ws), C.c_size_t(ws.numel() if need else 0),
+                                              _lib.stream_handle()), "ms3d_nbr_backward")
+        return dx
+
+    def nbr_wsum_backward_w(self, dout, x, group):
+        """dw [N, k] = <dout[n], x[idx[n, j]]>, 0 for an invalid slot"""
+        self._nbr_rows(dout, group.N, "dout")
+        self._nbr_rows(x, group.V, "x")
+        assert dout.size(1) == x.size(1)
+        dw = torch.empty((group.N, group.k), dtype=torch.float32, device=dout.device)
+        _lib.check(self.lib.ms3d_nbr_wsum_backward_w(_lib.ptr(dout), _lib.ptr(x), _lib.ptr(group.idx_held), C.c_long(group.N),
+                                                     int(group.k), int(x.size(1)), _lib.ptr(dw), _lib.stream_handle()),
+                   "ms3d_nbr_wsum_backward_w")
+        return dw
 
     # ---- instance normalisation over the batch grouping of a coordinate set (csrc/inorm.hip)
     def inorm_forward(self, x, group, eps, weight, bias):

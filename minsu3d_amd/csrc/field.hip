@@ -13,32 +13,17 @@
 // Layout as pool.hip: consecutive lanes take consecutive channels of one row (16 bytes per lane when C % 4 == 0 and the rows
 // are aligned, else one float), the table entry of a row is the same word for all of its lanes.  A voxel that holds
 // thousands of points is walked serially by its thread group: untuned.
-#include "common.h"
+#include "rows.h"
 #include "../../include/minsu3d_hip.h"
 
 namespace {
 
+using ms3d_rows::grid_of;
+using ms3d_rows::load_row;
+using ms3d_rows::store_row;
+using ms3d_rows::vec4;
+
 enum { RED_AVG = 0, RED_SUM = 1, RED_MAX = 2 };
-
-template <int VEC>
-__device__ __forceinline__ void load_row(const float *__restrict__ p, size_t row, int C, int cv, float (&v)[VEC])
-{
-    if constexpr (VEC == 4) {
-        const float4 r = reinterpret_cast<const float4 *>(p + row * C)[cv];
-        v[0] = r.x; v[1] = r.y; v[2] = r.z; v[3] = r.w;
-    } else {
-        v[0] = p[row * C + cv];
-    }
-}
-
-template <int VEC>
-__device__ __forceinline__ void store_row(float *__restrict__ p, size_t row, int C, int cv, const float (&v)[VEC])
-{
-    if constexpr (VEC == 4)
-        reinterpret_cast<float4 *>(p + row * C)[cv] = make_float4(v[0], v[1], v[2], v[3]);
-    else
-        p[row * C + cv] = v[0];
-}
 
 // VEC = floats per lane; CV = C / VEC lanes per row
 template <int VEC>
@@ -162,20 +147,6 @@ __global__ __launch_bounds__(256) void field_reduce_backward_kernel(const float 
         for (int c = 0; c < VEC; c++) g[c] = (w[c] == n) ? g[c] : 0.f;
     }
     store_row<VEC>(dfeat, (size_t)n, C, cv, g);
-}
-
-bool vec4(int C, const void *a, const void *b, const void *c = nullptr)
-{
-    return C % 4 == 0 && (((uintptr_t)a | (uintptr_t)b | (uintptr_t)c) & 15) == 0;
-}
-
-// grid of one thread per (row, lane of the row); false when it does not fit a launch
-bool grid_of(long rows, int CV, unsigned *blocks)
-{
-    const long b = (rows * CV + 255) / 256;
-    if (b > 0x7fffffffL) return false;
-    *blocks = (unsigned)b;
-    return true;
 }
 
 }  // namespace
