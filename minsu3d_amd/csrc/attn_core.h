@@ -36,17 +36,6 @@ int group_of(int D, int VEC)
     return G;
 }
 
-// every pointer 16-byte aligned; NULL counts as aligned, so an output that is not asked for does not decide the route
-template <typename... P> bool aligned16(const P *...p) { return ((... | (uintptr_t)p) & 15) == 0; }
-
-// The two instantiations of a kernel template, one argument list: VEC = 4 when v4, else 1; returns the launch's error.
-#define ATTN_LAUNCH(v4, kernel, grid, threads, lds, stream, ...)                      \
-    do {                                                                              \
-        if (v4) kernel<4><<<grid, threads, lds, stream>>>(__VA_ARGS__);               \
-        else kernel<1><<<grid, threads, lds, stream>>>(__VA_ARGS__);                  \
-        MS3D_LAUNCH_CHECK();                                                          \
-    } while (0)
-
 // the slice of a head this lane holds: x[it * VEC + j] = p[(it * G + l) * VEC + j], zero past D or with the load off
 template <int VEC>
 __device__ __forceinline__ void load_slice(const float *__restrict__ p, int l, int G, int D, bool on, float (&x)[Lane<VEC>::N])

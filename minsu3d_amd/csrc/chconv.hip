@@ -11,15 +11,16 @@
 //   backward-weight  dW[k, c] = sum_o in[nbr[k][o], c] * dout[o, c]                two stages: a [K, C] partial per fixed run
 //                                                                                  of CHCONV_WGRAD_ROWS output rows, then the
 //                                                                                  partials summed in ascending part order
-// Layout (as csrc/pool.hip): consecutive lanes take consecutive channels of one row, 16 bytes per lane when C % 4 == 0 and
-// the rows are 16-byte aligned (scalar otherwise); the table entry of (k, row) is the same word for all lanes of a row.
+// Layout: csrc/rows.h, with the rows cut into channel tiles, so a lane's accesses are the header's pointer forms.
 // Channels are cut into tiles of at most 64 (blockIdx.y), so that the weights of a tile ([K <= 254][64] floats <= 64 KiB)
 // always fit the LDS of a forward workgroup and the staged dout rows of a run ([128][64] floats = 32 KiB) that of a
 // backward-weight workgroup, whatever C is.
-#include "common.h"
+#include "rows.h"
 #include "../../include/minsu3d_hip.h"
 
 namespace {
+
+using namespace ms3d_rows;
 
 constexpr int CHCONV_MAX_K = 254;        // the pooling kernels' limit (their uint8 argmax); the same tables feed both
 constexpr int CHCONV_TILE_C = 64;        // channels per tile at most
@@ -37,22 +38,6 @@ Tiling tiling_of(int C, int VEC)
     t.TC = (per + VEC - 1) / VEC * VEC;
     t.LPR = t.TC / VEC;
     return t;
-}
-
-bool rows_vec4(int C, const void *a, const void *b)
-{
-    return C % 4 == 0 && ((uintptr_t)a & 15) == 0 && ((uintptr_t)b & 15) == 0;
-}
-
-template <int VEC>
-__device__ __forceinline__ void load_row(const float *__restrict__ p, float (&v)[VEC])
-{
-    if constexpr (VEC == 4) {
-        const float4 r = *reinterpret_cast<const float4 *>(p);
-        v[0] = r.x; v[1] = r.y; v[2] = r.z; v[3] = r.w;
-    } else {
-        v[0] = *p;
-    }
 }
 
 // One workgroup: the channel tile blockIdx.y and CHCONV_FWD_PASSES * (256 / LPR) consecutive output rows.  The tile's
@@ -96,21 +81,18 @@ __global__ __launch_bounds__(256) void chconv_forward_kernel(const float *__rest
             for (int u = 0; u < 4; u++) {
 #pragma unroll
                 for (int j = 0; j < VEC; j++) v[u][j] = 0.f;
-                if (idx[u] >= 0) load_row<VEC>(in + (size_t)idx[u] * C + c0 + lc, v[u]);
+                if (idx[u] >= 0) load_vec<VEC>(in + (size_t)idx[u] * C + c0 + lc, v[u]);
             }
 #pragma unroll
             for (int u = 0; u < 4; u++) {
                 if (idx[u] < 0) continue;
                 float wk[VEC];
-                load_row<VEC>(s_w + (k0 + u) * TC + lc, wk);
+                load_vec<VEC>(s_w + (k0 + u) * TC + lc, wk);
 #pragma unroll
                 for (int j = 0; j < VEC; j++) acc[j] = fmaf(wk[j], v[u][j], acc[j]);
             }
         }
-        if constexpr (VEC == 4)
-            *reinterpret_cast<float4 *>(out + (size_t)o * C + c0 + lc) = make_float4(acc[0], acc[1], acc[2], acc[3]);
-        else
-            out[(size_t)o * C + c0 + lc] = acc[0];
+        store_vec<VEC>(out + (size_t)o * C + c0 + lc, acc);
     }
 }
 
@@ -160,13 +142,13 @@ __global__ __launch_bounds__(256) void chconv_wgrad_partial_kernel(const float *
                 for (int u = 0; u < 4; u++) {
 #pragma unroll
                     for (int j = 0; j < VEC; j++) v[u][j] = 0.f;
-                    if (idx[u] >= 0) load_row<VEC>(in + (size_t)idx[u] * C + c0 + lc, v[u]);
+                    if (idx[u] >= 0) load_vec<VEC>(in + (size_t)idx[u] * C + c0 + lc, v[u]);
                 }
 #pragma unroll
                 for (int u = 0; u < 4; u++) {
                     if (idx[u] < 0) continue;
                     float d[VEC];
-                    load_row<VEC>(s_d + (chunk * 64 + jr[u]) * TC + lc, d);
+                    load_vec<VEC>(s_d + (chunk * 64 + jr[u]) * TC + lc, d);
 #pragma unroll
                     for (int j = 0; j < VEC; j++) acc[j] = fmaf(v[u][j], d[j], acc[j]);
                 }
@@ -180,12 +162,7 @@ __global__ __launch_bounds__(256) void chconv_wgrad_partial_kernel(const float *
                 if (g < s) acc[j] += t;
             }
         }
-        if (g == 0 && lc < tc) {
-            if constexpr (VEC == 4)
-                *reinterpret_cast<float4 *>(dst + (size_t)k * C + c0 + lc) = make_float4(acc[0], acc[1], acc[2], acc[3]);
-            else
-                dst[(size_t)k * C + c0 + lc] = acc[0];
-        }
+        if (g == 0 && lc < tc) store_vec<VEC>(dst + (size_t)k * C + c0 + lc, acc);
     }
 }
 
@@ -224,16 +201,14 @@ int ms3d_chconv_forward(const float *in, const float *w, const float *bias, cons
     hipStream_t stream = (hipStream_t)stream_;
     if (K < 1 || K > CHCONV_MAX_K || C < 1) return MS3D_E_UNSUPPORTED;
     if (Vout <= 0) return 0;
-    const bool v4 = rows_vec4(C, in, out);
+    const bool v4 = vec4(C, in, out);
     const Tiling t = tiling_of(C, v4 ? 4 : 1);
     const int rows_per_block = CHCONV_FWD_PASSES * (256 / t.LPR);
     const long blocks = ((long)Vout + rows_per_block - 1) / rows_per_block;
     if (blocks > 0x7fffffffL || t.ntiles > 65535) return MS3D_E_UNSUPPORTED;
     const dim3 grid((unsigned)blocks, (unsigned)t.ntiles);
     const size_t lds = sizeof(float) * (size_t)K * t.TC;              // <= 254 * 64 * 4 = 65,024 bytes
-    if (v4) chconv_forward_kernel<4><<<grid, 256, lds, stream>>>(in, w, bias, nbr, Vout, K, C, t.TC, t.LPR, out);
-    else chconv_forward_kernel<1><<<grid, 256, lds, stream>>>(in, w, bias, nbr, Vout, K, C, t.TC, t.LPR, out);
-    MS3D_LAUNCH_CHECK();
+    MS3D_LAUNCH_VEC(v4, chconv_forward_kernel, grid, 256, lds, stream, in, w, bias, nbr, Vout, K, C, t.TC, t.LPR, out);
     return 0;
 }
 
@@ -244,16 +219,14 @@ int ms3d_chconv_backward_weight(const float *in, const float *dout, const int *n
     if (K < 1 || K > CHCONV_MAX_K || C < 1) return MS3D_E_UNSUPPORTED;
     if ((long)K * C > 0x7fffffffL) return MS3D_E_UNSUPPORTED;
     if (Vout <= 0) return 0;                                          // (dW is not written: an empty sum is the caller's zero)
-    const bool v4 = rows_vec4(C, in, dout) && ((uintptr_t)partial_ws & 15) == 0;
+    const bool v4 = vec4(C, in, dout, partial_ws);
     const Tiling t = tiling_of(C, v4 ? 4 : 1);
     if (t.ntiles > 65535) return MS3D_E_UNSUPPORTED;
     int G = 1;                                                        // largest power of two <= 64 / LPR
     while (2 * G * t.LPR <= 64) G *= 2;
     const int parts = ms3d_chconv_wgrad_parts(Vout);
     const dim3 grid((unsigned)parts, (unsigned)t.ntiles);
-    if (v4) chconv_wgrad_partial_kernel<4><<<grid, 256, 0, stream>>>(in, dout, nbr, Vout, K, C, t.TC, t.LPR, G, partial_ws);
-    else chconv_wgrad_partial_kernel<1><<<grid, 256, 0, stream>>>(in, dout, nbr, Vout, K, C, t.TC, t.LPR, G, partial_ws);
-    MS3D_LAUNCH_CHECK();
+    MS3D_LAUNCH_VEC(v4, chconv_wgrad_partial_kernel, grid, 256, 0, stream, in, dout, nbr, Vout, K, C, t.TC, t.LPR, G, partial_ws);
     const int n = K * C;
     chconv_wgrad_reduce_kernel<<<ms3d_divup(n, 256), 256, 0, stream>>>(partial_ws, parts, n, dW);
     MS3D_LAUNCH_CHECK();

@@ -2,6 +2,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <type_traits>
 
 #define MS3D_WAVE 64
 #define MS3D_PL_ROWS 64  // output rows per tile of a pair list (ms3d_kmap_pairlist_build)
@@ -19,6 +20,38 @@
 
 static inline int ms3d_divup(long a, long b) { return (int)((a + b - 1) / b); }
 static inline size_t ms3d_align(size_t x) { return (x + 255) & ~(size_t)255; }
+
+// every pointer 16-byte aligned; NULL counts as aligned, so a pointer that is not asked for does not decide the route
+template <typename... P> static inline bool ms3d_aligned16(const P *...p) { return ((... | (uintptr_t)p) & 15) == 0; }
+
+// f(std::integral_constant<int, M>()) for the M of the list that equals mode; the last of the list when none does (the
+// launcher has checked the range of mode).  The call stands before the recursion so that what f instantiates is emitted in
+// the order of the list.
+template <int M, int... REST, typename F> static inline void ms3d_with_mode(int mode, F f)
+{
+    if (mode == M || sizeof...(REST) == 0) f(std::integral_constant<int, M>());
+    else if constexpr (sizeof...(REST) > 0) ms3d_with_mode<REST...>(mode, f);
+}
+
+// The two instantiations kernel<VEC> of a kernel template, one argument list: VEC = 4 when v4, else 1; returns the
+// launch's error from the calling function.
+#define MS3D_LAUNCH_VEC(v4, kernel, grid, threads, lds, stream, ...)                  \
+    do {                                                                              \
+        if (v4) kernel<4><<<grid, threads, lds, stream>>>(__VA_ARGS__);               \
+        else kernel<1><<<grid, threads, lds, stream>>>(__VA_ARGS__);                  \
+        MS3D_LAUNCH_CHECK();                                                          \
+    } while (0)
+
+// The same for kernel<MODE, VEC>: the instantiation of the run-time mode among the parenthesised list `modes`.
+#define MS3D_LAUNCH_MODE_VEC(modes, mode, v4, kernel, grid, threads, lds, stream, ...)                         \
+    do {                                                                                                       \
+        ms3d_with_mode<MS3D_UNPAREN modes>(mode, [&](auto m_) {                                                \
+            if (v4) kernel<decltype(m_)::value, 4><<<grid, threads, lds, stream>>>(__VA_ARGS__);               \
+            else kernel<decltype(m_)::value, 1><<<grid, threads, lds, stream>>>(__VA_ARGS__);                  \
+        });                                                                                                    \
+        MS3D_LAUNCH_CHECK();                                                                                   \
+    } while (0)
+#define MS3D_UNPAREN(...) __VA_ARGS__
 
 #ifdef __HIPCC__
 __device__ __forceinline__ int lane_id() { return (int)(threadIdx.x & 63); }

@@ -10,30 +10,22 @@
 //   reduce forward    out[v]  = avg | sum | max over the points of voxel v in ascending point index (order / seg_start: a
 //                               stable sort of the point -> voxel map)
 //   reduce backward   dfeat[n] = dvox[inverse[n]] / count | as is | where arg == n
-// Layout as pool.hip: consecutive lanes take consecutive channels of one row (16 bytes per lane when C % 4 == 0 and the rows
-// are aligned, else one float), the table entry of a row is the same word for all of its lanes.  A voxel that holds
-// thousands of points is walked serially by its thread group: untuned.
+// Layout: csrc/rows.h.  A voxel that holds thousands of points is walked serially by its thread group: untuned.
 #include "rows.h"
 #include "../../include/minsu3d_hip.h"
 
 namespace {
 
-using ms3d_rows::grid_of;
-using ms3d_rows::load_row;
-using ms3d_rows::store_row;
-using ms3d_rows::vec4;
+using namespace ms3d_rows;
 
 enum { RED_AVG = 0, RED_SUM = 1, RED_MAX = 2 };
 
-// VEC = floats per lane; CV = C / VEC lanes per row
 template <int VEC>
 __global__ __launch_bounds__(256) void interp_forward_kernel(const float *__restrict__ x, const int *__restrict__ rows,
                                                              const float *__restrict__ weights, int N, int C, int CV,
                                                              float *__restrict__ out)
 {
-    const long t = (long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (t >= (long)N * CV) return;
-    const int n = (int)(t / CV), cv = (int)(t - (long)n * CV);
+    MS3D_ROW_LANE(N, CV, n, cv);
     float acc[VEC];
 #pragma unroll
     for (int c = 0; c < VEC; c++) acc[c] = 0.f;
@@ -56,9 +48,7 @@ __global__ __launch_bounds__(256) void interp_backward_kernel(const float *__res
                                                               const int *__restrict__ seg_start, int Vin, int N, int C, int CV,
                                                               float *__restrict__ din)
 {
-    const long t = (long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (t >= (long)Vin * CV) return;
-    const int v = (int)(t / CV), cv = (int)(t - (long)v * CV);
+    MS3D_ROW_LANE(Vin, CV, v, cv);
     float acc[VEC];
 #pragma unroll
     for (int c = 0; c < VEC; c++) acc[c] = 0.f;
@@ -82,9 +72,7 @@ __global__ __launch_bounds__(256) void field_reduce_kernel(const float *__restri
                                                            const int *__restrict__ seg_start, int V, int C, int CV,
                                                            float *__restrict__ out, int *__restrict__ arg)
 {
-    const long t = (long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (t >= (long)V * CV) return;
-    const int v = (int)(t / CV), cv = (int)(t - (long)v * CV);
+    MS3D_ROW_LANE(V, CV, v, cv);
     float acc[VEC];
     int win[VEC];
 #pragma unroll
@@ -111,12 +99,7 @@ __global__ __launch_bounds__(256) void field_reduce_kernel(const float *__restri
         }
     }
     store_row<VEC>(out, (size_t)v, C, cv, acc);
-    if constexpr (MODE == RED_MAX) {
-        if constexpr (VEC == 4)
-            reinterpret_cast<int4 *>(arg + (size_t)v * C)[cv] = make_int4(win[0], win[1], win[2], win[3]);
-        else
-            arg[(size_t)v * C + cv] = win[0];
-    }
+    if constexpr (MODE == RED_MAX) store_arg<VEC>(arg, (size_t)v, C, cv, win);
 }
 
 template <int MODE, int VEC>
@@ -125,9 +108,7 @@ __global__ __launch_bounds__(256) void field_reduce_backward_kernel(const float 
                                                                     const int *__restrict__ arg, int N, int C, int CV,
                                                                     float *__restrict__ dfeat)
 {
-    const long t = (long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (t >= (long)N * CV) return;
-    const int n = (int)(t / CV), cv = (int)(t - (long)n * CV);
+    MS3D_ROW_LANE(N, CV, n, cv);
     const int v = inverse[n];
     float g[VEC];
     load_row<VEC>(dvox, (size_t)v, C, cv, g);
@@ -137,12 +118,7 @@ __global__ __launch_bounds__(256) void field_reduce_backward_kernel(const float 
         for (int c = 0; c < VEC; c++) g[c] = g[c] / cnt;
     } else if constexpr (MODE == RED_MAX) {
         int w[VEC];
-        if constexpr (VEC == 4) {
-            const int4 a = reinterpret_cast<const int4 *>(arg + (size_t)v * C)[cv];
-            w[0] = a.x; w[1] = a.y; w[2] = a.z; w[3] = a.w;
-        } else {
-            w[0] = arg[(size_t)v * C + cv];
-        }
+        load_arg<VEC>(arg, (size_t)v, C, cv, w);
 #pragma unroll
         for (int c = 0; c < VEC; c++) g[c] = (w[c] == n) ? g[c] : 0.f;
     }
@@ -163,9 +139,7 @@ int ms3d_interp_forward(const float *x, const int *rows, const float *weights, l
     const int CV = v4 ? C / 4 : C;
     unsigned blocks;
     if (!grid_of(N, CV, &blocks)) return MS3D_E_UNSUPPORTED;
-    if (v4) interp_forward_kernel<4><<<blocks, 256, 0, stream>>>(x, rows, weights, (int)N, C, CV, out);
-    else interp_forward_kernel<1><<<blocks, 256, 0, stream>>>(x, rows, weights, (int)N, C, CV, out);
-    MS3D_LAUNCH_CHECK();
+    MS3D_LAUNCH_VEC(v4, interp_forward_kernel, blocks, 256, 0, stream, x, rows, weights, (int)N, C, CV, out);
     return 0;
 }
 
@@ -180,9 +154,8 @@ int ms3d_interp_backward(const float *dout, const float *weights, const long lon
     const int CV = v4 ? C / 4 : C;
     unsigned blocks;
     if (!grid_of(Vin, CV, &blocks)) return MS3D_E_UNSUPPORTED;
-    if (v4) interp_backward_kernel<4><<<blocks, 256, 0, stream>>>(dout, weights, entry_sorted, seg_start, (int)Vin, (int)N, C, CV, din);
-    else interp_backward_kernel<1><<<blocks, 256, 0, stream>>>(dout, weights, entry_sorted, seg_start, (int)Vin, (int)N, C, CV, din);
-    MS3D_LAUNCH_CHECK();
+    MS3D_LAUNCH_VEC(v4, interp_backward_kernel, blocks, 256, 0, stream, dout, weights, entry_sorted, seg_start, (int)Vin, (int)N,
+                    C, CV, din);
     return 0;
 }
 
@@ -197,14 +170,8 @@ int ms3d_field_reduce(int mode, const float *feats, const long long *order, cons
     const int CV = v4 ? C / 4 : C;
     unsigned blocks;
     if (!grid_of(V, CV, &blocks)) return MS3D_E_UNSUPPORTED;
-#define MS3D_FIELD_RED(M)                                                                                              \
-    if (v4) field_reduce_kernel<M, 4><<<blocks, 256, 0, stream>>>(feats, order, seg_start, (int)V, C, CV, out, arg);     \
-    else field_reduce_kernel<M, 1><<<blocks, 256, 0, stream>>>(feats, order, seg_start, (int)V, C, CV, out, arg);
-    if (mode == RED_AVG) { MS3D_FIELD_RED(RED_AVG) }
-    else if (mode == RED_SUM) { MS3D_FIELD_RED(RED_SUM) }
-    else { MS3D_FIELD_RED(RED_MAX) }
-#undef MS3D_FIELD_RED
-    MS3D_LAUNCH_CHECK();
+    MS3D_LAUNCH_MODE_VEC((RED_AVG, RED_SUM, RED_MAX), mode, v4, field_reduce_kernel, blocks, 256, 0, stream, feats, order,
+                         seg_start, (int)V, C, CV, out, arg);
     return 0;
 }
 
@@ -219,14 +186,8 @@ int ms3d_field_reduce_backward(int mode, const float *dvox, const int *inverse, 
     const int CV = v4 ? C / 4 : C;
     unsigned blocks;
     if (!grid_of(N, CV, &blocks)) return MS3D_E_UNSUPPORTED;
-#define MS3D_FIELD_RED_BWD(M)                                                                                                    \
-    if (v4) field_reduce_backward_kernel<M, 4><<<blocks, 256, 0, stream>>>(dvox, inverse, seg_start, arg, (int)N, C, CV, dfeat);   \
-    else field_reduce_backward_kernel<M, 1><<<blocks, 256, 0, stream>>>(dvox, inverse, seg_start, arg, (int)N, C, CV, dfeat);
-    if (mode == RED_AVG) { MS3D_FIELD_RED_BWD(RED_AVG) }
-    else if (mode == RED_SUM) { MS3D_FIELD_RED_BWD(RED_SUM) }
-    else { MS3D_FIELD_RED_BWD(RED_MAX) }
-#undef MS3D_FIELD_RED_BWD
-    MS3D_LAUNCH_CHECK();
+    MS3D_LAUNCH_MODE_VEC((RED_AVG, RED_SUM, RED_MAX), mode, v4, field_reduce_backward_kernel, blocks, 256, 0, stream, dvox,
+                         inverse, seg_start, arg, (int)N, C, CV, dfeat);
     return 0;
 }
 

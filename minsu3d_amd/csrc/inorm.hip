@@ -37,6 +37,7 @@ constexpr int INORM_SLICES = 256;     // slices per segment: a constant of the l
 constexpr int INORM_CW_MAX = 32;      // column lanes (4 channels each) of a pass at most
 constexpr int INORM_UNROLL = 4;       // row loads in flight per lane
 
+// (not the load_row / store_row of csrc/rows.h: guarded four-channel accesses that give both routes the same bits)
 template <bool V4>
 __device__ __forceinline__ void load4(const float *__restrict__ p, int c, int C, float (&v)[4])
 {
@@ -307,8 +308,6 @@ __global__ __launch_bounds__(256) void inorm_apply_kernel(const float *__restric
     store4<V4>(out + (size_t)r * C, c, C, o);
 }
 
-bool aligned16(const void *p) { return ((uintptr_t)p & 15) == 0; }      // (NULL counts as aligned)
-
 // lanes per row CL = ceil(C / 4); column lanes of a workgroup CW = the power of two >= CL, at most INORM_CW_MAX
 void lanes_of(int C, int &CL, int &CW)
 {
@@ -344,7 +343,7 @@ int ms3d_inorm_forward(const float *x, long V, int C, const long long *order, co
     if (V > 0x7fffffffL || blocks > 0x7fffffffL) return MS3D_E_UNSUPPORTED;
     double *partial = (double *)workspace;
     if (((uintptr_t)partial & 7) || ((uintptr_t)mean & 7) || ((uintptr_t)invstd & 7)) return MS3D_E_UNSUPPORTED;
-    const bool v4 = C % 4 == 0 && aligned16(x) && aligned16(y) && aligned16(weight) && aligned16(bias);
+    const bool v4 = C % 4 == 0 && ms3d_aligned16(x, y, weight, bias);
     const dim3 grid(INORM_SLICES, (unsigned)B);
     if (v4)
         inorm_partial_kernel<true, false><<<grid, 256, 0, stream>>>(x, nullptr, nullptr, nullptr, C, CL, CW, order, seg_start,
@@ -382,7 +381,7 @@ int ms3d_inorm_backward(const float *dy, const float *x, long V, int C, const lo
     double *partial = (double *)workspace;
     if (((uintptr_t)partial & 7) || ((uintptr_t)mean & 7) || ((uintptr_t)invstd & 7)) return MS3D_E_UNSUPPORTED;
     double *S = partial + (size_t)B * INORM_SLICES * 2 * C;             // [B][2][C] behind the slice partials
-    const bool v4 = C % 4 == 0 && aligned16(dy) && aligned16(x) && aligned16(weight) && aligned16(dx);
+    const bool v4 = C % 4 == 0 && ms3d_aligned16(dy, x, weight, dx);
     const dim3 grid(INORM_SLICES, (unsigned)B);
     if (v4)
         inorm_partial_kernel<true, true><<<grid, 256, 0, stream>>>(x, dy, mean, invstd, C, CL, CW, order, seg_start, partial);

@@ -239,11 +239,11 @@ int ms3d_kattn_forward(const float *q, const float *k, const float *v, const flo
     if (shape_check(K, H, D)) return MS3D_E_UNSUPPORTED;
     if (Vout <= 0) return 0;
     if (!q || !k || !v || !nbr || !out || !lse) return MS3D_E_UNSUPPORTED;
-    const bool v4 = D % 4 == 0 && aligned16(q, k, v, out);
+    const bool v4 = D % 4 == 0 && ms3d_aligned16(q, k, v, out);
     const int G = group_of(D, v4 ? 4 : 1);
     const long per = KATTN_THREADS / G, blocks = ((long)Vout * H + per - 1) / per;
     if (blocks > 0x7fffffffL) return MS3D_E_UNSUPPORTED;
-    ATTN_LAUNCH(v4, kattn_forward_kernel, (unsigned)blocks, KATTN_THREADS, 0, stream, q, k, v, rel_bias, nbr, Vout, K, H, D, G,
+    MS3D_LAUNCH_VEC(v4, kattn_forward_kernel, (unsigned)blocks, KATTN_THREADS, 0, stream, q, k, v, rel_bias, nbr, Vout, K, H, D, G,
                 scale, out, lse);
     return 0;
 }
@@ -258,7 +258,7 @@ int ms3d_kattn_backward_q(const float *q, const float *k, const float *v, const 
     if (!q || !k || !v || !nbr || !out || !lse || !dout || !delta) return MS3D_E_UNSUPPORTED;
     if (dbias && (!rel_bias || !partial_ws)) return MS3D_E_UNSUPPORTED;
     if (dbias && ws_floats < ms3d_kattn_dbias_ws_floats(Vout, K, H)) return MS3D_E_WORKSPACE;
-    const bool v4 = D % 4 == 0 && aligned16(q, k, v, out, dout, dq);
+    const bool v4 = D % 4 == 0 && ms3d_aligned16(q, k, v, out, dout, dq);
     const int G = group_of(D, v4 ? 4 : 1);
     int GPB = KATTN_THREADS / G;                                      // groups of a workgroup: a power of two
     if (dbias)
@@ -270,7 +270,7 @@ int ms3d_kattn_backward_q(const float *q, const float *k, const float *v, const 
     const int T = GPB * G;
     const size_t lds = dbias ? sizeof(float) * 2 * (size_t)GPB * K : 0;
     float *partial = dbias ? partial_ws : nullptr;
-    ATTN_LAUNCH(v4, kattn_backward_q_kernel, grid, T, lds, stream, q, k, v, rel_bias, nbr, out, lse, dout, Vout, K, H, D, G, HB,
+    MS3D_LAUNCH_VEC(v4, kattn_backward_q_kernel, grid, T, lds, stream, q, k, v, rel_bias, nbr, out, lse, dout, Vout, K, H, D, G, HB,
                 RG, scale, dq, delta, partial);
     if (dbias) {
         const int n = K * H;
@@ -288,11 +288,11 @@ int ms3d_kattn_backward_kv(const float *q, const float *k, const float *v, const
     if (shape_check(K, H, D)) return MS3D_E_UNSUPPORTED;
     if (Vin <= 0) return 0;
     if (!q || !k || !v || !nbr_inv || !out || !lse || !delta || !dout || (!dk && !dv)) return MS3D_E_UNSUPPORTED;
-    const bool v4 = D % 4 == 0 && aligned16(q, k, v, out, dout, dk, dv);
+    const bool v4 = D % 4 == 0 && ms3d_aligned16(q, k, v, out, dout, dk, dv);
     const int G = group_of(D, v4 ? 4 : 1);
     const long per = KATTN_THREADS / G, blocks = ((long)Vin * H + per - 1) / per;
     if (blocks > 0x7fffffffL) return MS3D_E_UNSUPPORTED;
-    ATTN_LAUNCH(v4, kattn_backward_kv_kernel, (unsigned)blocks, KATTN_THREADS, 0, stream, q, k, v, rel_bias, nbr_inv, out, lse,
+    MS3D_LAUNCH_VEC(v4, kattn_backward_kv_kernel, (unsigned)blocks, KATTN_THREADS, 0, stream, q, k, v, rel_bias, nbr_inv, out, lse,
                 delta, dout, Vin, K, H, D, G, scale, dk, dv);
     return 0;
 }

@@ -10,8 +10,7 @@
 //                                dout[n] | dout[n] / float(valid[n]) | w[e] * dout[n] (one fmaf) | dout[n][c] where arg[n][c] == j
 //                                (entry_sorted / seg_start: a stable sort of the index by row, built once per map by the caller)
 //   weight backward   dw[n][j] = <dout[n], x[idx[n][j]]>, 0 for an invalid slot
-// Layout as field.hip: consecutive lanes take consecutive channels of one row (16 bytes per lane when C % 4 == 0 and the rows
-// are aligned, else one float), the table entry of a row is the same word for all of its lanes.
+// Layout: csrc/rows.h.
 //
 // Long rows.  Carrying M picks back to all rows gives the feature backward few destinations with hundreds of entries each, so a
 // row of more than MS3D_NBR_CHUNK entries is cut into chunks of that many: a thread group per chunk sums it, in the same ascending
@@ -27,25 +26,21 @@
 
 namespace {
 
-using ms3d_rows::grid_of;
-using ms3d_rows::load_row;
-using ms3d_rows::store_row;
-using ms3d_rows::vec4;
+using namespace ms3d_rows;
 
 enum { NBR_MAX = 0, NBR_AVG = 1, NBR_SUM = 2, NBR_WEIGHTED = 3 };
+#define NBR_MODES (NBR_MAX, NBR_AVG, NBR_SUM, NBR_WEIGHTED)       // the modes of the backward; the pooling forward has the first three
 
 template <int MODE, int VEC>
 __global__ __launch_bounds__(256) void nbr_pool_forward_kernel(const float *__restrict__ x, const long long *__restrict__ idx,
                                                                int N, int k, int C, int CV, float *__restrict__ out,
                                                                unsigned char *__restrict__ arg)
 {
-    const long t = (long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (t >= (long)N * CV) return;
-    const int n = (int)(t / CV), cv = (int)(t - (long)n * CV);
+    MS3D_ROW_LANE(N, CV, n, cv);
     float acc[VEC];
-    unsigned win[VEC];
+    int win[VEC];
 #pragma unroll
-    for (int c = 0; c < VEC; c++) { acc[c] = 0.f; win[c] = 255u; }
+    for (int c = 0; c < VEC; c++) { acc[c] = 0.f; win[c] = 255; }
     const long long *row = idx + (size_t)n * k;
     int seen = 0;
 #pragma unroll 4
@@ -57,7 +52,7 @@ __global__ __launch_bounds__(256) void nbr_pool_forward_kernel(const float *__re
 #pragma unroll
         for (int c = 0; c < VEC; c++) {
             if constexpr (MODE == NBR_MAX) {
-                if (seen == 0 || f[c] > acc[c]) { acc[c] = f[c]; win[c] = (unsigned)j; }
+                if (seen == 0 || f[c] > acc[c]) { acc[c] = f[c]; win[c] = j; }
             } else {
                 acc[c] += f[c];
             }
@@ -72,12 +67,7 @@ __global__ __launch_bounds__(256) void nbr_pool_forward_kernel(const float *__re
         }
     }
     store_row<VEC>(out, (size_t)n, C, cv, acc);
-    if constexpr (MODE == NBR_MAX) {
-        if constexpr (VEC == 4)
-            reinterpret_cast<unsigned *>(arg + (size_t)n * C)[cv] = win[0] | (win[1] << 8) | (win[2] << 16) | (win[3] << 24);
-        else
-            arg[(size_t)n * C + cv] = (unsigned char)win[0];
-    }
+    if constexpr (MODE == NBR_MAX) store_arg<VEC>(arg, (size_t)n, C, cv, win);
 }
 
 template <int VEC>
@@ -85,9 +75,7 @@ __global__ __launch_bounds__(256) void nbr_wsum_forward_kernel(const float *__re
                                                                const float *__restrict__ w, int N, int k, int C, int CV,
                                                                float *__restrict__ out)
 {
-    const long t = (long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (t >= (long)N * CV) return;
-    const int n = (int)(t / CV), cv = (int)(t - (long)n * CV);
+    MS3D_ROW_LANE(N, CV, n, cv);
     float acc[VEC];
 #pragma unroll
     for (int c = 0; c < VEC; c++) acc[c] = 0.f;
@@ -123,11 +111,10 @@ __device__ __forceinline__ bool nbr_addend(long long e, const float *__restrict_
     } else if constexpr (MODE == NBR_WEIGHTED) {
         factor = w[e];
     } else if constexpr (MODE == NBR_MAX) {
-        unsigned a;
-        if constexpr (VEC == 4) a = reinterpret_cast<const unsigned *>(arg + (size_t)n * C)[cv];
-        else a = arg[(size_t)n * C + cv];
+        int a[VEC];
+        load_arg<VEC>(arg, (size_t)n, C, cv, a);
 #pragma unroll
-        for (int c = 0; c < VEC; c++) g[c] = (((a >> (8 * c)) & 255u) == (unsigned)j) ? g[c] : 0.f;
+        for (int c = 0; c < VEC; c++) g[c] = (a[c] == j) ? g[c] : 0.f;
     }
     return true;
 }
@@ -169,9 +156,7 @@ __global__ __launch_bounds__(256) void nbr_backward_chunk_kernel(const float *__
                                                                  const int *__restrict__ chunk_start, int n_chunks, int V, int N,
                                                                  int k, int C, int CV, float *__restrict__ partial)
 {
-    const long t = (long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (t >= (long)n_chunks * CV) return;
-    const int q = (int)(t / CV), cv = (int)(t - (long)q * CV);
+    MS3D_ROW_LANE(n_chunks, CV, q, cv);
     int lo = 0, hi = V;                          // the last row v with chunk_start[v] <= q owns chunk q
     for (int it = 0; it < 32 && hi - lo > 1; it++) {
         const int mid = lo + ((hi - lo) >> 1);
@@ -197,9 +182,7 @@ __global__ __launch_bounds__(256) void nbr_backward_row_kernel(const float *__re
                                                                int n_chunks, const float *__restrict__ partial, int V, int N,
                                                                int k, int C, int CV, float *__restrict__ dx)
 {
-    const long t = (long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (t >= (long)V * CV) return;
-    const int v = (int)(t / CV), cv = (int)(t - (long)v * CV);
+    MS3D_ROW_LANE(V, CV, v, cv);
     float acc[VEC];
 #pragma unroll
     for (int c = 0; c < VEC; c++) acc[c] = 0.f;
@@ -265,18 +248,12 @@ int ms3d_nbr_pool_forward(int mode, const float *x, long V, const long long *idx
     if (mode < NBR_MAX || mode > NBR_SUM || !nbr_shape(V, N, k, C)) return MS3D_E_UNSUPPORTED;
     if (N == 0) return 0;
     if (!idx || !out || (V > 0 && !x) || (mode == NBR_MAX && !arg)) return MS3D_E_UNSUPPORTED;
-    const bool v4 = vec4(C, x, out) && (mode != NBR_MAX || ((uintptr_t)arg & 3) == 0);
+    const bool v4 = vec4(C, x, out) && (mode != NBR_MAX || arg_aligned4(arg));
     const int CV = v4 ? C / 4 : C;
     unsigned blocks;
     if (!grid_of(N, CV, &blocks)) return MS3D_E_UNSUPPORTED;
-#define MS3D_NBR_POOL(M)                                                                                                 \
-    if (v4) nbr_pool_forward_kernel<M, 4><<<blocks, 256, 0, stream>>>(x, idx, (int)N, k, C, CV, out, arg);                 \
-    else nbr_pool_forward_kernel<M, 1><<<blocks, 256, 0, stream>>>(x, idx, (int)N, k, C, CV, out, arg);
-    if (mode == NBR_MAX) { MS3D_NBR_POOL(NBR_MAX) }
-    else if (mode == NBR_AVG) { MS3D_NBR_POOL(NBR_AVG) }
-    else { MS3D_NBR_POOL(NBR_SUM) }
-#undef MS3D_NBR_POOL
-    MS3D_LAUNCH_CHECK();
+    MS3D_LAUNCH_MODE_VEC((NBR_MAX, NBR_AVG, NBR_SUM), mode, v4, nbr_pool_forward_kernel, blocks, 256, 0, stream, x, idx, (int)N, k,
+                         C, CV, out, arg);
     return 0;
 }
 
@@ -291,9 +268,7 @@ int ms3d_nbr_wsum_forward(const float *x, long V, const long long *idx, const fl
     const int CV = v4 ? C / 4 : C;
     unsigned blocks;
     if (!grid_of(N, CV, &blocks)) return MS3D_E_UNSUPPORTED;
-    if (v4) nbr_wsum_forward_kernel<4><<<blocks, 256, 0, stream>>>(x, idx, w, (int)N, k, C, CV, out);
-    else nbr_wsum_forward_kernel<1><<<blocks, 256, 0, stream>>>(x, idx, w, (int)N, k, C, CV, out);
-    MS3D_LAUNCH_CHECK();
+    MS3D_LAUNCH_VEC(v4, nbr_wsum_forward_kernel, blocks, 256, 0, stream, x, idx, w, (int)N, k, C, CV, out);
     return 0;
 }
 
@@ -308,35 +283,18 @@ int ms3d_nbr_backward(int mode, const float *dout, const float *w, const unsigne
     if (!seg_start || !chunk_start || !dx) return MS3D_E_UNSUPPORTED;
     if (N > 0 && (!dout || !entry_sorted || (mode == NBR_WEIGHTED && !w) || (mode == NBR_MAX && !arg) || (mode == NBR_AVG && !valid)))
         return MS3D_E_UNSUPPORTED;
-    if (n_chunks > 0 && (!ws || ((uintptr_t)ws & 15) != 0)) return MS3D_E_UNSUPPORTED;
+    if (n_chunks > 0 && (!ws || !ms3d_aligned16(ws))) return MS3D_E_UNSUPPORTED;
     if (ws_bytes < ms3d_nbr_ws_bytes(n_chunks, C)) return MS3D_E_WORKSPACE;
     float *partial = (float *)ws;
-    const bool v4 = vec4(C, dout, dx) && (mode != NBR_MAX || ((uintptr_t)arg & 3) == 0);
+    const bool v4 = vec4(C, dout, dx) && (mode != NBR_MAX || arg_aligned4(arg));
     const int CV = v4 ? C / 4 : C;
     unsigned blocks, cblocks = 0;
     if (!grid_of(V, CV, &blocks) || !grid_of(n_chunks, CV, &cblocks)) return MS3D_E_UNSUPPORTED;
-#define MS3D_NBR_BWD(M)                                                                                                          \
-    if (v4) {                                                                                                                    \
-        if (n_chunks > 0)                                                                                                        \
-            nbr_backward_chunk_kernel<M, 4><<<cblocks, 256, 0, stream>>>(dout, w, arg, valid, entry_sorted, seg_start,            \
-                                                                         chunk_start, (int)n_chunks, (int)V, (int)N, k, C, CV,   \
-                                                                         partial);                                               \
-        nbr_backward_row_kernel<M, 4><<<blocks, 256, 0, stream>>>(dout, w, arg, valid, entry_sorted, seg_start, chunk_start,      \
-                                                                  (int)n_chunks, partial, (int)V, (int)N, k, C, CV, dx);         \
-    } else {                                                                                                                     \
-        if (n_chunks > 0)                                                                                                        \
-            nbr_backward_chunk_kernel<M, 1><<<cblocks, 256, 0, stream>>>(dout, w, arg, valid, entry_sorted, seg_start,            \
-                                                                         chunk_start, (int)n_chunks, (int)V, (int)N, k, C, CV,   \
-                                                                         partial);                                               \
-        nbr_backward_row_kernel<M, 1><<<blocks, 256, 0, stream>>>(dout, w, arg, valid, entry_sorted, seg_start, chunk_start,      \
-                                                                  (int)n_chunks, partial, (int)V, (int)N, k, C, CV, dx);         \
-    }
-    if (mode == NBR_MAX) { MS3D_NBR_BWD(NBR_MAX) }
-    else if (mode == NBR_AVG) { MS3D_NBR_BWD(NBR_AVG) }
-    else if (mode == NBR_SUM) { MS3D_NBR_BWD(NBR_SUM) }
-    else { MS3D_NBR_BWD(NBR_WEIGHTED) }
-#undef MS3D_NBR_BWD
-    MS3D_LAUNCH_CHECK();
+    if (n_chunks > 0)
+        MS3D_LAUNCH_MODE_VEC(NBR_MODES, mode, v4, nbr_backward_chunk_kernel, cblocks, 256, 0, stream, dout, w, arg, valid,
+                             entry_sorted, seg_start, chunk_start, (int)n_chunks, (int)V, (int)N, k, C, CV, partial);
+    MS3D_LAUNCH_MODE_VEC(NBR_MODES, mode, v4, nbr_backward_row_kernel, blocks, 256, 0, stream, dout, w, arg, valid, entry_sorted,
+                         seg_start, chunk_start, (int)n_chunks, partial, (int)V, (int)N, k, C, CV, dx);
     return 0;
 }
 

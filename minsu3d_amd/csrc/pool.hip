@@ -6,27 +6,25 @@
 //                                                                        submanifold map is its own inverse up to k <-> K-1-k,
 //                                                                        the caller passes whichever table names, per offset,
 //                                                                        the output row an input row feeds)
-// Layout: consecutive lanes take consecutive channels of one row (16 bytes per lane when C % 4 == 0), so the lanes of a
-// row read one contiguous run of its neighbour's row; the table entry of (k, row) is the same word for all of them.
+// Layout: csrc/rows.h (one thread per (row, lane of the row)).
 // Max keeps the winning offset index per output element (uint8, 255 = the row had no input); ties go to the lowest k
 // (strict >).  Average divides by the number of PRESENT inputs of the row.
-#include "common.h"
+#include "rows.h"
 #include "../../include/minsu3d_hip.h"
 
 namespace {
 
+using namespace ms3d_rows;
+
 enum { POOL_MAX = 0, POOL_AVG = 1, POOL_SUM = 2 };
 constexpr int ARG_NONE = 255;
 
-// VEC = floats per lane (4: C % 4 == 0, rows 16-byte aligned; 1 otherwise); CV = C / VEC lanes per row
 template <int MODE, int VEC>
 __global__ __launch_bounds__(256) void pool_forward_kernel(const float *__restrict__ in, const int *__restrict__ nbr, int Vout,
                                                            int K, int C, int CV, float *__restrict__ out,
                                                            unsigned char *__restrict__ arg, int *__restrict__ count)
 {
-    const long t = (long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (t >= (long)Vout * CV) return;
-    const int o = (int)(t / CV), cv = (int)(t - (long)o * CV);
+    MS3D_ROW_LANE(Vout, CV, o, cv);
     float acc[VEC];
     int win[VEC];
 #pragma unroll
@@ -36,12 +34,7 @@ __global__ __launch_bounds__(256) void pool_forward_kernel(const float *__restri
         const int i = nbr[(size_t)k * Vout + o];
         if (i < 0) continue;
         float v[VEC];
-        if constexpr (VEC == 4) {
-            const float4 r = reinterpret_cast<const float4 *>(in + (size_t)i * C)[cv];
-            v[0] = r.x; v[1] = r.y; v[2] = r.z; v[3] = r.w;
-        } else {
-            v[0] = in[(size_t)i * C + cv];
-        }
+        load_row<VEC>(in, (size_t)i, C, cv, v);
 #pragma unroll
         for (int j = 0; j < VEC; j++) {
             if constexpr (MODE == POOL_MAX) {
@@ -59,15 +52,8 @@ __global__ __launch_bounds__(256) void pool_forward_kernel(const float *__restri
         }
         if (cv == 0) count[o] = n;
     }
-    if constexpr (VEC == 4) {
-        reinterpret_cast<float4 *>(out + (size_t)o * C)[cv] = make_float4(acc[0], acc[1], acc[2], acc[3]);
-        if constexpr (MODE == POOL_MAX)
-            reinterpret_cast<uchar4 *>(arg + (size_t)o * C)[cv] =
-                make_uchar4((unsigned char)win[0], (unsigned char)win[1], (unsigned char)win[2], (unsigned char)win[3]);
-    } else {
-        out[(size_t)o * C + cv] = acc[0];
-        if constexpr (MODE == POOL_MAX) arg[(size_t)o * C + cv] = (unsigned char)win[0];
-    }
+    store_row<VEC>(out, (size_t)o, C, cv, acc);
+    if constexpr (MODE == POOL_MAX) store_arg<VEC>(arg, (size_t)o, C, cv, win);
 }
 
 template <int MODE, int VEC>
@@ -76,9 +62,7 @@ __global__ __launch_bounds__(256) void pool_backward_kernel(const float *__restr
                                                             const unsigned char *__restrict__ arg, const int *__restrict__ count,
                                                             float *__restrict__ din)
 {
-    const long t = (long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (t >= (long)Vin * CV) return;
-    const int i = (int)(t / CV), cv = (int)(t - (long)i * CV);
+    MS3D_ROW_LANE(Vin, CV, i, cv);
     float acc[VEC];
 #pragma unroll
     for (int j = 0; j < VEC; j++) acc[j] = 0.f;
@@ -86,20 +70,10 @@ __global__ __launch_bounds__(256) void pool_backward_kernel(const float *__restr
         const int o = nbr_inv[(size_t)k * Vin + i];
         if (o < 0) continue;
         float g[VEC];
-        if constexpr (VEC == 4) {
-            const float4 r = reinterpret_cast<const float4 *>(dout + (size_t)o * C)[cv];
-            g[0] = r.x; g[1] = r.y; g[2] = r.z; g[3] = r.w;
-        } else {
-            g[0] = dout[(size_t)o * C + cv];
-        }
+        load_row<VEC>(dout, (size_t)o, C, cv, g);
         if constexpr (MODE == POOL_MAX) {
             int w[VEC];
-            if constexpr (VEC == 4) {
-                const uchar4 a = reinterpret_cast<const uchar4 *>(arg + (size_t)o * C)[cv];
-                w[0] = a.x; w[1] = a.y; w[2] = a.z; w[3] = a.w;
-            } else {
-                w[0] = arg[(size_t)o * C + cv];
-            }
+            load_arg<VEC>(arg, (size_t)o, C, cv, w);
 #pragma unroll
             for (int j = 0; j < VEC; j++) acc[j] += (w[j] == k) ? g[j] : 0.f;
         } else if constexpr (MODE == POOL_AVG) {
@@ -111,15 +85,7 @@ __global__ __launch_bounds__(256) void pool_backward_kernel(const float *__restr
             for (int j = 0; j < VEC; j++) acc[j] += g[j];
         }
     }
-    if constexpr (VEC == 4)
-        reinterpret_cast<float4 *>(din + (size_t)i * C)[cv] = make_float4(acc[0], acc[1], acc[2], acc[3]);
-    else
-        din[(size_t)i * C + cv] = acc[0];
-}
-
-bool rows_vec4(int C, const void *a, const void *b, const void *arg)
-{
-    return C % 4 == 0 && ((uintptr_t)a & 15) == 0 && ((uintptr_t)b & 15) == 0 && ((uintptr_t)arg & 3) == 0;
+    store_row<VEC>(din, (size_t)i, C, cv, acc);
 }
 
 }  // namespace
@@ -133,18 +99,12 @@ int ms3d_pool_forward(int mode, const float *in, const int *nbr, int Vout, int K
     if (mode < POOL_MAX || mode > POOL_SUM || K < 1 || K >= ARG_NONE || C < 1) return MS3D_E_UNSUPPORTED;
     if ((mode == POOL_MAX && !arg) || (mode == POOL_AVG && !count)) return MS3D_E_UNSUPPORTED;
     if (Vout <= 0) return 0;
-    const bool v4 = rows_vec4(C, in, out, arg);
+    const bool v4 = vec4(C, in, out) && arg_aligned4(arg);
     const int CV = v4 ? C / 4 : C;
-    const long blocks = ((long)Vout * CV + 255) / 256;
-    if (blocks > 0x7fffffffL) return MS3D_E_UNSUPPORTED;
-#define MS3D_POOL_FWD(M)                                                                                               \
-    if (v4) pool_forward_kernel<M, 4><<<(unsigned)blocks, 256, 0, stream>>>(in, nbr, Vout, K, C, CV, out, arg, count);    \
-    else pool_forward_kernel<M, 1><<<(unsigned)blocks, 256, 0, stream>>>(in, nbr, Vout, K, C, CV, out, arg, count);
-    if (mode == POOL_MAX) { MS3D_POOL_FWD(POOL_MAX) }
-    else if (mode == POOL_AVG) { MS3D_POOL_FWD(POOL_AVG) }
-    else { MS3D_POOL_FWD(POOL_SUM) }
-#undef MS3D_POOL_FWD
-    MS3D_LAUNCH_CHECK();
+    unsigned blocks;
+    if (!grid_of(Vout, CV, &blocks)) return MS3D_E_UNSUPPORTED;
+    MS3D_LAUNCH_MODE_VEC((POOL_MAX, POOL_AVG, POOL_SUM), mode, v4, pool_forward_kernel, blocks, 256, 0, stream, in, nbr, Vout, K,
+                         C, CV, out, arg, count);
     return 0;
 }
 
@@ -155,18 +115,12 @@ int ms3d_pool_backward(int mode, const float *dout, const int *nbr_inv, int Vin,
     if (mode < POOL_MAX || mode > POOL_SUM || K < 1 || K >= ARG_NONE || C < 1) return MS3D_E_UNSUPPORTED;
     if ((mode == POOL_MAX && !arg) || (mode == POOL_AVG && !count)) return MS3D_E_UNSUPPORTED;
     if (Vin <= 0) return 0;
-    const bool v4 = rows_vec4(C, dout, din, arg);
+    const bool v4 = vec4(C, dout, din) && arg_aligned4(arg);
     const int CV = v4 ? C / 4 : C;
-    const long blocks = ((long)Vin * CV + 255) / 256;
-    if (blocks > 0x7fffffffL) return MS3D_E_UNSUPPORTED;
-#define MS3D_POOL_BWD(M)                                                                                               \
-    if (v4) pool_backward_kernel<M, 4><<<(unsigned)blocks, 256, 0, stream>>>(dout, nbr_inv, Vin, K, C, CV, arg, count, din); \
-    else pool_backward_kernel<M, 1><<<(unsigned)blocks, 256, 0, stream>>>(dout, nbr_inv, Vin, K, C, CV, arg, count, din);
-    if (mode == POOL_MAX) { MS3D_POOL_BWD(POOL_MAX) }
-    else if (mode == POOL_AVG) { MS3D_POOL_BWD(POOL_AVG) }
-    else { MS3D_POOL_BWD(POOL_SUM) }
-#undef MS3D_POOL_BWD
-    MS3D_LAUNCH_CHECK();
+    unsigned blocks;
+    if (!grid_of(Vin, CV, &blocks)) return MS3D_E_UNSUPPORTED;
+    MS3D_LAUNCH_MODE_VEC((POOL_MAX, POOL_AVG, POOL_SUM), mode, v4, pool_backward_kernel, blocks, 256, 0, stream, dout, nbr_inv,
+                         Vin, K, C, CV, arg, count, din);
     return 0;
 }
 

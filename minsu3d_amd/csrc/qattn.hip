@@ -324,17 +324,17 @@ int ms3d_qattn_forward(const float *queries, const float *k, const float *v, con
     if (ws_floats < ms3d_qattn_ws_floats(chunks, Q, H, D)) return MS3D_E_WORKSPACE;
     const size_t C = (size_t)H * D, nacc = (size_t)chunks * Q * C, nqh = (size_t)chunks * Q * H;
     float *w_acc = ws, *w_m = ws + nacc, *w_l = ws + nacc + nqh;
-    const bool v4 = D % 4 == 0 && aligned16(queries, k, v, out, ws);
+    const bool v4 = D % 4 == 0 && ms3d_aligned16(queries, k, v, out, ws);
     const Shape sh{B, Q, H, D, group_of(D, v4 ? 4 : 1), scale};
     const unsigned tiles = item_tiles(Q, H, sh.G);
     if (!tiles) return MS3D_E_UNSUPPORTED;
     if (chunks > 0) {
         const dim3 grid((unsigned)chunks, tiles);
-        ATTN_LAUNCH(v4, qattn_forward_kernel, grid, QATTN_THREADS, 0, stream, queries, k, v, mask, row_map, order, seg_start,
+        MS3D_LAUNCH_VEC(v4, qattn_forward_kernel, grid, QATTN_THREADS, 0, stream, queries, k, v, mask, row_map, order, seg_start,
                     chunk_seg, chunk_first, sh, w_acc, w_m, w_l);
     }
     const dim3 mgrid((unsigned)B, tiles);
-    ATTN_LAUNCH(v4, qattn_forward_merge_kernel, mgrid, QATTN_THREADS, 0, stream, chunk_first, sh, w_acc, w_m, w_l, out, lse);
+    MS3D_LAUNCH_VEC(v4, qattn_forward_merge_kernel, mgrid, QATTN_THREADS, 0, stream, chunk_first, sh, w_acc, w_m, w_l, out, lse);
     return 0;
 }
 
@@ -352,18 +352,18 @@ int ms3d_qattn_backward_q(const float *queries, const float *k, const float *v, 
     if (ws_floats < ms3d_qattn_backward_ws_floats(chunks, Q, H, D)) return MS3D_E_WORKSPACE;
     const size_t C = (size_t)H * D, nacc = (size_t)chunks * Q * C;
     float *w_a = ws, *w_p = ws + nacc, *w_d = ws + 2 * nacc;
-    const bool v4 = D % 4 == 0 && aligned16(queries, k, v, out, dout, ws, dq);
+    const bool v4 = D % 4 == 0 && ms3d_aligned16(queries, k, v, out, dout, ws, dq);
     const Shape sh{B, Q, H, D, group_of(D, v4 ? 4 : 1), scale};
     const unsigned tiles = item_tiles(Q, H, sh.G);
     if (!tiles) return MS3D_E_UNSUPPORTED;
     if (chunks > 0) {
         const dim3 grid((unsigned)chunks, tiles);
         const int rows = dq != nullptr;
-        ATTN_LAUNCH(v4, qattn_backward_q_kernel, grid, QATTN_THREADS, 0, stream, queries, k, v, mask, row_map, order, seg_start,
+        MS3D_LAUNCH_VEC(v4, qattn_backward_q_kernel, grid, QATTN_THREADS, 0, stream, queries, k, v, mask, row_map, order, seg_start,
                     chunk_seg, chunk_first, out, lse, dout, sh, rows, w_a, w_p, w_d);
     }
     const dim3 mgrid((unsigned)B, tiles);
-    ATTN_LAUNCH(v4, qattn_backward_q_merge_kernel, mgrid, QATTN_THREADS, 0, stream, chunk_first, sh, w_a, w_p, w_d, dq, delta);
+    MS3D_LAUNCH_VEC(v4, qattn_backward_q_merge_kernel, mgrid, QATTN_THREADS, 0, stream, chunk_first, sh, w_a, w_p, w_d, dq, delta);
     return 0;
 }
 
@@ -375,11 +375,11 @@ int ms3d_qattn_backward_kv(const float *queries, const float *k, const float *v,
     if (!sample_shape_served(V, B, Q, H, D)) return MS3D_E_UNSUPPORTED;
     if (V == 0 || B == 0 || Q == 0) return 0;                         // (dk / dv are not written: the caller's zero)
     if (!queries || !k || !v || !seg_of_row || !out || !lse || !delta || !dout || (!dk && !dv)) return MS3D_E_UNSUPPORTED;
-    const bool v4 = D % 4 == 0 && aligned16(queries, k, v, out, dout, dk, dv);
+    const bool v4 = D % 4 == 0 && ms3d_aligned16(queries, k, v, out, dout, dk, dv);
     const Shape sh{B, Q, H, D, group_of(D, v4 ? 4 : 1), scale};
     const long per = QATTN_THREADS / sh.G, blocks = (V * H + per - 1) / per;
     if (blocks > 0x7fffffffL) return MS3D_E_UNSUPPORTED;
-    ATTN_LAUNCH(v4, qattn_backward_kv_kernel, (unsigned)blocks, QATTN_THREADS, 0, stream, queries, k, v, mask, row_map, seg_of_row,
+    MS3D_LAUNCH_VEC(v4, qattn_backward_kv_kernel, (unsigned)blocks, QATTN_THREADS, 0, stream, queries, k, v, mask, row_map, seg_of_row,
                 out, lse, delta, dout, V, sh, dk, dv);
     return 0;
 }

@@ -638,11 +638,10 @@ int ms3d_scatter_add_rows_sorted(const float *src, const long long *keys_sorted,
                                  float *dst, ms3d_stream_t stream)
 {
     if (n <= 0 || C <= 0) return 0;
-    if (C % 4 == 0 && ((uintptr_t)src % 16) == 0 && ((uintptr_t)dst % 16) == 0)
-        segment_sum_sorted_kernel<4><<<ms3d_divup(n * (C / 4), 256), 256, 0, (hipStream_t)stream>>>(src, keys_sorted, order, n, C / 4, dst);
-    else
-        segment_sum_sorted_kernel<1><<<ms3d_divup(n * C, 256), 256, 0, (hipStream_t)stream>>>(src, keys_sorted, order, n, C, dst);
-    MS3D_LAUNCH_CHECK();
+    const bool v4 = C % 4 == 0 && ms3d_aligned16(src, dst);
+    const int CV = v4 ? C / 4 : C;
+    MS3D_LAUNCH_VEC(v4, segment_sum_sorted_kernel, ms3d_divup(n * CV, 256), 256, 0, (hipStream_t)stream, src, keys_sorted, order, n,
+                    CV, dst);
     return 0;
 }
 

@@ -8,15 +8,16 @@
 //   broadcast       out[r] = x[r] (op) g[grow[r]]; the gradient of x is the identity, a column slice or the same kernel
 //   its reduction   dg[j] = sum over the rows of g row j's batch of dout[r] (* x[r]): per-slice partial sums in a fixed
 //                   thread order, then a combine in slice order
-// Layout as in pool.hip: consecutive lanes take consecutive channels of one row, 16 bytes per lane when C % 4 == 0 and the
-// rows are 16-byte aligned, 4 bytes otherwise.
+// Layout: csrc/rows.h.
 //
 // The rule for a coordinate only one operand holds (MinkowskiEngine's, as recalled): the result is zero-filled, receives a
 // at a's rows and is then set to fn(out, b) at b's rows -- a + b, a - b (only b: -b), a * b (only a: a; only b: 0 * b).
-#include "common.h"
+#include "rows.h"
 #include "../../include/minsu3d_hip.h"
 
 namespace {
+
+using namespace ms3d_rows;
 
 enum { OP_SUM = 0, OP_SUB = 1, OP_MUL = 2 };
 enum { BC_ADD = 0, BC_MUL = 1, BC_CAT = 2, BC_COPY = 3 };
@@ -28,32 +29,10 @@ struct RowPtrs {
 };
 
 template <int VEC>
-__device__ __forceinline__ void load_row(const float *__restrict__ p, size_t row, int ld, int cv, float (&v)[VEC])
-{
-    if constexpr (VEC == 4) {
-        const float4 r = reinterpret_cast<const float4 *>(p + row * ld)[cv];
-        v[0] = r.x; v[1] = r.y; v[2] = r.z; v[3] = r.w;
-    } else {
-        v[0] = p[row * ld + cv];
-    }
-}
-template <int VEC>
-__device__ __forceinline__ void store_row(float *__restrict__ p, size_t row, int ld, int cv, const float (&v)[VEC])
-{
-    if constexpr (VEC == 4)
-        reinterpret_cast<float4 *>(p + row * ld)[cv] = make_float4(v[0], v[1], v[2], v[3]);
-    else
-        p[row * ld + cv] = v[0];
-}
-
-// VEC = floats per lane; CV = C / VEC lanes per row
-template <int VEC>
 __global__ __launch_bounds__(256) void union_combine_kernel(RowPtrs in, int n_sets, const int *__restrict__ in_row, int n_out,
                                                             int op, int C, int CV, float *__restrict__ out)
 {
-    const long t = (long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (t >= (long)n_out * CV) return;
-    const int o = (int)(t / CV), cv = (int)(t - (long)o * CV);
+    MS3D_ROW_LANE(n_out, CV, o, cv);
     float acc[VEC];
 #pragma unroll
     for (int j = 0; j < VEC; j++) acc[j] = 0.f;
@@ -81,9 +60,7 @@ __global__ __launch_bounds__(256) void union_combine_backward_kernel(const float
                                                                      const int *__restrict__ other_row, int C, int CV,
                                                                      float *__restrict__ din)
 {
-    const long t = (long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (t >= (long)V * CV) return;
-    const int r = (int)(t / CV), cv = (int)(t - (long)r * CV);
+    MS3D_ROW_LANE(V, CV, r, cv);
     const int o = out_row[r];
     float g[VEC];
     load_row<VEC>(dout, (size_t)o, C, cv, g);
@@ -114,9 +91,7 @@ __global__ __launch_bounds__(256) void broadcast_forward_kernel(const float *__r
                                                                 const int *__restrict__ grow, int V, int C, int Cg, int Cout,
                                                                 int CxV, int CoV, float *__restrict__ out)
 {
-    const long t = (long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (t >= (long)V * CoV) return;
-    const int r = (int)(t / CoV), cv = (int)(t - (long)r * CoV);
+    MS3D_ROW_LANE(V, CoV, r, cv);
     float v[VEC];
     if (MODE == BC_CAT && cv < CxV) {
         load_row<VEC>(x, (size_t)r, C, cv, v);
@@ -172,12 +147,7 @@ __global__ __launch_bounds__(256) void broadcast_reduce_partial_kernel(const flo
             for (int i = s0 + ty; i < s1; i += RY) {
                 const size_t r = (size_t)order[begin + i];
                 float d[VEC];
-                if constexpr (VEC == 4) {
-                    const float4 q = *reinterpret_cast<const float4 *>(dout + r * ldd + col_off + 4 * cv);
-                    d[0] = q.x; d[1] = q.y; d[2] = q.z; d[3] = q.w;
-                } else {
-                    d[0] = dout[r * ldd + col_off + cv];
-                }
+                load_vec<VEC>(dout + r * ldd + col_off + VEC * cv, d);
                 if (x) {
                     float v[VEC];
                     load_row<VEC>(x, r, C, cv, v);
@@ -217,8 +187,6 @@ __global__ __launch_bounds__(256) void broadcast_reduce_combine_kernel(const flo
     dg[t] = s;
 }
 
-bool aligned16(const void *p) { return ((uintptr_t)p & 15) == 0; }
-
 }  // namespace
 
 extern "C" {
@@ -231,17 +199,15 @@ int ms3d_union_combine(int op, const float *const *in_feats, int n_sets, const i
     if (op < OP_SUM || op > OP_MUL || (op != OP_SUM && n_sets != 2)) return MS3D_E_UNSUPPORTED;
     if (n_out <= 0) return 0;
     RowPtrs in;
-    bool v4 = C % 4 == 0 && aligned16(out);
+    bool v4 = vec4(C, out);
     for (int i = 0; i < MAX_SETS; i++) {
         in.f[i] = i < n_sets ? in_feats[i] : nullptr;
-        v4 = v4 && aligned16(in.f[i]);
+        v4 = v4 && ms3d_aligned16(in.f[i]);
     }
     const int CV = v4 ? C / 4 : C;
-    const long blocks = ((long)n_out * CV + 255) / 256;
-    if (blocks > 0x7fffffffL) return MS3D_E_UNSUPPORTED;
-    if (v4) union_combine_kernel<4><<<(unsigned)blocks, 256, 0, stream>>>(in, n_sets, in_row, n_out, op, C, CV, out);
-    else union_combine_kernel<1><<<(unsigned)blocks, 256, 0, stream>>>(in, n_sets, in_row, n_out, op, C, CV, out);
-    MS3D_LAUNCH_CHECK();
+    unsigned blocks;
+    if (!grid_of(n_out, CV, &blocks)) return MS3D_E_UNSUPPORTED;
+    MS3D_LAUNCH_VEC(v4, union_combine_kernel, blocks, 256, 0, stream, in, n_sets, in_row, n_out, op, C, CV, out);
     return 0;
 }
 
@@ -253,17 +219,12 @@ int ms3d_union_combine_backward(int op, int which, const float *dout, const int 
     if (op != OP_SUM && which > 1) return MS3D_E_UNSUPPORTED;
     if (op == OP_MUL && !other_row) return MS3D_E_UNSUPPORTED;
     if (V <= 0) return 0;
-    const bool v4 = C % 4 == 0 && aligned16(dout) && aligned16(din) && aligned16(other);
+    const bool v4 = vec4(C, dout, din, other);
     const int CV = v4 ? C / 4 : C;
-    const long blocks = ((long)V * CV + 255) / 256;
-    if (blocks > 0x7fffffffL) return MS3D_E_UNSUPPORTED;
-    if (v4)
-        union_combine_backward_kernel<4><<<(unsigned)blocks, 256, 0, stream>>>(dout, out_row, V, op, which, other, other_row, C,
-                                                                              CV, din);
-    else
-        union_combine_backward_kernel<1><<<(unsigned)blocks, 256, 0, stream>>>(dout, out_row, V, op, which, other, other_row, C,
-                                                                              CV, din);
-    MS3D_LAUNCH_CHECK();
+    unsigned blocks;
+    if (!grid_of(V, CV, &blocks)) return MS3D_E_UNSUPPORTED;
+    MS3D_LAUNCH_VEC(v4, union_combine_backward_kernel, blocks, 256, 0, stream, dout, out_row, V, op, which, other, other_row, C, CV,
+                    din);
     return 0;
 }
 
@@ -277,19 +238,12 @@ int ms3d_broadcast_forward(int mode, const float *x, const float *g, const int *
     if ((mode == BC_ADD || mode == BC_MUL) && C != Cg) return MS3D_E_UNSUPPORTED;
     if (V <= 0) return 0;
     const int Cout = (mode == BC_CAT) ? C + Cg : Cg;
-    const bool v4 = C % 4 == 0 && Cg % 4 == 0 && aligned16(x) && aligned16(g) && aligned16(out);
+    const bool v4 = vec4(C, x, g, out) && Cg % 4 == 0;
     const int vec = v4 ? 4 : 1;
-    const long blocks = ((long)V * (Cout / vec) + 255) / 256;
-    if (blocks > 0x7fffffffL) return MS3D_E_UNSUPPORTED;
-#define MS3D_BCAST(M)                                                                                                  \
-    if (v4) broadcast_forward_kernel<M, 4><<<(unsigned)blocks, 256, 0, stream>>>(x, g, grow, V, C, Cg, Cout, C / 4, Cout / 4, out); \
-    else broadcast_forward_kernel<M, 1><<<(unsigned)blocks, 256, 0, stream>>>(x, g, grow, V, C, Cg, Cout, C, Cout, out);
-    if (mode == BC_ADD) { MS3D_BCAST(BC_ADD) }
-    else if (mode == BC_MUL) { MS3D_BCAST(BC_MUL) }
-    else if (mode == BC_CAT) { MS3D_BCAST(BC_CAT) }
-    else { MS3D_BCAST(BC_COPY) }
-#undef MS3D_BCAST
-    MS3D_LAUNCH_CHECK();
+    unsigned blocks;
+    if (!grid_of(V, Cout / vec, &blocks)) return MS3D_E_UNSUPPORTED;
+    MS3D_LAUNCH_MODE_VEC((BC_ADD, BC_MUL, BC_CAT, BC_COPY), mode, v4, broadcast_forward_kernel, blocks, 256, 0, stream, x, g, grow,
+                         V, C, Cg, Cout, C / vec, Cout / vec, out);
     return 0;
 }
 
@@ -308,18 +262,13 @@ int ms3d_broadcast_reduce(const float *dout, int ldd, int col_off, const float *
     if (G > 65535) return MS3D_E_UNSUPPORTED;                  // one grid row per global row
     if (ms3d_broadcast_reduce_workspace_bytes(G, C) > workspace_bytes) return MS3D_E_WORKSPACE;
     float *partial = (float *)workspace;
-    const bool v4 = C % 4 == 0 && ldd % 4 == 0 && col_off % 4 == 0 && aligned16(dout) && aligned16(x) && aligned16(partial);
+    const bool v4 = vec4(C, dout, x, partial) && ldd % 4 == 0 && col_off % 4 == 0;
     const int CV = v4 ? C / 4 : C;
     int CW = 1;
     while (CW < CV && CW < 64) CW <<= 1;
     dim3 grid(REDUCE_SLICES, G);
-    if (v4)
-        broadcast_reduce_partial_kernel<4><<<grid, 256, 0, stream>>>(dout, ldd, col_off, x, C, CV, CW, order, seg_start, seg_of_g,
-                                                                    partial);
-    else
-        broadcast_reduce_partial_kernel<1><<<grid, 256, 0, stream>>>(dout, ldd, col_off, x, C, CV, CW, order, seg_start, seg_of_g,
-                                                                    partial);
-    MS3D_LAUNCH_CHECK();
+    MS3D_LAUNCH_VEC(v4, broadcast_reduce_partial_kernel, grid, 256, 0, stream, dout, ldd, col_off, x, C, CV, CW, order, seg_start,
+                    seg_of_g, partial);
     broadcast_reduce_combine_kernel<<<ms3d_divup((long)G * C, 256), 256, 0, stream>>>(partial, G, C, dg);
     MS3D_LAUNCH_CHECK();
     return 0;

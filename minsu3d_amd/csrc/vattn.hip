@@ -253,11 +253,11 @@ int ms3d_vattn_forward(const float *x, const float *keys, const float *values, c
     if (!sample_shape_served(V, B, Q, H, D)) return MS3D_E_UNSUPPORTED;
     if (V == 0 || B == 0 || Q == 0) return 0;                         // (out / lse are not written: the caller's zero)
     if (!x || !keys || !values || !seg_of_row || !out || !lse) return MS3D_E_UNSUPPORTED;
-    const bool v4 = D % 4 == 0 && aligned16(x, keys, values, out);
+    const bool v4 = D % 4 == 0 && ms3d_aligned16(x, keys, values, out);
     const Shape sh{B, Q, H, D, group_of(D, v4 ? 4 : 1), scale};
     const unsigned blocks = row_blocks(V, H, sh.G);
     if (!blocks) return MS3D_E_UNSUPPORTED;
-    ATTN_LAUNCH(v4, vattn_forward_kernel, blocks, VATTN_THREADS, 0, stream, x, keys, values, mask, row_map, seg_of_row, V, sh,
+    MS3D_LAUNCH_VEC(v4, vattn_forward_kernel, blocks, VATTN_THREADS, 0, stream, x, keys, values, mask, row_map, seg_of_row, V, sh,
                 out, lse);
     return 0;
 }
@@ -270,11 +270,11 @@ int ms3d_vattn_backward_x(const float *x, const float *keys, const float *values
     if (!sample_shape_served(V, B, Q, H, D)) return MS3D_E_UNSUPPORTED;
     if (V == 0 || B == 0 || Q == 0) return 0;
     if (!x || !keys || !values || !seg_of_row || !out || !lse || !dout || !delta) return MS3D_E_UNSUPPORTED;
-    const bool v4 = D % 4 == 0 && aligned16(x, keys, values, out, dout, dx);
+    const bool v4 = D % 4 == 0 && ms3d_aligned16(x, keys, values, out, dout, dx);
     const Shape sh{B, Q, H, D, group_of(D, v4 ? 4 : 1), scale};
     const unsigned blocks = row_blocks(V, H, sh.G);
     if (!blocks) return MS3D_E_UNSUPPORTED;
-    ATTN_LAUNCH(v4, vattn_backward_x_kernel, blocks, VATTN_THREADS, 0, stream, x, keys, values, mask, row_map, seg_of_row, out,
+    MS3D_LAUNCH_VEC(v4, vattn_backward_x_kernel, blocks, VATTN_THREADS, 0, stream, x, keys, values, mask, row_map, seg_of_row, out,
                 lse, dout, V, sh, dx, delta);
     return 0;
 }
@@ -294,17 +294,17 @@ int ms3d_vattn_backward_kv(const float *x, const float *keys, const float *value
     if (ws_floats < ms3d_vattn_backward_kv_ws_floats(chunks, Q, H, D)) return MS3D_E_WORKSPACE;
     const size_t nacc = (size_t)chunks * Q * H * D;
     float *w_k = ws, *w_v = ws + nacc;
-    const bool v4 = D % 4 == 0 && aligned16(x, keys, values, out, dout, dkeys, dvalues, ws);
+    const bool v4 = D % 4 == 0 && ms3d_aligned16(x, keys, values, out, dout, dkeys, dvalues, ws);
     const Shape sh{B, Q, H, D, group_of(D, v4 ? 4 : 1), scale};
     const unsigned tiles = item_tiles(Q, H, sh.G);
     if (!tiles) return MS3D_E_UNSUPPORTED;
     if (chunks > 0) {
         const dim3 grid((unsigned)chunks, tiles);
-        ATTN_LAUNCH(v4, vattn_backward_kv_kernel, grid, VATTN_THREADS, 0, stream, x, keys, values, mask, row_map, order,
+        MS3D_LAUNCH_VEC(v4, vattn_backward_kv_kernel, grid, VATTN_THREADS, 0, stream, x, keys, values, mask, row_map, order,
                     seg_start, chunk_seg, chunk_first, out, lse, delta, dout, sh, w_k, w_v);
     }
     const dim3 mgrid((unsigned)B, tiles);
-    ATTN_LAUNCH(v4, vattn_backward_kv_merge_kernel, mgrid, VATTN_THREADS, 0, stream, chunk_first, sh, w_k, w_v, dkeys, dvalues);
+    MS3D_LAUNCH_VEC(v4, vattn_backward_kv_merge_kernel, mgrid, VATTN_THREADS, 0, stream, chunk_first, sh, w_k, w_v, dkeys, dvalues);
     return 0;
 }
 

@@ -449,6 +449,78 @@ def test_composed_point_voxel_point_step(ME, size):
 
 
 # ---------------------------------------------------------------------------------------------- 8. size (printed only)
+# ------------------------------------------------------------------------------------------------ the scalar route
+def off_by_one_float(a):
+    """the same values in storage that starts one float behind a 16-byte boundary (a slice of a larger buffer)"""
+    buf = torch.empty(a.size + 1, dtype=torch.float32, device="cuda")
+    t = buf[1:].view(a.shape)
+    t.copy_(torch.from_numpy(a))
+    assert buf.data_ptr() % 16 == 0 and t.data_ptr() % 16 == 4 and t.is_contiguous() and t.contiguous().data_ptr() == t.data_ptr()
+    return t
+
+
+def same_bits(a, b):
+    a, b = a.cpu().numpy(), b.cpu().numpy()
+    return a.shape == b.shape and a.dtype == b.dtype == np.float32 and np.array_equal(a.view(np.int32), b.view(np.int32))
+
+
+def test_misaligned_rows_take_the_scalar_route():
+    """C = 8 would take four floats per lane (130 points: 260 threads, two blocks); features and upstream gradients one float
+    off the alignment take one, and give the same bytes in interpolation and in all three reductions, both directions, and
+    for max the same winners"""
+    from minsu3d_amd.backend import get_backend
+    be = get_backend()
+    rng = np.random.default_rng(131)
+    N, V, C = 130, 40, 8
+    # points -> voxels: every voxel holds a point, some hold many; the stable sort of the map and its segments
+    inverse = np.concatenate([np.arange(V), rng.integers(0, V // 4, N - V)]).astype(np.int32)
+    rng.shuffle(inverse)
+    order = np.argsort(inverse, kind="stable").astype(np.int64)
+    seg_start = np.concatenate([[0], np.cumsum(np.bincount(inverse, minlength=V))]).astype(np.int32)
+    feats = rng.standard_normal((N, C)).astype(np.float32)
+    feats[:, 0] = np.round(feats[:, 0])                            # ties for max: the first point of the voxel wins
+    dvox = rng.standard_normal((V, C)).astype(np.float32)
+    for mode in (R.AVG, R.SUM, R.MAX):
+        a, aarg = be.field_reduce(mode, dev(feats), dev(order), dev(seg_start), V)
+        b, barg = be.field_reduce(mode, off_by_one_float(feats), dev(order), dev(seg_start), V)
+        assert same_bits(a, b), mode
+        if mode == R.MAX:
+            assert torch.equal(aarg, barg)
+            w = aarg.cpu().numpy()
+            assert np.array_equal(inverse[w], np.tile(np.arange(V)[:, None], (1, C)))
+            assert np.array_equal(a.cpu().numpy(), feats[w, np.arange(C)[None, :]])
+        else:
+            assert aarg is None and barg is None
+        da = be.field_reduce_backward(mode, dev(dvox), dev(inverse), dev(seg_start), aarg)
+        db = be.field_reduce_backward(mode, off_by_one_float(dvox), dev(inverse), dev(seg_start), barg)
+        assert same_bits(da, db), mode
+        if mode == R.SUM:
+            assert np.array_equal(da.cpu().numpy(), dvox[inverse])
+
+    # voxels -> points: eight corners per point, a third of them absent; the table sorted by voxel row, entry = 8 * point + corner
+    rows = rng.integers(0, V, (8, N)).astype(np.int32)
+    rows[rng.random((8, N)) < 0.33] = -1
+    rows[:, 5] = -1                                                # a point without corners
+    weights = rng.random((8, N)).astype(np.float32)
+    flat = rows.T.reshape(-1)
+    e = np.nonzero(flat >= 0)[0]
+    entry_sorted = e[np.argsort(flat[e], kind="stable")].astype(np.int64)
+    eseg = np.concatenate([[0], np.cumsum(np.bincount(flat[e], minlength=V))]).astype(np.int32)
+    x = rng.standard_normal((V, C)).astype(np.float32)
+    dout = rng.standard_normal((N, C)).astype(np.float32)
+    a = be.interp_forward(dev(x), dev(rows), dev(weights))
+    b = be.interp_forward(off_by_one_float(x), dev(rows), dev(weights))
+    want = sum(np.where(rows[j][:, None] >= 0, weights[j].astype(np.float64)[:, None] * x[np.maximum(rows[j], 0)], 0.0) for j in range(8))
+    assert np.allclose(a.cpu().numpy(), want, rtol=0, atol=1e-5 * np.abs(want).max()) and not a[5].any()
+    assert same_bits(a, b)
+    a = be.interp_backward(dev(dout), dev(weights), dev(entry_sorted), dev(eseg), V)
+    b = be.interp_backward(off_by_one_float(dout), dev(weights), dev(entry_sorted), dev(eseg), V)
+    want = np.zeros((V, C))
+    np.add.at(want, flat[e], weights.T.reshape(-1)[e].astype(np.float64)[:, None] * dout[e // 8])
+    assert np.allclose(a.cpu().numpy(), want, rtol=0, atol=1e-5 * np.abs(want).max())
+    assert same_bits(a, b)
+
+
 def _ms(fn, reps=5):
     fn()
     torch.cuda.synchronize()

@@ -417,6 +417,105 @@ def test_one_training_step_twice_gives_identical_bytes(ME):
 
 
 # ---------------------------------------------------------------------------------------------- 4. one size case
+# ------------------------------------------------------------------------------------------------ the scalar route
+def off_by_one_float(a):
+    """the same values in storage that starts one float behind a 16-byte boundary (a slice of a larger buffer)"""
+    buf = torch.empty(a.size + 1, dtype=torch.float32, device="cuda")
+    t = buf[1:].view(a.shape)
+    t.copy_(torch.from_numpy(a))
+    assert buf.data_ptr() % 16 == 0 and t.data_ptr() % 16 == 4 and t.is_contiguous() and t.contiguous().data_ptr() == t.data_ptr()
+    return t
+
+
+def same_bits(a, b):
+    a, b = host(a), host(b)
+    return a.shape == b.shape and a.dtype == b.dtype == np.float32 and np.array_equal(a.view(np.int32), b.view(np.int32))
+
+
+def test_misaligned_rows_take_the_scalar_route(ME, be):
+    """C = 8 would take four floats per lane (130 rows: 260 threads, two blocks); operands one float off the alignment take
+    one, and give the same bytes: the union of two sets under all three operations and the broadcast add / multiply / copy,
+    forward and backward"""
+    rng = np.random.default_rng(130)
+    V, C = 130, 8
+    o = np.arange(V)
+    held = [o % 3 != 0, (o % 2 == 0) | (o % 3 == 0)]              # every union row has an operand; both absences occur
+    in_row = np.full((2, V), -1, np.int32)
+    out_rows = []
+    for i in range(2):
+        rows = rng.permutation(np.nonzero(held[i])[0]).astype(np.int32)       # set row -> union row
+        in_row[i, rows] = np.arange(rows.size, dtype=np.int32)
+        out_rows.append(rows)
+    feats = [rng.standard_normal((r.size, C)).astype(np.float32) for r in out_rows]
+    dout = rng.standard_normal((V, C)).astype(np.float32)
+    for op in (R.SUM, R.SUB, R.MUL):
+        a = be.union_combine(op, [dev(f) for f in feats], dev(in_row), V)
+        b = be.union_combine(op, [off_by_one_float(f) for f in feats], dev(in_row), V)
+        assert np.array_equal(host(a), R.combine_np(op, feats, in_row)), op
+        assert same_bits(a, b), op
+        for which in (0, 1):
+            other = (feats[1 - which], in_row[1 - which]) if op == R.MUL else None
+            a = be.union_combine_backward(op, which, dev(dout), dev(out_rows[which]),
+                                          *(() if other is None else (dev(other[0]), dev(other[1]))))
+            b = be.union_combine_backward(op, which, off_by_one_float(dout), dev(out_rows[which]),
+                                          *(() if other is None else (off_by_one_float(other[0]), dev(other[1]))))
+            want = R.combine_backward_np(op, which, dout, out_rows[which], *(() if other is None else other))
+            assert np.array_equal(host(a), want), (op, which)
+            assert same_bits(a, b), (op, which)
+
+    coords = big_cloud(rng, V, B=3, grid=12)
+    g_batch = np.array([2, 0], np.int32)                           # batch 1 has no global row
+    gc = np.zeros((2, 4), np.int32)
+    gc[:, 0] = g_batch
+    xt = ME.SparseTensor(dev(np.zeros((V, 1), np.float32)), coordinate_manager=ME.CoordinateManager(dev(coords)))
+    gt = ME.SparseTensor(dev(np.zeros((2, 1), np.float32)), coordinates=dev(gc))
+    grow, red = xt.coordinate_manager.broadcast_map(1, gt.coordinate_manager, 1)
+    assert (host(grow) == -1).any() and (host(grow) == 0).any() and (host(grow) == 1).any()      # (per row as it is held)
+    x = rng.standard_normal((V, C)).astype(np.float32)
+    g = rng.standard_normal((2, C)).astype(np.float32)
+    for mode in (R.ADD, R.MULTIPLY, R.COPY):
+        xa, xb = (None, None) if mode == R.COPY else (dev(x), off_by_one_float(x))
+        a = be.broadcast(mode, xa, dev(g), grow)
+        b = be.broadcast(mode, xb, off_by_one_float(g), grow)
+        assert np.array_equal(host(a), R.broadcast_np(mode, x, g, host(grow))), mode
+        assert same_bits(a, b), mode
+        xa, xb = (dev(x), off_by_one_float(x)) if mode == R.MULTIPLY else (None, None)
+        a = be.broadcast_reduce(dev(dout), 0, C, xa, *red)
+        b = be.broadcast_reduce(off_by_one_float(dout), 0, C, xb, *red)
+        dg = R.broadcast_dg_np(mode, dout, x, host(grow), 2, C)
+        assert np.abs(host(a).astype(np.float64) - dg).max() / np.abs(dg).max() <= RTOL, mode
+        assert same_bits(a, b), mode
+        if mode == R.MULTIPLY:                                     # the gradient of x: the same kernel on dout
+            assert same_bits(be.broadcast(mode, dev(dout), dev(g), grow),
+                             be.broadcast(mode, off_by_one_float(dout), off_by_one_float(g), grow))
+
+
+def test_concatenate_of_3_and_4_channels_reduces_by_the_scalar_route(ME):
+    """x of 3 channels in front of g of 4: the gradient of g is read from dout at leading dimension 7, column offset 3,
+    neither a multiple of four, so the reduction takes one float per lane"""
+    rng = np.random.default_rng(7)
+    V, Cx, Cg = 130, 3, 4
+    coords = big_cloud(rng, V, B=3, grid=12)
+    g_batch = np.array([2, 0], np.int32)
+    gc = np.zeros((2, 4), np.int32)
+    gc[:, 0] = g_batch
+    grow = R.grow_np(coords[:, 0], g_batch)
+    x = rng.standard_normal((V, Cx)).astype(np.float32)
+    g = rng.standard_normal((2, Cg)).astype(np.float32)
+    xt = ME.SparseTensor(dev(x).requires_grad_(True), coordinate_manager=ME.CoordinateManager(dev(coords)))
+    gt = ME.SparseTensor(dev(g).requires_grad_(True), coordinates=dev(gc))
+    y = ME.MinkowskiBroadcastConcatenation()(xt, gt)
+    want = R.broadcast_np(R.CAT, x, g, grow)
+    assert want.shape == (V, Cx + Cg) and np.array_equal(host(y.F), want)
+    dout = rng.standard_normal(want.shape).astype(np.float32)
+    y.F.backward(dev(dout))
+    assert np.array_equal(host(xt._F.grad), dout[:, :Cx])
+    dg = R.broadcast_dg_np(R.CAT, dout, x, grow, 2, Cx)
+    e = np.abs(host(gt._F.grad).astype(np.float64) - dg).max() / np.abs(dg).max()
+    print(f"concatenate 3 + 4: dg rel err {e:.3e} (bound {RTOL:.0e})")
+    assert e <= RTOL, e
+
+
 def _ms(fn, reps=20, warm=3):
     for _ in range(warm):
         fn()
