@@ -721,6 +721,46 @@ int ms3d_nbr_backward(int mode, const float *dout, const float *w, const unsigne
 int ms3d_nbr_wsum_backward_w(const float *dout, const float *x, const long long *idx, long N, int k, int C, float *dw,
                              ms3d_stream_t stream);
 
+/* ---- multi-head softmax attention over a neighbour index, with gradients (csrc/nattn.hip, on csrc/attn_core.h): the local
+ * self-attention of a point or voxel transformer over its k nearest rows, the cross-attention of picks over their groups.
+ * float32; q [N][C] on the target, k / v [V][C] the support rows as held, C = H * D, D <= 128; idx int64 [N][k] as above; bias
+ * float32 [N][k][H] (one additive term per entry and head) or NULL:
+ *   out[n][h][:] = sum_j softmax_j(scale * <q[n][h], k[i][h]> + bias[n][j][h]) v[i][h][:],  i = idx[n][j],
+ * over the slots with 0 <= i < V in ascending slot; the maximum is always subtracted before exp; lse [N][H] = m + log sum
+ * exp(s - m).  A query without a valid slot gives out = 0 and lse = 0; a query with one valid slot returns that v row bit for
+ * bit.  The bias of an invalid slot is never read.  A value of idx that is < 0 or >= V switches the gather off: nothing is read
+ * outside [0, V) in any pass.  Every direction is a gather with one writer per element: no atomics of any kind, no spin, no grid
+ * barrier, every loop counted, every sum in an order fixed by the shapes and the index alone; nothing is allocated inside a
+ * call and nothing of size N * k * C exists.
+ * ms3d_nattn_backward_q: the same sweep with p recomputed from lse; writes delta [N][H] (always; the residual the kv pass
+ *   subtracts, csrc/attn_core.h), dq = scale * (sum ds' k - delta * sum p k) (or NULL) and dbias [N][k][H] (or NULL):
+ *   p * (e - delta) for a valid slot, 0.0f for an invalid one, every element stored by exactly one thread.  The bits of p and e of
+ *   a slot wait in LDS until delta is known; the workgroup is sized from k alone so that the stash stays within 64 KiB.
+ * ms3d_nattn_backward_kv: a gather on the support side: row i walks entry_sorted[seg_start[i] .. seg_start[i + 1]) (the table of
+ *   ms3d_nbr_backward: entries e = n * k + j grouped by row, in the order the caller laid down) with p = exp(s - lse[n]),
+ *   dv += p dout[n], dk += p (e_val - delta[n]) q[n], dk scaled once at the store; an entry outside [0, N * k) is skipped; a row no
+ *   entry names stores exact zeros (no memset in front).  One of dk, dv may be NULL.  A row of more than T =
+ *   ms3d_nbr_chunk_entries() entries uses chunk_start / n_chunks as ms3d_nbr_backward does: each chunk is summed from 0 into a
+ *   partial (a dk row and a dv row) in ws, the row adds its partials from 0 in ascending chunk order; at most two launches.
+ *   ws: ms3d_nattn_ws_bytes(n_chunks, C) = 8 * n_chunks * C bytes, 16-byte aligned, never assumed zero; less: MS3D_E_WORKSPACE,
+ *   NULL or misaligned with n_chunks > 0: MS3D_E_UNSUPPORTED.
+ * Checks, in this order: k < 1, k > 254, H < 1, D < 1, D > 128, H * D or k * H or N * k beyond 2^31 - 1, V or N negative or
+ * beyond 2^31 - 1: MS3D_E_UNSUPPORTED; then N == 0 or V == 0: 0, nothing is launched and no pointer is looked at; then a NULL
+ * pointer that would be read or written: MS3D_E_UNSUPPORTED; a grid beyond 2^31 - 1 blocks: MS3D_E_UNSUPPORTED.  The 16-byte
+ * route is taken when D % 4 == 0 and every row pointer is 16-byte aligned, else the scalar one (two rounds for D > 64). */
+size_t ms3d_nattn_ws_bytes(long n_chunks, int C);
+int ms3d_nattn_forward(const float *q, const float *k, const float *v, const float *bias /*[N][k][H] or NULL*/,
+                       const long long *idx /*[N][k] held rows or < 0*/, long V, long N, int k_slots, int H, int D, float scale,
+                       float *out, float *lse /*[N][H]*/, ms3d_stream_t stream);
+int ms3d_nattn_backward_q(const float *q, const float *k, const float *v, const float *bias, const long long *idx,
+                          const float *out, const float *lse, const float *dout, long V, long N, int k_slots, int H, int D,
+                          float scale, float *dq /*or NULL*/, float *dbias /*[N][k][H] or NULL*/, float *delta /*[N][H], always*/,
+                          ms3d_stream_t stream);
+int ms3d_nattn_backward_kv(const float *q, const float *k, const float *v, const float *bias, const float *out, const float *lse,
+                           const float *delta, const float *dout, const long long *entry_sorted, const int *seg_start,
+                           const int *chunk_start, long n_chunks, long V, long N, int k_slots, int H, int D, float scale,
+                           float *dk, float *dv /*one may be NULL*/, void *ws, size_t ws_bytes, ms3d_stream_t stream);
+
 /* Pair list = tile-compacted form of an offset-major table, built once per table and shared by every convolution of
  * the level (forward, backward-data, backward-weight).  Output rows are cut into tiles of 64; per tile and offset the
  * valid (input row, output row) pairs are stored contiguously, padded to a multiple of 16 ("batch" = one MFMA group).

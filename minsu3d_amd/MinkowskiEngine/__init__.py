@@ -328,11 +328,60 @@ attention over a kNN graph once the caller has taken a softmax over [N, k] (an e
     nothing of size [N, k, C] is ever made.  CPU tensors take the same rules as torch expressions (x[idx.clamp(min=0)]
     masked, then reduced in slot order).  Modules without parameters: MinkowskiKNNPooling(k, mode="max") -- forward(x,
     queries=None, nmap=None) -- and MinkowskiKNNInterpolation(k=3, eps=1e-8) -- forward(x, y, nmap=None).
-    Out of scope (each raises where it can be asked for): per-head or per-channel weights [N, k, H], a fused softmax over the
-    slots or vector attention itself, a fused x_j - x_i / relative-position edge feature, a materialising differentiable
+    Out of scope (each raises where it can be asked for): per-head or per-channel weights [N, k, H] in neighbor_sum (multi-head
+    softmax attention over the slots: neighbor_attention, below), vector attention itself, a fused x_j - x_i /
+    relative-position edge feature, a materialising differentiable
     [N, k, C] gather with masked slots, float16 / bfloat16 rows, k above 254, gradients with respect to coordinates or
     distances, mixed voxel / point maps (knn_query refuses them); a backend without the kernels raises NotImplementedError
     naming ms3d_nbr_pool_forward for device tensors.
+
+Multi-head attention over a neighbour index -- the local self-attention of a point or voxel transformer over its k nearest rows,
+the cross-attention of picks over their groups; the block the FPS + kNN layers exist to feed (an engine extra, nothing of
+MinkowskiEngine's):
+
+    neighbor_attention(q, k, v, nmap, num_heads, bias=None, scale=None)
+    MinkowskiNeighborAttention(in_channels, num_heads, k=16, qkv_bias=True, pos_bias=True, pos_hidden=16)
+    NeighborMap.relative_positions()          # float32 [..., k, 3]
+
+    The rule, all of it: out[n, h, :] = sum_j softmax_j(scale * <q[n, h], k[i, h]> + bias[n, j, h]) v[i, h, :] over the slots j
+    of query n with i = idx[n, j] >= 0, in ascending slot; C = num_heads * D, scale = D ** -0.5 unless given; the maximum is
+    always subtracted before exp; a query without a valid slot is exact zeros, contributes to no gradient and receives none;
+    a query with a single valid slot returns that v row bit for bit.
+    k and v, the support: SparseTensors or TensorFields on the set the map was made for, or float32 [V, C] for a from_index
+    map; both of the same kind and set, with the same C.  q lives on the map's TARGET: the support's own set (queries=None),
+    y's set (a tensor y), or a plain float32 tensor [..., C] in the shape of the index's leading dimensions ([B, M] picks, a
+    from_index map).  The record knows its target beside its support (`target`, a keyword of the record that defaults to "not
+    checked"; knn_map and from_index fill it): a q on another set, or with another row count, is a ValueError on the host.
+    bias: float32 [..., k, num_heads] in the caller's numbering of the queries, differentiable; the value of an invalid slot is
+    never read and its gradient is 0; where the target holds its rows in another order it is permuted once (PermuteRowsFn), as
+    neighbor_sum permutes its weights.  The result is a SparseTensor / TensorField on the target's set, or a plain [..., C]
+    tensor.  Gradients go to q, k, v and bias; none to idx, d2 or the coordinates.  Frozen k and v skip their pass (the
+    transposed table and the chunk list are then never built); frozen q and bias skip theirs only when k and v are frozen
+    too, because the kv pass reads the per-row residual delta the q pass leaves (csrc/attn_core.h).
+    NeighborMap.relative_positions(): float32 [..., k, 3], the position of support row idx[n, j] minus the position of query
+    n -- integer coordinates cast to float32 (coordinate units) for voxels, the field's float32 points for points --, zeros in
+    the invalid slots, in the caller's numbering, not differentiable; made on first use by torch gathers of the three
+    coordinate columns and kept (knn_map remembers references to the position tensors of both sides, no copies); a
+    from_index map has none: ValueError.  It is the only input a position bias needs, and 3 channels wide, so it stays torch.
+    MinkowskiNeighborAttention: forward(x, nmap=None) = proj(neighbor_attention(q, k, v, nmap, num_heads, bias)) over
+    knn_map(x, k) or a given map (its k wins), (q, k, v) the column blocks of qkv(x); `qkv` nn.Linear(C, 3C), `proj`
+    nn.Linear(C, C), and with pos_bias `pos` = Sequential(Linear(3, pos_hidden), ReLU, Linear(pos_hidden, num_heads)) applied
+    to relative_positions(), its last layer zero-initialised so the block starts as plain attention.  Outside
+    prepare_conv_weights, like the other attention blocks.
+    csrc/nattn.hip on csrc/attn_core.h: three gathers with one writer per element, float32, rows read where they are held, no
+    atomics, every sum in an order fixed by the shapes and the index -- the same bytes on every run and whether the managers
+    hold their rows Morton-sorted or not.  Forward and the q pass: one group of lanes per (query, head), the slots four at a
+    time; dbias [N, k, H] is stored by the q pass after its sweep from the bits of p and e it stashed in LDS.  The kv pass
+    walks the record's transposed table per (support row, head); a row of more than ms3d_nbr_chunk_entries() entries goes
+    through the record's chunk list and a workspace of two partial rows per chunk.  Nothing of size [N, k, C] is made.  CPU
+    tensors (float32 or float64) take the same rule as a torch expression over the masked [N, k, C] gather, with autograd's
+    backward.
+    Refusals, each naming neighbor_attention: C % num_heads != 0, num_heads < 1, D > 128 (ValueError; k > 254 is the
+    record's), a bias of another shape, dtype or device, mixed k / v kinds or sets (ValueError), float16 / bfloat16 rows
+    (NotImplementedError); a backend without the kernels raises NotImplementedError naming ms3d_nattn_forward for device
+    tensors.
+    Out of scope: vector attention (per-channel weights from an MLP), a value-side position term v_j + delta_ij, attention
+    dropout, a value head dimension different from D, gradients to positions.
 
 Not supported (each raises NotImplementedError naming it): `axis_types` of a KernelGenerator, a region of more than 254
 offsets, a dense grid of more than 2^31 - 1 cells, to_sparse of a tensor
@@ -356,6 +405,7 @@ from .tensor import farthest_point_sampling  # noqa: F401  (engine extra: the se
 from .tensor import knn_query  # noqa: F401  (engine extra: the k nearest rows of a query's own sample)
 from .tensor import knn_map, NeighborMap  # noqa: F401  (engine extra: a neighbour index as a record the ops below read)
 from .functional import neighbor_pool, neighbor_sum, knn_interpolate  # noqa: F401  (engine extra: csrc/neighbor.hip)
+from .functional import neighbor_attention  # noqa: F401  (engine extra: csrc/nattn.hip)
 from .modules import (MinkowskiConvolution, MinkowskiConvolutionTranspose, MinkowskiBatchNorm,  # noqa: F401
                       MinkowskiReLU, prepare_conv_weights, release_conv_weights,
                       MinkowskiMaxPooling, MinkowskiAvgPooling, MinkowskiSumPooling, MinkowskiGlobalMaxPooling,
@@ -367,6 +417,7 @@ from .modules import (MinkowskiConvolution, MinkowskiConvolutionTranspose, Minko
                       MinkowskiInstanceNorm, MinkowskiStableInstanceNorm,
                       MinkowskiKernelAttention, kernel_attention, MinkowskiQueryAttention, query_attention,
                       MinkowskiVoxelAttention, voxel_attention, MinkowskiKNNPooling, MinkowskiKNNInterpolation,
+                      MinkowskiNeighborAttention,
                       MinkowskiToSparseTensor, MinkowskiToDenseTensor, MinkowskiToFeature,
                       MinkowskiELU, MinkowskiLeakyReLU, MinkowskiPReLU, MinkowskiSELU, MinkowskiCELU, MinkowskiGELU,
                       MinkowskiSiLU, MinkowskiTanh, MinkowskiSoftplus, MinkowskiHardswish, MinkowskiHardtanh,

@@ -1046,6 +1046,126 @@ def knn_interpolate(x, nmap, eps=1e-8):
     return neighbor_sum(x, nmap, w)
 
 
+class NeighborAttentionFn(torch.autograd.Function):
+    """out[n, h, :] = sum_j softmax_j(scale * <q[n, h], k[i, h]> + bias[n, j, h]) * v[i, h, :] over the valid slots i =
+    idx_held[n, j] of a NeighbourGroup (csrc/nattn.hip; float32, C = num_heads * D; a query without a valid slot is zero).  q
+    and bias in the row order of the record's idx_held, k / v as held.  Saves q, k, v, bias, out and the log-sum-exp lse [N, H];
+    the backward recomputes the probabilities from lse.  The q pass repeats the forward sweep (dq, dbias [N, k, H] and delta
+    [N, H], the residual the kv pass subtracts), the kv pass gathers through the record's table grouped by support row: no
+    atomics, the same bytes on every run.  Frozen q and bias skip the q pass unless the kv pass needs its delta (the pass then
+    stores nothing else); frozen k and v skip the kv pass, and the table and the chunk list are then never built."""
+
+    @staticmethod
+    def forward(ctx, q, k, v, bias, nmap, num_heads, scale):
+        q, k, v = q.contiguous(), k.contiguous(), v.contiguous()
+        bias = None if bias is None else bias.contiguous()
+        out, lse = get_backend().nattn_forward(q, k, v, bias, nmap, num_heads, scale)
+        ctx.save_for_backward(q, k, v, bias, out, lse)
+        ctx.geom = (nmap, num_heads, scale)
+        return out
+
+    @staticmethod
+    def backward(ctx, dout):
+        q, k, v, bias, out, lse = ctx.saved_tensors
+        nmap, H, scale = ctx.geom
+        need_q, need_k, need_v = ctx.needs_input_grad[:3]
+        need_b = bias is not None and ctx.needs_input_grad[3]
+        be = get_backend()
+        dout = dout.contiguous()
+        dq = dk = dv = db = None
+        if need_q or need_b or need_k or need_v:
+            dq, db, delta = be.nattn_backward_q(q, k, v, bias, nmap, out, lse, dout, H, scale, need_dq=need_q, need_dbias=need_b)
+            if need_k or need_v:
+                dk, dv = be.nattn_backward_kv(q, k, v, bias, nmap, out, lse, delta, dout, H, scale, need_dk=need_k,
+                                              need_dv=need_v)
+        return dq, dk, dv, db, None, None, None
+
+
+_NATTN_MAX_D = 128                       # the limit of csrc/nattn.hip
+
+
+def _nattn_query(q, nmap, name):
+    """-> the rows of q [N, C] in the row order of the record's idx_held, after the record has refused a q that does not live
+    on its target"""
+    if torch.is_tensor(q):
+        target = (None, None)
+        if q.dim() < 1 or tuple(q.shape[:-1]) != nmap.lead:
+            raise ValueError(f"{name}: plain q must be {list(nmap.lead) + ['C']}, one row per query of the map, got "
+                             f"{list(q.shape)}")
+        rows = q.reshape(nmap.N, q.size(-1))
+    elif hasattr(q, "coordinate_manager"):
+        target, rows = (q.coordinate_manager, q.tensor_stride), q._raw()
+    elif hasattr(q, "_shared"):
+        target, rows = (q._shared, None), q._F
+    else:
+        raise TypeError(f"{name}: q must be a SparseTensor, a TensorField or a float tensor [..., C], got {type(q).__name__}")
+    nmap.check_target(target, rows.size(0), rows.device)
+    return rows
+
+
+def neighbor_attention(q, k, v, nmap, num_heads, bias=None, scale=None):
+    """multi-head softmax attention of every query of nmap over its neighbours, with a per-entry, per-head additive bias: the
+    rules are in the package docstring."""
+    name = "neighbor_attention"
+    held = k if torch.is_tensor(k) else getattr(k, "_F", None)
+    if torch.is_tensor(held) and held.is_cuda and not hasattr(get_backend(), "nattn_forward"):
+        raise NotImplementedError(f"{name} on device tensors needs the HIP backend (ms3d_nattn_forward)")
+    krows = _nbr_input(k, nmap, name)
+    if type(k) is not type(v) and not (torch.is_tensor(k) and torch.is_tensor(v)):
+        raise ValueError(f"{name}: k and v must be of the same kind on the same set, got {type(k).__name__} and "
+                         f"{type(v).__name__}")
+    try:
+        vrows = _nbr_input(v, nmap, name)
+    except ValueError as e:
+        raise ValueError(f"{name}: k and v must live on the same set -- {e}") from None
+    qrows = _nattn_query(q, nmap, name)
+    C = krows.size(1)
+    if vrows.size(1) != C or qrows.size(1) != C:
+        raise ValueError(f"{name}: q, k and v must have the same number of channels, got {qrows.size(1)}, {C}, {vrows.size(1)}")
+    if isinstance(num_heads, bool) or not isinstance(num_heads, int) or num_heads < 1:
+        raise ValueError(f"{name}: num_heads must be a Python int >= 1, got {num_heads!r}")
+    if C % num_heads != 0:
+        raise ValueError(f"{name}: {C} channels do not divide into num_heads={num_heads}")
+    H, D = num_heads, C // num_heads
+    if D > _NATTN_MAX_D:
+        raise ValueError(f"{name}: head dimension D = {D} is above the kernels' limit of {_NATTN_MAX_D}")
+    if qrows.dtype != krows.dtype or vrows.dtype != krows.dtype or qrows.device != krows.device:
+        if torch.float16 in (qrows.dtype, vrows.dtype) or torch.bfloat16 in (qrows.dtype, vrows.dtype):
+            raise NotImplementedError(f"{name}: float16 / bfloat16 rows (float32; float64 on the CPU path)")
+        raise ValueError(f"{name}: q, k and v must share one dtype and device, got {qrows.dtype}, {krows.dtype}, {vrows.dtype}")
+    b = None
+    if bias is not None:
+        want = nmap.lead + (nmap.k, H)
+        if not torch.is_tensor(bias) or tuple(bias.shape) != want:
+            raise ValueError(f"{name}: bias must be a tensor {list(want)} (one term per query, slot and head), got "
+                             f"{list(bias.shape) if torch.is_tensor(bias) else type(bias).__name__}")
+        if bias.dtype != krows.dtype or bias.device != krows.device:
+            raise ValueError(f"{name}: bias is {bias.dtype} on {bias.device}, the rows {krows.dtype} on {krows.device}")
+        b = bias.reshape(nmap.N, nmap.k * H)
+        if nmap.row_perm is not None:            # the caller's query rows -> the order the target set holds them in
+            b = PermuteRowsFn.apply(b, *nmap.row_perm)
+        b = b.view(nmap.N, nmap.k, H)
+    scale = float(D ** -0.5 if scale is None else scale)
+    if krows.is_cuda:
+        if nmap.N == 0 or nmap.V == 0:           # no launch on an empty grid; the inputs stay in the graph, their gradients are zeros
+            zero = (qrows.sum() + krows.sum() + vrows.sum() + (0 if b is None else b.sum())) * 0
+            return _nbr_result(zero.expand(nmap.N, C), nmap)
+        return _nbr_result(NeighborAttentionFn.apply(qrows, krows, vrows, b, nmap, H, scale), nmap)
+    kg, ok = _nbr_gathered(krows, nmap)          # the CPU path: the same rule as a torch expression; makes [N, k, C]
+    vg, _ = _nbr_gathered(vrows, nmap)
+    s = torch.einsum("nhd,njhd->njh", qrows.view(nmap.N, H, D), kg.reshape(nmap.N, nmap.k, H, D)) * scale
+    if b is not None:
+        s = s + torch.where(ok.unsqueeze(-1), b, torch.zeros((), dtype=b.dtype))     # an invalid slot's bias is never used
+    s = s.masked_fill(~ok.unsqueeze(-1), float("-inf"))
+    m = s.amax(1, keepdim=True)
+    m = torch.where(torch.isfinite(m), m, torch.zeros((), dtype=m.dtype))            # a query without a valid slot: exp(-inf) = 0
+    p = torch.exp(s - m.detach())
+    den = p.sum(1, keepdim=True)
+    p = torch.where(den > 0, p / torch.where(den > 0, den, torch.ones((), dtype=den.dtype)), p)
+    out = torch.einsum("njh,njhd->nhd", p, vg.reshape(nmap.N, nmap.k, H, D)).reshape(nmap.N, C)
+    return _nbr_result(out, nmap)
+
+
 class DenseScatterFn(torch.autograd.Function):
     """rows -> grid (SparseTensor.dense): out [B, C, X, Y, Z] with out[b, :, cell] = x[cell_row[cell]], zeros where the cell has
     no row (csrc/dense.hip).  cell_row / row_cell: the two directions of one cell map over the rows as the engine HOLDS them.

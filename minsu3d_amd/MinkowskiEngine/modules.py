@@ -1073,6 +1073,49 @@ class MinkowskiKNNInterpolation(nn.Module):
         return f"k={self.k}, eps={self.eps}"
 
 
+class MinkowskiNeighborAttention(nn.Module):
+    """The self-attention block over the kNN graph of a SparseTensor or TensorField (an engine extra): forward(x, nmap=None) =
+    proj(neighbor_attention(q, k, v, nmap, num_heads, bias)) with (q, k, v) = the three C-wide column blocks of qkv(x) and nmap
+    = knn_map(x, k) unless one is given (its k wins).  `qkv` is nn.Linear(C, 3C) (bias when qkv_bias), `proj` nn.Linear(C, C);
+    with pos_bias, `pos` = Sequential(Linear(3, pos_hidden), ReLU, Linear(pos_hidden, num_heads)) turns
+    nmap.relative_positions() into the bias [N, k, num_heads]; its last layer starts at zero, so the block starts as plain
+    attention.  scale = (C / num_heads) ** -0.5.
+
+    Not a _ConvBase: prepare_conv_weights lays out (K, cin, cout) weight images, and this block has none."""
+
+    def __init__(self, in_channels, num_heads, k=16, qkv_bias=True, pos_bias=True, pos_hidden=16):
+        super().__init__()
+        name = type(self).__name__
+        if isinstance(k, bool) or not isinstance(k, int) or k < 1:
+            raise ValueError(f"{name}: k must be a Python int >= 1, got {k!r}")
+        if isinstance(num_heads, bool) or not isinstance(num_heads, int) or num_heads < 1 or in_channels % num_heads != 0:
+            raise ValueError(f"{name}: {in_channels} channels do not divide into num_heads={num_heads}")
+        self.in_channels = self.out_channels = in_channels
+        self.num_heads, self.k = num_heads, k
+        self.qkv = nn.Linear(in_channels, 3 * in_channels, bias=qkv_bias)
+        self.proj = nn.Linear(in_channels, in_channels)
+        self.pos = None
+        if pos_bias:
+            self.pos = nn.Sequential(nn.Linear(3, pos_hidden), nn.ReLU(), nn.Linear(pos_hidden, num_heads))
+            with torch.no_grad():
+                self.pos[2].weight.zero_()
+                self.pos[2].bias.zero_()
+
+    def forward(self, x, nmap=None):
+        if nmap is None:
+            nmap = knn_map(x, self.k)
+        C = self.in_channels
+        rows = x._raw() if isinstance(x, SparseTensor) else x._F
+        like = x._like
+        q, k, v = (like(t.contiguous()) for t in self.qkv(rows).split(C, dim=1))
+        bias = None if self.pos is None else self.pos(nmap.relative_positions())
+        y = Fn.neighbor_attention(q, k, v, nmap, self.num_heads, bias)
+        return like(self.proj(y._raw() if isinstance(y, SparseTensor) else y._F))
+
+    def extra_repr(self):
+        return f"in={self.in_channels}, num_heads={self.num_heads}, k={self.k}, pos_bias={self.pos is not None}"
+
+
 class _GlobalPoolBase(nn.Module):
     """one output row per batch index present, in ascending batch order.  The result is a plain tensor wrapper on its own
     coordinate set (batch index, 0, 0, 0); rows are grouped by batch through a cached stable sort, not assumed contiguous."""

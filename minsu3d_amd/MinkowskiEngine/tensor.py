@@ -1834,25 +1834,30 @@ def _nbr_set(t):
 
 
 def knn_map(x, k, queries=None, max_squared_distance=None):
-    """knn_query(x, k, queries, max_squared_distance) wrapped as a NeighborMap: the record ME.neighbor_pool, neighbor_sum and
-    knn_interpolate read.  It remembers the support set (x's coordinate set or field) and the target the results live on:
+    """knn_query(x, k, queries, max_squared_distance) wrapped as a NeighborMap: the record ME.neighbor_pool, neighbor_sum,
+    knn_interpolate and neighbor_attention read.  It remembers references to the position tensors of both sides (for
+    NeighborMap.relative_positions(); no copies), the support set (x's coordinate set or field) and the target the results live on:
     x's own set (queries=None), y's set (a SparseTensor / TensorField y), or none -- plain [B, M, C] results -- for an int64
     [B, M] tensor of picks.  The index is translated into the rows as both sets HOLD them here, once, by torch gathers; the
     transposed table of the backward is made on first use and kept, so every layer over one graph shares it.  Arguments,
     refusals and host reads are knn_query's."""
     idx, d2 = knn_query(x, k, queries, max_squared_distance)
     support, wrap, group = _nbr_set(x)
+    data = _SupportSet(x, "knn_map", "x").data               # positions as held: references, for relative_positions()
     row_map = row_held_of = None
     if queries is None:
-        target = group
+        target, token, positions = group, support, (data, data, None)
     elif torch.is_tensor(queries):
-        target, wrap = None, None
+        target, wrap, token = None, None, (None, None)
+        held = queries.to(data.device).reshape(-1).clamp(0, max(group.V - 1, 0))
+        positions = (data, data, held if group.held_of is None else group.held_of[held])
     else:
-        _, wrap, target = _nbr_set(queries)
+        token, wrap, target = _nbr_set(queries)
+        positions = (data, _SupportSet(queries, "knn_map", "queries").data, None)
     if target is not None and target.row_map is not None:
         row_map, row_held_of = target.row_map, target.held_of
     return NeighbourGroup(idx, group.V, d2, held_of=group.held_of, row_map=row_map, row_held_of=row_held_of, support=support,
-                          wrap=wrap)
+                          wrap=wrap, target=token, positions=positions)
 
 
 def _dense_input(x, format, device):

@@ -29,7 +29,7 @@ def lib():
                      "ms3d_chconv_wgrad_ws_floats", "ms3d_kattn_dbias_ws_floats", "ms3d_inorm_workspace_bytes",
                      "ms3d_dense_occupancy_workspace_bytes", "ms3d_kmap_pairs_workspace_bytes",
                      "ms3d_qattn_ws_floats", "ms3d_qattn_backward_ws_floats", "ms3d_vattn_backward_kv_ws_floats",
-                     "ms3d_fps_ws_bytes", "ms3d_knn_ws_bytes", "ms3d_nbr_ws_bytes"):
+                     "ms3d_fps_ws_bytes", "ms3d_knn_ws_bytes", "ms3d_nbr_ws_bytes", "ms3d_nattn_ws_bytes"):
             if hasattr(_lib, name):
                 getattr(_lib, name).restype = C.c_size_t
         if hasattr(_lib, "ms3d_qattn_chunks"):

@@ -283,13 +283,23 @@ class NeighbourGroup:
       support       what the index points into, compared by check(); wrap: features [N, C] in the target's held order -> the
                     op's result (None: a plain tensor [..., C]); row_perm: (held -> caller, caller -> held) rows of the target
                     where the two orders differ, else None
-    Made on first use and kept: the transposed table (entry_sorted int64 [E], seg_start int32 [V + 1]: the entries e = n * k + j
+      target        what the QUERIES live on, compared by check_target() (neighbor_attention's q); UNCHECKED when nobody said
+    Made on first use and kept: relative_positions() (from the position tensors knn_map left references to), the transposed
+    table (entry_sorted int64 [E], seg_start int32 [V + 1]: the entries e = n * k + j
     with idx_held >= 0 grouped by support row, ascending e inside a row -- in the caller's numbering of the queries where the
     target holds them in another order -- one stable sort, as CoordinateManager.interpolation_map builds its group) and, only when a feature backward runs on the device, the chunk list (chunk_start int32
     [V + 1], n_chunks: the cut of the rows that have more than ms3d_nbr_chunk_entries() entries -- one host read)."""
 
-    def __init__(self, idx, V, d2=None, held_of=None, row_map=None, row_held_of=None, support=(None, None), wrap=None):
+    UNCHECKED = object()                 # a target nobody named: check_target compares the row count and the device only
+
+    def __init__(self, idx, V, d2=None, held_of=None, row_map=None, row_held_of=None, support=(None, None), wrap=None,
+                 target=UNCHECKED, positions=None):
+        """target: the identity of the set the QUERIES live on, in the form of `support` ((None, None): plain rows), read by
+        check_target -- what an op with an input on the target side (neighbor_attention's q) compares.  positions: (support
+        data [V, 4], target data [*, 4], target rows) as held, batch column first -- references, no copies; target rows: None
+        (query n is row n of the target data) or int64 [N] rows of it -- what relative_positions() gathers on first use."""
         assert idx.dtype == torch.int64 and idx.dim() >= 1 and 1 <= idx.size(-1) <= NBR_MAX_K
+        self.target, self._positions = target, positions
         assert d2 is None or tuple(d2.shape) == tuple(idx.shape)
         self.idx, self.d2, self.V, self.k, self.device = idx, d2, int(V), idx.size(-1), idx.device
         self.lead = tuple(idx.shape[:-1])
@@ -322,7 +332,41 @@ class NeighbourGroup:
             raise ValueError(f"NeighborMap.from_index: d2 must have the shape of idx, {list(idx.shape)}")
         if idx.numel() and int(idx.max()) >= num_rows:
             raise ValueError(f"NeighborMap.from_index: idx holds {int(idx.max())}, which is no row of {num_rows}")
-        return cls(idx, num_rows, None if d2 is None else d2.to(idx.device))
+        return cls(idx, num_rows, None if d2 is None else d2.to(idx.device), target=(None, None))
+
+    def check_target(self, target, N, device):
+        """refuses query-side rows of another set, another number of rows or another device, on the host"""
+        mine = self.target
+        if mine is not NeighbourGroup.UNCHECKED and (mine[0] is not target[0] or mine[1] != target[1]):
+            raise ValueError("this NeighborMap's queries live on another set than q: with queries=None q is on x's own set, with "
+                             "a tensor y on y's set, with [B, M] picks or a from_index map q is a plain tensor [..., C]")
+        if N != self.N or device != self.device:
+            raise ValueError(f"a NeighborMap of {self.N} queries on {self.device} for {N} query rows on {device}")
+
+    def relative_positions(self):
+        """float32 [..., k, 3] in the caller's numbering of the queries: the position of support row idx[n, j] minus the position
+        of query n -- integer coordinates cast to float32 (coordinate units) for voxels, the field's float32 points for
+        points; zeros in the invalid slots.  Not differentiable.  Made on first use by torch gathers of the three coordinate
+        columns and kept.  A from_index map knows no positions: ValueError."""
+        rel = self.__dict__.get("_relpos")
+        if rel is None:
+            if self._positions is None:
+                raise ValueError("NeighborMap.relative_positions: a map made by from_index (or built without positions) holds no "
+                                 "coordinates; make it with knn_map")
+            sup, tgt, rows = self._positions
+            with torch.no_grad():
+                ok = self.idx_held >= 0
+                if self.N == 0 or self.V == 0:
+                    rel = torch.zeros((self.N, self.k, 3), dtype=torch.float32, device=self.device)
+                else:
+                    at = sup[:, 1:][self.idx_held.clamp(min=0)].to(torch.float32)                  # [N, k, 3]
+                    own = (tgt[:, 1:] if rows is None else tgt[:, 1:][rows]).to(torch.float32)     # [N, 3], held order
+                    rel = torch.where(ok.unsqueeze(-1), at - own.unsqueeze(1), torch.zeros((), dtype=torch.float32,
+                                                                                           device=self.device))
+                    if self.row_perm is not None:
+                        rel = rel[self.row_perm[1]]
+                rel = self.__dict__["_relpos"] = rel.reshape(*self.lead, self.k, 3).contiguous()
+        return rel
 
     def check(self, support, V, device):
         """refuses features of another set, another number of rows or another device, on the host: a stale record never
@@ -1771,6 +1815,71 @@ class _HipEngine:
                                                      int(group.k), int(x.size(1)), _lib.ptr(dw), _lib.stream_handle()),
                    "ms3d_nbr_wsum_backward_w")
         return dw
+
+    # ---- multi-head attention over a neighbour index (csrc/nattn.hip); group: the NeighbourGroup of the index.  q [N, C] in the
+    # row order of idx_held, k / v [V, C] as held, bias [N, k, H] in the row order of idx_held or None
+    def _nattn_check(self, q, k, v, bias, group, H):
+        self._nbr_rows(q, group.N, "q")
+        self._nbr_rows(k, group.V, "k")
+        self._nbr_rows(v, group.V, "v")
+        c = q.size(1)
+        assert k.size(1) == c and v.size(1) == c and H >= 1 and c % H == 0 and group.device == q.device
+        if bias is not None:
+            assert bias.is_cuda and bias.dtype == torch.float32 and bias.is_contiguous() and \
+                tuple(bias.shape) == (group.N, group.k, H), "bias"
+        return c // H
+
+    def nattn_forward(self, q, k, v, bias, group, H, scale):
+        """-> (out [N, C], lse [N, H]): softmax over the valid slots of scale * <q[n, h], k[i, h]> + bias[n, j, h], applied to v"""
+        d = self._nattn_check(q, k, v, bias, group, H)
+        out = torch.empty_like(q)
+        lse = torch.empty((group.N, H), dtype=torch.float32, device=q.device)
+        _lib.check(self.lib.ms3d_nattn_forward(_lib.ptr(q), _lib.ptr(k), _lib.ptr(v), _lib.ptr(bias), _lib.ptr(group.idx_held),
+                                               C.c_long(group.V), C.c_long(group.N), int(group.k), int(H), int(d),
+                                               C.c_float(scale), _lib.ptr(out), _lib.ptr(lse), _lib.stream_handle()),
+                   "ms3d_nattn_forward")
+        return out, lse
+
+    def nattn_backward_q(self, q, k, v, bias, group, out, lse, dout, H, scale, need_dq=True, need_dbias=True):
+        """-> (dq [N, C] or None, dbias [N, k, H] or None, delta [N, H]); delta, the residual sum_j p <dout, v - out> per query
+        and head, is what nattn_backward_kv reads.  dbias: 0 in the invalid slots, every element stored once"""
+        d = self._nattn_check(q, k, v, bias, group, H)
+        self._nbr_rows(dout, group.N, "dout")
+        assert tuple(dout.shape) == tuple(q.shape) == tuple(out.shape)
+        need_dbias = need_dbias and bias is not None
+        dq = torch.empty_like(q) if need_dq else None
+        dbias = torch.empty_like(bias) if need_dbias else None
+        delta = torch.empty((group.N, H), dtype=torch.float32, device=q.device)
+        _lib.check(self.lib.ms3d_nattn_backward_q(_lib.ptr(q), _lib.ptr(k), _lib.ptr(v), _lib.ptr(bias), _lib.ptr(group.idx_held),
+                                                  _lib.ptr(out), _lib.ptr(lse), _lib.ptr(dout), C.c_long(group.V),
+                                                  C.c_long(group.N), int(group.k), int(H), int(d), C.c_float(scale),
+                                                  _lib.ptr(dq), _lib.ptr(dbias), _lib.ptr(delta), _lib.stream_handle()),
+                   "ms3d_nattn_backward_q")
+        return dq, dbias, delta
+
+    def nattn_backward_kv(self, q, k, v, bias, group, out, lse, delta, dout, H, scale, need_dk=True, need_dv=True):
+        """-> (dk, dv) [V, C] (None where not asked for): a gather through the record's table grouped by support row; rows of
+        more than nbr_chunk_entries() entries through chunk partials (group.chunks)"""
+        d = self._nattn_check(q, k, v, bias, group, H)
+        self._nbr_rows(dout, group.N, "dout")
+        assert tuple(dout.shape) == tuple(q.shape) == tuple(out.shape) and (need_dk or need_dv)
+        c, dev = q.size(1), q.device
+        entry_sorted, seg_start = group.table
+        if entry_sorted.numel() == 0:            # no valid slot anywhere: nothing to walk (and no pointer to pass)
+            return (torch.zeros_like(k) if need_dk else None), (torch.zeros_like(v) if need_dv else None)
+        chunk_start, n_chunks = group.chunks
+        dk = torch.empty_like(k) if need_dk else None
+        dv = torch.empty_like(v) if need_dv else None
+        need = self.lib.ms3d_nattn_ws_bytes(C.c_long(n_chunks), int(c))
+        ws = self.ws.get("nattn", need, dev) if need else None
+        _lib.check(self.lib.ms3d_nattn_backward_kv(_lib.ptr(q), _lib.ptr(k), _lib.ptr(v), _lib.ptr(bias), _lib.ptr(out),
+                                                   _lib.ptr(lse), _lib.ptr(delta), _lib.ptr(dout), _lib.ptr(entry_sorted),
+                                                   _lib.ptr(seg_start), _lib.ptr(chunk_start), C.c_long(n_chunks),
+                                                   C.c_long(group.V), C.c_long(group.N), int(group.k), int(H), int(d),
+                                                   C.c_float(scale), _lib.ptr(dk), _lib.ptr(dv), _lib.ptr(ws),
+                                                   C.c_size_t(ws.numel() if need else 0), _lib.stream_handle()),
+                   "ms3d_nattn_backward_kv")
+        return dk, dv
 
     # ---- instance normalisation over the batch grouping of a coordinate set (csrc/inorm.hip)
     def inorm_forward(self, x, group, eps, weight, bias):
